@@ -32,6 +32,10 @@ Rank 0 prints ONE JSON line.
                 a stated time budget and in a child process with a hard wall-clock limit (if the budget bites the bs-1
                 figure is reported as well and said so); plus the config-1 plumbing row (Market 128^2, bs 2, 30-channel
                 64x64 appearance input).  Rank 0, N = 1 only.
+  --dump-outputs DIR  after the timed steps rank 0 writes what the LAST timed step computed to DIR/<name>.npy (see
+                dump_outputs): the values train_fn returned and a fixed sample of the updated parameters.  Inputs, weights,
+                dropout masks and posterior noise are all seeded, so two builds run with the same arguments can be compared
+                array for array.
 """
 import argparse
 import json
@@ -83,8 +87,17 @@ def parse():
                          "fp32-input-MFMA precision, 10 replayed steps each on this box)")
     ap.add_argument("--cpu-budget", type=float, default=100.0, help="seconds of CPU work allowed for the bs-16 baseline")
     ap.add_argument("--cpu-threads", type=int, default=64, help="cap on the CPU baseline's threads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- the values train_fn returned and "
+                         "a fixed seeded sample of the parameters it updated -- as DIR/<name>.npy (float32 / float64), so that "
+                         "two builds can be compared output for output (the inputs are seeded: the same arguments, the same inputs)")
     ap.add_argument("--cpu-child", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed region is --steps training steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def make_config(args):
@@ -663,6 +676,48 @@ def timed_steps(trainer, batch, warmup, steps, sync_all):
     return time.perf_counter() - t0, out
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: the whole dump stays below this
+DUMP_PARAM_SAMPLE = 4096      # elements per parameter tensor in the dumped sample (smaller tensors: all of them)
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs: what the last timed step computed, as .npy files under ``path``.
+
+    - ``out_<key>.npy``: every value train_fn returned (loss terms, learning_rate, gamma, imax); float tensors keep their
+      dtype (float32 / float64), anything else is written as float64.
+    - ``params_sample.npy`` (float32): the parameters the step updated, in ``model.state_dict()`` order; of a tensor with more
+      than DUMP_PARAM_SAMPLE elements only DUMP_PARAM_SAMPLE of them, at sorted indices drawn without replacement from a
+      generator seeded with the tensor's position -- the same elements in every run of the same configuration.
+    Called right after the timed steps (a replayed graph's outputs are valid until the next train_fn call).
+    -> {file name: bytes}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for k, v in out.items():
+        t = v.detach().cpu() if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        arrays[f"out_{k}"] = t.numpy()
+    vals = []
+    for pos, p in enumerate(model.state_dict().values()):
+        if not p.is_floating_point():
+            continue
+        flat = p.detach().reshape(-1).float().cpu()
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            g = torch.Generator().manual_seed(pos)
+            flat = flat[torch.randperm(flat.numel(), generator=g)[:DUMP_PARAM_SAMPLE].sort().values]
+        vals.append(flat)
+    arrays["params_sample"] = torch.cat(vals).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes would exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    sizes = {}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+        sizes[name + ".npy"] = int(a.nbytes)
+    return sizes
+
+
 class GraphGuard:
     """In-process watchdog of the graph-replay phase of a multi-rank run (see main): armed before the first replay of a graph
     that holds RCCL collectives, cancelled when the timed replays have come back.  On expiry rank 0 writes the eager result it
@@ -927,6 +982,10 @@ def main():
     if guard is not None:
         guard.cancel()                     # the replayed steps came back: the graph measurement is the result
     heartbeat("timed steps done")
+    if args.dump_outputs and rank == 0:    # before any further train_fn call: the step's outputs and parameters as it left them
+        sizes = dump_outputs(args.dump_outputs, out, trainer.vunet)
+        print(f"bench.py: wrote {len(sizes)} arrays ({sum(sizes.values())} bytes) of the last timed step to {args.dump_outputs}",
+              file=sys.stderr)
     # host time to ISSUE one step: measured on steps that start with an empty device queue (inside the timed loop the host
     # runs ahead until the launch queue is full and is then throttled to the GPU's pace, which says nothing about the host)
     issue = []

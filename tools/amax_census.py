@@ -2,8 +2,8 @@
 """Which convolutions of a bs-16 training step still run their own |x|-maxima pass (vunet_absmax_partials) in the fp16 scheme:
 caller, shapes of the sources, whether each carries a producer tag (needs an MI355X).  r02: 37 per step -- inputs produced by
 the 3-channel / 1x1 / stride-2 kernels (no tags), two-source layers, gradients summed by the autograd engine."""
-import sys, copy, contextlib, collections, traceback, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, copy, contextlib, collections, traceback, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from behavior_driven_video_synthesis_amd import ops
 from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import DEFAULT_CONFIG, ShapePoseNet, synthetic_batch
 cfg = copy.deepcopy(DEFAULT_CONFIG)

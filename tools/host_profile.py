@@ -1,5 +1,5 @@
-import cProfile, pstats, sys, io, torch
-sys.path.insert(0, "/root/repo")
+import cProfile, os, pstats, sys, io, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import DEFAULT_CONFIG, ShapePoseNet, synthetic_batch
 import copy, contextlib
 cfg = copy.deepcopy(DEFAULT_CONFIG)

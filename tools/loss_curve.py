@@ -5,8 +5,8 @@
 
 The first steps agree to 4-5 digits across schemes; later the trajectories separate chaotically (the KL term of a single
 repeated batch spikes at different steps in every scheme, fp32 included) -- not a precision effect."""
-import sys, copy, contextlib, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, copy, contextlib, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from behavior_driven_video_synthesis_amd import ops
 from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import DEFAULT_CONFIG, ShapePoseNet, synthetic_batch
 mode = sys.argv[1]

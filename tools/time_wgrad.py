@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the split weight-gradient kernel (h2 scheme) on the bs-16 layer shapes (needs an MI355X):  python tools/time_wgrad.py"""
 import ctypes, os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from behavior_driven_video_synthesis_amd import ops
 ops.set_conv_precision("h2")
 for name, n, c1, cout, h, w in [("128ch 128^2", 16, 128, 128, 128, 128), ("64ch 256^2", 16, 64, 64, 256, 256), ("256ch 64^2", 16, 256, 256, 64, 64), ("32ch 256^2", 16, 32, 32, 256, 256), ("64+64->64 128^2", 16, 128, 64, 128, 128),

@@ -2,11 +2,12 @@
 """Time the direct weight-gradient kernel (stride-2, 1x1 and small-map layers of the bs-16 step; needs an MI355X):
 python tools/time_wgrad_direct.py     (VUNET_HIP_LIB=<variant> for A/B builds; 20 back-to-back launches per shape)"""
 import ctypes
+import os
 import sys
 
 import torch
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from behavior_driven_video_synthesis_amd import ops  # noqa: E402
 
 ops.set_conv_precision("h2")
