@@ -62,6 +62,7 @@ __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(
 __device__ __forceinline__ float seq_act(float v, int act) {
   if (act == 1) return fmaxf(v, 0.01f * v);   // nn.LeakyReLU() default slope 0.01 (lib/modules.py:244)
   if (act == 2) return tanhf(v);              // the scale nets' head (lib/modules.py:252-253)
+  if (act == 3) return fmaxf(v, 0.f);         // nn.ReLU: the adversarial pose regressor (models/pose_behavior_rnn.py:47-62)
   return v;
 }
 
@@ -661,7 +662,7 @@ static int seq_linear_launch(const vunet_seq_linear_desc* d, int layout, const f
   if (d->nets < 1 || d->nets > 2 || (d->nets == 2 && !w1)) return VUNET_ERR_ARG;
   if (d->B < 1 || d->B > 16 * SEQ_MAX_NB || d->M < 16 || d->M % 16) return VUNET_ERR_ARG;
   if (d->S < 1 || d->S > 8 || d->K < 32 || d->K % (32 * d->S) || d->ldx < d->K || d->ldx % 4) return VUNET_ERR_ARG;
-  if (d->act0 < 0 || d->act0 > 2 || d->act1 < 0 || d->act1 > 2) return VUNET_ERR_ARG;
+  if (d->act0 < 0 || d->act0 > 3 || d->act1 < 0 || d->act1 > 3) return VUNET_ERR_ARG;
   SeqLinearArgs a;
   a.w[0] = w0;
   a.w[1] = w1;

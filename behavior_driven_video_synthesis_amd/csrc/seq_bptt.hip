@@ -6,6 +6,7 @@
 // (dW = sum_t dgates_t^T [x_t | 0 | h_t]).  Interface: include/vunet_seq_train.h.
 #include "common.h"
 #include "../../include/vunet_seq_train.h"
+#include "../../include/vunet_seq_reg.h"
 
 namespace {
 
@@ -172,9 +173,10 @@ __global__ __launch_bounds__(256) void seq_vae_loss_parts_kernel(const float* __
 }
 
 // one wave: the partial sums in index order -> the scalars, per-step errors, and gamma for the next step
+// wkl: the KL term's weight -- gamma itself (vunet_seq_vae_loss), or a fixed weight while gamma still advances (cvae: True)
 __global__ __launch_bounds__(64) void seq_vae_loss_final_kernel(const float* __restrict__ part, int B, int T, int n, int H, float recon_weight,
-                                                                float* __restrict__ gamma, const float* __restrict__ imax, float gamma_step,
-                                                                float* __restrict__ scalars, float* __restrict__ per_seq) {
+                                                                const float* wkl, float* gamma, const float* __restrict__ imax,
+                                                                float gamma_step, float* __restrict__ scalars, float* __restrict__ per_seq) {
   const int lane = threadIdx.x;
   float r = 0.f, k = 0.f;
   for (int t = lane; t < T; t += 64) {
@@ -194,11 +196,11 @@ __global__ __launch_bounds__(64) void seq_vae_loss_final_kernel(const float* __r
   if (lane == 0) {
     scalars[4] = sm / ((float)B * (float)H);
     scalars[5] = sl / ((float)B * (float)H);
-    const float recon = r / ((float)B * (float)T * (float)n), kl = k / (float)B, g = *gamma;
-    scalars[0] = recon_weight * recon + g * kl;
+    const float recon = r / ((float)B * (float)T * (float)n), kl = k / (float)B, w = *wkl, g = *gamma;
+    scalars[0] = recon_weight * recon + w * kl;
     scalars[1] = recon;
     scalars[2] = kl;
-    scalars[3] = g;
+    scalars[3] = w;
     if (gamma_step > 0.f) *gamma = fmaxf(g - gamma_step * (*imax - kl), 0.f);   // experiments/behavior_net.py:111-116
   }
 }
@@ -302,8 +304,25 @@ extern "C" int vunet_seq_vae_loss(const float* xs, const float* target, const fl
   hipStream_t st = (hipStream_t)stream;
   VUNET_LAUNCH(seq_vae_loss_parts_kernel, dim3(T + B), dim3(256), 0, st, xs, target, mu, logstd, B, T, n, H, recon_weight, gamma_dev, part,
                dxs, dmu, dlogstd);
-  VUNET_LAUNCH(seq_vae_loss_final_kernel, dim3(1), dim3(64), 0, st, part, B, T, n, H, recon_weight, gamma_dev, imax_dev, gamma_step, scalars,
-               per_seq);
+  VUNET_LAUNCH(seq_vae_loss_final_kernel, dim3(1), dim3(64), 0, st, part, B, T, n, H, recon_weight, gamma_dev, gamma_dev, imax_dev, gamma_step,
+               scalars, per_seq);
+  return vunet_check_launch();
+}
+
+// include/vunet_seq_reg.h: the same loss with the KL weight read from kl_weight_dev (``cvae: True`` -- a weight of 1) while gamma
+// still advances
+extern "C" int vunet_seq_vae_loss_w(const float* xs, const float* target, const float* mu, const float* logstd, int32_t B, int32_t T,
+                                    int32_t n, int32_t H, float recon_weight, const float* kl_weight_dev, float* gamma_dev,
+                                    const float* imax_dev, float gamma_step, float* part, float* scalars, float* per_seq, float* dxs,
+                                    float* dmu, float* dlogstd, void* stream) {
+  if (!xs || !target || !mu || !logstd || !kl_weight_dev || !gamma_dev || !part || !scalars || B < 1 || B > 64 || T < 1 || n < 1 || H < 1)
+    return VUNET_ERR_ARG;
+  if (gamma_step > 0.f && !imax_dev) return VUNET_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  VUNET_LAUNCH(seq_vae_loss_parts_kernel, dim3(T + B), dim3(256), 0, st, xs, target, mu, logstd, B, T, n, H, recon_weight, kl_weight_dev,
+               part, dxs, dmu, dlogstd);
+  VUNET_LAUNCH(seq_vae_loss_final_kernel, dim3(1), dim3(64), 0, st, part, B, T, n, H, recon_weight, kl_weight_dev, gamma_dev, imax_dev,
+               gamma_step, scalars, per_seq);
   return vunet_check_launch();
 }
 

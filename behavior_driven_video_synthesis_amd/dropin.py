@@ -9,7 +9,10 @@
 ``experiments/shape_and_pose_net.py``'s ``from models.vunets import VunetAlter`` (:10), ``from lib.losses import vgg_loss``
 and friends resolve to the HIP-backed classes without a single edited line.  ``UnsupervisedTransformer2`` and
 ``ResidualBehaviorNet`` train under autograd on this path (``experiments/behavior_net.py:591-714``: csrc/seq_train.hip,
-csrc/seq_bptt.hip), so an unchanged ``main.py --config config/behavior_net.yaml`` runs both of its stages.  Each alias is a
+csrc/seq_bptt.hip), so an unchanged ``main.py --config config/behavior_net.yaml`` runs both of its stages -- with
+``use_regressor: False``.  The shipped YAML's ``use_regressor: True`` does not run through the drop-in: the reference's own
+regressor code raises on torch >= 1.5 before any of this package's kernels are reached (it steps the regressor in place between
+the loss's forward and backward); that configuration trains through ``experiments.behavior_net.BehaviorNet``.  Each alias is a
 HYBRID module: names this package defines come from here -- except ``HIDDEN`` ones, the flat-input building blocks of
 ``lib/modules.py`` (``ActNorm``, ``BasicFullyConnectedNet``) that the reference's OTHER flows (``ConditionalFlow``,
 ``SupervisedTransformer``, ... in its own ``models/flow/blocks.py``) import by name and use on 4-d inputs and under autograd:
@@ -46,7 +49,9 @@ ALIASES = {
 
 
 # names this package defines for its own modules' use but does NOT export under the reference's module name
-HIDDEN = {"lib.modules": ("ActNorm", "BasicFullyConnectedNet", "Linear", "_Marker")}
+HIDDEN = {"lib.modules": ("ActNorm", "BasicFullyConnectedNet", "Linear", "_Marker"),
+          # the regressor's mirror is a parameter holder for BehaviorNet's fused step; the reference's loop keeps its own class
+          "models.pose_behavior_rnn": ("Regressor_fly",)}
 
 
 def _hybrid(alias: str, ours, ref_root: str):

@@ -2,17 +2,21 @@
 
 ``BehaviorNet.train_fn(batch)`` is the reference's ``train_fn`` (:446-760) for a batch ``{"keypoints": [B, T + 1, n_kps]}``:
 
-* first stage (``only_flow`` False, :591-660): ``net(seq_b, seq_b, seq_len)`` -> ``recon_loss_weight * mean(MSE) + gamma *
-  kl_loss`` -> backward -> ``Adam(lr_init)`` -> the gamma controller (:111-116).  Forward, loss, back-propagation through
-  time and the fused optimiser step are one recorded hipGraph (csrc/seq.hip, csrc/seq_bptt.hip, csrc/seq_train.hip).
+* first stage (``only_flow`` False, :591-660): ``net(seq_b, seq_b, seq_len)`` -> ``recon_loss_weight * mean(MSE) + tuning *
+  kl_loss`` (``tuning`` = gamma, or 1 with ``cvae``) -> with ``use_regressor`` (:627-648) five inner steps of the adversarial
+  pose regressor and ``loss -= w clamp(L_5, max=0.45) + w clamp(L_5, max=0.7)`` -> backward -> ``Adam(lr_init)`` -> the gamma
+  controller (:111-116).  Forward, loss, the regressor's steps, back-propagation through time and the fused optimiser step
+  are one recorded hipGraph (csrc/seq.hip, csrc/seq_bptt.hip, csrc/seq_train.hip, csrc/seq_reg.hip).  ``train_fn(...,
+  update=epoch < n_epochs - 10)`` is the reference's freeze of the last ten epochs (:656-660): the regressor still trains,
+  the net and gamma do not.  The regressor term follows the reference's pinned torch 1.3.1, whose Adam writes through
+  ``p.data``: its gradient reaches mu through the regressor's weights AFTER the fifth inner update, with the fifth forward's
+  ReLU masks (seq_train.RegressorTrainEngine).
 * flow stage (``only_flow`` True, :703-714): the net encodes under ``no_grad``, then ``latent_flow(bs.detach())`` ->
   ``FlowLoss`` -> backward -> ``Adam(flow_lr * batch_size, betas (0.5, 0.9), weight_decay)`` with the weight gradient fused
   into the update (``seq_train.FlowTrainEngine``).
 
 Not on this path, and said here rather than silently dropped:
 * the second pass ``net(seq_2, seq_start_t, seq_len)`` (:600-603): none of its outputs reaches the loss or the log;
-* ``use_regressor`` (:627-648): the reference steps the regressor's weights in place between the loss's forward and its
-  backward, which torch >= 1.5 refuses (tests/golden/g11_cvae_training.npz records the error); the trainer raises if asked;
 * the action classifiers (:662-690): models/pose_discriminator.py is outside the path and they feed no
   gradient that the net's optimiser uses.
 """
@@ -24,9 +28,10 @@ from typing import Dict, Optional
 import torch
 
 from ..models.flow.simple_flow import UnsupervisedTransformer2
-from ..models.pose_behavior_rnn import ResidualBehaviorNet
+from ..models.pose_behavior_rnn import Regressor_fly, ResidualBehaviorNet
 from ..ops import _call, _p, _stream
 from ..optim import FusedAdam
+from ..seq_train import RegressorTrainEngine
 
 DEFAULT_CONFIG = {   # config/behavior_net.yaml
     "architecture": {"decoder_arch": "lstm", "linear_in_decoder": False, "dim_hidden_b": 1024, "flow_mid_channels_factor": 2,
@@ -42,9 +47,6 @@ class BehaviorNet:
         import copy
         self.config = copy.deepcopy(DEFAULT_CONFIG if config is None else config)
         arch, tr = self.config["architecture"], self.config["training"]
-        if tr.get("use_regressor", False):
-            raise NotImplementedError("use_regressor: the reference's own step raises on torch >= 1.5 (an in-place optimiser step "
-                                      "between the loss's forward and backward, experiments/behavior_net.py:636-653); not built")
         self.device = torch.device(device)
         self.only_flow = bool(tr.get("only_flow", False))
         self.net = ResidualBehaviorNet(n_kps=n_kps, information_bottleneck=True, **arch).to(self.device)     # :310-313
@@ -60,6 +62,14 @@ class BehaviorNet:
         self.imax = float(tr["information_max"])
         self.imax_dev = torch.full((1,), self.imax, device=self.device)
         self.hip_graph = hip_graph
+        self.use_regressor = bool(tr.get("use_regressor", False))
+        self.cvae = bool(arch.get("cvae", False))
+        self.kl_weight_dev = torch.ones(1, device=self.device) if self.cvae else None   # tuning = 1. (:606)
+        self.regressor = self.regressor_engine = None
+        self._reg_generation = 0
+        if self.use_regressor:   # :305-306
+            self.regressor = Regressor_fly(arch["dim_hidden_b"], n_kps).to(self.device)
+            self.regressor_engine = RegressorTrainEngine(self.regressor, lr=1e-4)
 
     # ---- the reference's knobs
     @property
@@ -79,7 +89,7 @@ class BehaviorNet:
         self.optimizer._lr_mirrored = float(lr)
 
     # ---- one step
-    def _cvae_step(self, seq_b, target, eps) -> Dict:
+    def _cvae_step(self, seq_b, target, eps, reg_index, update: bool) -> Dict:
         tr = self.config["training"]
         eng = self.net.train_engine()
         eng._check()
@@ -92,40 +102,68 @@ class BehaviorNet:
             torch.randn(p["eps"].shape, out=p["eps"])
         else:
             p["eps"].copy_(eps)
-        tuning_is_gamma = not self.config["architecture"].get("cvae", False)
-        if not tuning_is_gamma:
-            raise NotImplementedError("cvae: True (a fixed KL weight of 1) is not wired; config/behavior_net.yaml trains with False")
+        rp = None
+        if self.use_regressor:
+            rp = self.regressor_engine.plan(rows)
+            if reg_index is None:   # torch.randint(0, seq_len, (1,)) per inner step (:629), drawn outside the recording
+                rp["idx"].random_(0, t_in)
+            else:
+                idx = torch.as_tensor(reg_index).reshape(-1)
+                if idx.numel() != 5 or int(idx.min()) < 0 or int(idx.max()) >= t_in:
+                    raise ValueError(f"reg_index: five indices in [0, {t_in}), got {idx.tolist()}")
+                rp["idx"].copy_(idx)
         grads = {n: q.grad for n, q in self.net.named_parameters()}
+        gamma_step = float(tr["gamma_step"]) if update else 0.0   # the frozen epochs do not move gamma (:656-660)
 
         def issue():
             eng._fill_images()
             eng._issue_train_forward(rows, p, t_in, t_in, t_in, 0, False)
-            _call("vunet_seq_vae_loss", _p(p["xs"]), _p(p["target"]), _p(p["mu"]), _p(p["logstd"]), rows, t_in, eng.n, eng.H,
-                  float(tr["recon_loss_weight"]), _p(self.gamma_dev), _p(self.imax_dev), float(tr["gamma_step"]), _p(p["part"]),
-                  _p(p["scalars"]), _p(p["per_seq"]), _p(p["gxs"]), _p(p["gmu"]), _p(p["glogstd"]), _stream())
-            eng._issue_train_backward(rows, p, t_in, t_in, False)
-            eng._unpack_grads(p, grads)
-            self.optimizer.step()
+            dxs, dmu, dlogstd = (_p(p["gxs"]), _p(p["gmu"]), _p(p["glogstd"])) if update else (None, None, None)
+            if self.cvae:
+                _call("vunet_seq_vae_loss_w", _p(p["xs"]), _p(p["target"]), _p(p["mu"]), _p(p["logstd"]), rows, t_in, eng.n, eng.H,
+                      float(tr["recon_loss_weight"]), _p(self.kl_weight_dev), _p(self.gamma_dev), _p(self.imax_dev), gamma_step,
+                      _p(p["part"]), _p(p["scalars"]), _p(p["per_seq"]), dxs, dmu, dlogstd, _stream())
+            else:
+                _call("vunet_seq_vae_loss", _p(p["xs"]), _p(p["target"]), _p(p["mu"]), _p(p["logstd"]), rows, t_in, eng.n, eng.H,
+                      float(tr["recon_loss_weight"]), _p(self.gamma_dev), _p(self.imax_dev), gamma_step, _p(p["part"]),
+                      _p(p["scalars"]), _p(p["per_seq"]), dxs, dmu, dlogstd, _stream())
+            if rp is not None:
+                self.regressor_engine.issue_step(rows, rp, p["mu"], p["x1"], t_in, float(tr["weight_regressor"]), p["scalars"],
+                                                 p["gmu"] if update else None)
+            if update:
+                eng._issue_train_backward(rows, p, t_in, t_in, False)
+                eng._unpack_grads(p, grads)
+                self.optimizer.step()
         eng.graph.enabled = self.hip_graph
-        mode = eng.graph.run_step(("cvae", rows, t_in), issue)
-        if mode == "replayed":
+        mode = eng.graph.run_step(("cvae", rows, t_in, self.use_regressor, self.cvae, bool(update), self._reg_generation), issue)
+        if mode == "replayed" and update:
             self.optimizer.note_replayed_steps(1)
-        eng._packed_for = None     # the parameters moved: an inference call re-fills the images
+        if update:
+            eng._packed_for = None     # the parameters moved: an inference call re-fills the images
+        p["reg"] = rp
         return p
 
     def train_fn(self, batch: Dict[str, torch.Tensor], eps: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                 sync: bool = True) -> Dict:
+                 sync: bool = True, update: bool = True, reg_index=None) -> Dict:
         """``eps``: the reparametrisation noise (None: drawn); ``noise``: the draw behind the flow stage's logged
-        ``reference_nll_loss``.  ``sync`` False returns device tensors instead of floats (no host round trip per step)."""
+        ``reference_nll_loss``.  ``sync`` False returns device tensors instead of floats (no host round trip per step).
+        ``update``: the caller passes ``epoch < n_epochs - 10`` (:656); False runs the step without the net's backward, its
+        optimiser step and the gamma update -- the regressor still trains and the logs are produced.  ``reg_index``: the five
+        inner steps' sequence indices (None: drawn on the device)."""
         kps = batch["keypoints"].to(self.device, torch.float32)
         seq_b, target = kps[:, :-1].contiguous(), kps[:, 1:].contiguous()       # prepare_input (lib/utils.py:914-917)
         seq_len = seq_b.shape[1]
         out: Dict = {}
         if not self.only_flow:
-            p = self._cvae_step(seq_b, target, eps)
+            if self.use_regressor and seq_len != 50:
+                raise ValueError(f"use_regressor needs seq_len == 50: the regressor's fc4 is Linear(50, 128) on a one-hot over the "
+                                 f"sequence (models/pose_behavior_rnn.py:55), got seq_len {seq_len}")
+            p = self._cvae_step(seq_b, target, eps, reg_index, update)
             sc = p["scalars"]
             out.update(loss=sc[0], loss_recon=sc[1], kl_loss=sc[2], gamma=self.gamma_dev[0], mu_s=sc[4], logstd_s=sc[5],
                        loss_per_seq_recon=p["per_seq"])
+            if p["reg"] is not None:
+                out["loss_regressor"] = p["reg"]["reg"][4]
         else:
             with torch.no_grad():
                 xs, cs, _, bs, mu_s, logstd_s, pre_s = self.net(seq_b, seq_b, seq_len, eps=eps)
@@ -148,8 +186,12 @@ class BehaviorNet:
 
     # ---- checkpoints in the reference's layout (:1003-1011: model / optimizer / flow / flow optimizer)
     def state_dict(self) -> dict:
-        return {"model": self.net.state_dict(), "optimizer": self.optimizer.state_dict(), "flow": self.latent_flow.state_dict(),
-                "flow_optimizer": self.flow_engine.optimizer_state_dict(), "gamma": self.gamma}
+        sd = {"model": self.net.state_dict(), "optimizer": self.optimizer.state_dict(), "flow": self.latent_flow.state_dict(),
+              "flow_optimizer": self.flow_engine.optimizer_state_dict(), "gamma": self.gamma}
+        if self.use_regressor:
+            sd["regressor"] = self.regressor_engine.state_dict()
+            sd["regressor_optimizer"] = self.regressor_engine.optimizer_state_dict()
+        return sd
 
     def load_state_dict(self, sd: dict):
         self.net.load_state_dict(sd["model"])
@@ -161,3 +203,7 @@ class BehaviorNet:
             self.flow_engine.load_optimizer_state_dict(sd["flow_optimizer"])
         if "gamma" in sd:
             self.gamma_dev.fill_(float(sd["gamma"]))
+        if self.use_regressor and sd.get("regressor") is not None:   # (its optimiser state starts afresh)
+            self.regressor.load_state_dict(sd["regressor"])
+            self.regressor_engine.load_module()
+            self._reg_generation += 1      # a recorded step holds the old fc5 image and moments

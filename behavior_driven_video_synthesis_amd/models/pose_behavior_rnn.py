@@ -117,3 +117,20 @@ class ResidualBehaviorNet(nn.Module):
         """:603-626: -> (xs [B, len, n_kps], cs (each step's input pose), [], b)."""
         xs, cs = self.engine().generate_seq(b.contiguous(), x_pose.contiguous(), int(len), int(start_frame))
         return xs, cs, [], b
+
+
+class Regressor_fly(nn.Module):
+    """models/pose_behavior_rnn.py:47-62: the adversarial pose regressor of the cVAE's first stage -- same constructor, parameter
+    keys and initialisation (``nn.Linear``, created in the same order).  A parameter holder: the regressor is trained inside
+    ``BehaviorNet``'s fused step (``seq_train.RegressorTrainEngine``, csrc/seq_reg.hip) and has no forward of its own here; the
+    drop-in keeps handing the reference's loop the reference's class (``dropin.HIDDEN``)."""
+
+    def __init__(self, n_dim, n_key):
+        super().__init__()
+        self.n_dim, self.n_key = n_dim, n_key
+        self.act = nn.ReLU()
+        self.fc1 = nn.Linear(n_dim, n_dim)
+        self.fc2 = nn.Linear(n_dim, n_dim // 2)
+        self.fc3 = nn.Linear(n_dim // 2, n_dim // 4)
+        self.fc4 = nn.Linear(50, 128)
+        self.fc5 = nn.Linear(128 + n_dim // 4, n_key)

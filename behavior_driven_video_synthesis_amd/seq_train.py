@@ -854,3 +854,148 @@ def behavior_autograd(engine: BehaviorTrainEngine, x1, x2, length, start_frame, 
     named = list(engine.net.named_parameters())
     return _BehaviorFn.apply(engine, [n for n, _ in named], x1.contiguous(), x2.contiguous(), int(length), int(start_frame), eps,
                              bool(sample_prior), *[q for _, q in named])
+
+
+# ================================================================================================
+# the cVAE's adversarial pose regressor (experiments/behavior_net.py:627-648; models/pose_behavior_rnn.py:47-62)
+# ================================================================================================
+ACT_RELU_SEQ = 3   # vunet_seq_linear's plain ReLU
+REG_STEPS = 5      # inner regressor steps per cVAE step (:628)
+
+
+class RegressorTrainEngine:
+    """``Regressor_fly``'s five inner steps of the cVAE's first stage and the adversarial term's gradient wrt mu, issued into
+    the cVAE step's recorded launch sequence (include/vunet_seq_reg.h, csrc/seq_reg.hip).  Per inner step k: forward (fc1 -> fc2
+    -> fc3 with ReLU, fc4 of the one-hot as one column of W4, fc5), ``L_k = mean((pred - seq_b[:, idx_k])^2)``, its input
+    gradients on the weights before the step, then the weight gradients fused into the regressor's own Adam (betas 0.9 / 0.999,
+    eps 1e-8; its step count advances by five per cVAE step).  After the fifth, the input gradient of ``L_5`` is run back to mu
+    through the UPDATED weights with the fifth forward's ReLU masks -- what the reference's torch 1.3.1 computes, whose Adam
+    writes through ``p.data`` -- scaled by ``-w ([L_5 <= 0.45] + [L_5 <= 0.7])``.
+
+    The module's fc1 .. fc4 parameters are the kernels' operands and are updated in place; fc5 (51 rows) trains as a zero-padded
+    64-row image, written back into the module by ``write_back``."""
+
+    def __init__(self, reg, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8):
+        H, n = reg.n_dim, reg.n_key
+        if H % 256:
+            raise ValueError(f"the regressor's training kernels take dim_hidden_b as a multiple of 256 (its fc3 has dim_hidden_b / 4 "
+                             f"rows, tiles of 64), got {H}")
+        if n > 64:
+            raise ValueError(f"the regressor's output is padded to 64 rows: at most 64 pose dimensions, got {n}")
+        self.reg = reg
+        self.H, self.H4, self.K5, self.n = H, H // 4, H // 4 + 128, n
+        dev = reg.fc1.weight.device
+        self.adam = AdamState(dev, lr, betas, eps, 0.0)
+        self._plans: Dict[int, dict] = {}
+        self.load_module()
+
+    def load_module(self):
+        """(Re)build the training state from the module's parameters: the fc5 image; Adam's moments and step count are reset."""
+        r = self.reg
+        self.w5 = weight_image(r.fc5.weight.detach(), 64, self.K5)
+        self.b5 = padded_vector(r.fc5.bias.detach(), 64)
+        self.layers = [_TrainLayer("fc1", r.fc1, r.fc1.weight.data, r.fc1.bias.data),
+                       _TrainLayer("fc2", r.fc2, r.fc2.weight.data, r.fc2.bias.data),
+                       _TrainLayer("fc3", r.fc3, r.fc3.weight.data, r.fc3.bias.data),
+                       _TrainLayer("fc5", r.fc5, self.w5, self.b5)]
+        for layer in self.layers:
+            layer.moments()
+        w4 = r.fc4.weight.data
+        self.m4, self.v4 = torch.zeros_like(w4), torch.zeros_like(w4)
+        self.bm4, self.bv4 = torch.zeros_like(r.fc4.bias.data), torch.zeros_like(r.fc4.bias.data)
+        self.adam.step_dev.zero_()
+        self._plans.clear()
+
+    def plan(self, rows: int) -> dict:
+        p = self._plans.get(rows)
+        if p is not None:
+            return p
+        dev = self.w5.device
+        bp, H, H2, H4, K5 = _up(rows, 16), self.H, self.H // 2, self.H4, self.K5
+        z = lambda *s: torch.zeros(*s, device=dev)   # noqa: E731
+        S = {"fc5": FlowTrainEngine._dx_split(64, K5, 1), "fc3": FlowTrainEngine._dx_split(H4, H2, 1),
+             "fc2": FlowTrainEngine._dx_split(H2, H, 1), "fc1": FlowTrainEngine._dx_split(H, H, 1)}
+        p = dict(b_pad=bp, S=S, idx=torch.zeros(REG_STEPS, dtype=torch.int32, device=dev), mu=z(bp, H), h1=z(bp, H), h2=z(bp, H2),
+                 h3=z(bp, H4), cat=z(bp, K5), pred=z(bp, 64), tgt=z(bp, self.n), dpred=z(bp, 64), dz1=z(bp, H), dz2=z(bp, H2),
+                 dz3=z(bp, H4), dzc=z(bp, 128), reg=z(6), adv=z(rows, H),
+                 raw=z(max(S["fc5"] * bp * K5, S["fc3"] * bp * H2, S["fc2"] * bp * H, S["fc1"] * bp * H)))
+        # the update sweep: fc1, fc2, fc3, fc5 in one launch (fc4 has its own kernel)
+        entries, tile = [], 0
+        for layer, dz, x, ldz in zip(self.layers, (p["dz1"], p["dz2"], p["dz3"], p["dpred"]), (p["mu"], p["h1"], p["h2"], p["cat"]),
+                                     (H, H2, H4, 64)):
+            m, k = layer.w.shape
+            entries.append(SeqDwLayer(layer.w.data_ptr(), layer.m.data_ptr(), layer.v.data_ptr(), None, layer.b.data_ptr(),
+                                      layer.bm.data_ptr(), layer.bv.data_ptr(), None, dz.data_ptr(), x.data_ptr(), m, k, ldz, k, tile,
+                                      k // 64, k, 1, 0, 0, None))
+            tile += (m // 64) * (k // 64)
+        p["dw"] = dict(table=_table(entries, dev), n=len(entries), tiles=tile)
+        self._plans[rows] = p
+        return p
+
+    def _dx_chain(self, rows: int, p: dict, dzc: Optional[torch.Tensor]):
+        """d L / d pred (p['dpred']) back to the dZ of fc1 (p['dz1']) on the weights as they are now; ``dzc``: fc4's dZ too."""
+        r, bp, S = self.reg, p["b_pad"], p["S"]
+        d = SeqDxDesc(rows, 64, self.K5, 1, S["fc5"], 0)
+        _call("vunet_seq_dx", ctypes.byref(d), _p(self.w5), None, _p(p["dpred"]), _p(p["raw"]), _stream())
+        _call("vunet_seq_reg_cat_bwd", _p(p["raw"]), S["fc5"], bp, self.H4, _p(p["cat"]), _p(p["dz3"]), _p(dzc), _stream())
+        for lin, s, dz_in, y_prev, dz_out in ((r.fc3, S["fc3"], p["dz3"], p["h2"], p["dz2"]), (r.fc2, S["fc2"], p["dz2"], p["h1"], p["dz1"])):
+            m, k = lin.weight.shape
+            d = SeqDxDesc(rows, m, k, 1, s, 0)
+            _call("vunet_seq_dx", ctypes.byref(d), _p(lin.weight.data), None, _p(dz_in), _p(p["raw"]), _stream())
+            _call("vunet_seq_dz_finish", _p(p["raw"]), _p(y_prev), _p(dz_out), 1, s, bp, k, 0.0, _stream())
+
+    def issue_step(self, rows: int, p: dict, mu: torch.Tensor, seq: torch.Tensor, t_len: int, weight: float, scalars: torch.Tensor,
+                   gmu: Optional[torch.Tensor]):
+        """The five inner steps on ``mu`` [rows, H] and ``seq`` [rows, t_len, n] with the indices in ``p['idx']``; the fifth adds
+        the adversarial term into ``scalars[0]`` (the logged loss) and -- ``gmu`` not None -- its gradient into ``gmu``."""
+        r, H, H2, H4, K5 = self.reg, self.H, self.H // 2, self.H4, self.K5
+        hpp = ctypes.byref(self.adam.hp)
+        _call("vunet_seq_unpack_rows", _p(mu), H, 0, 0, 1, _p(p["mu"]), rows, H, 0, _stream())     # fc1's operand, padded rows
+        for k in range(REG_STEPS):
+            for lin, x, y, m, kk in ((r.fc1, p["mu"], p["h1"], H, H), (r.fc2, p["h1"], p["h2"], H2, H), (r.fc3, p["h2"], p["h3"], H4, H2)):
+                linear(SeqLinearDesc(rows, m, kk, kk, ACT_RELU_SEQ, ACT_NONE, 1, 1, 1), [lin.weight.data], x, [lin.bias.data], y)
+            _call("vunet_seq_reg_gather", _p(r.fc4.weight.data), _p(r.fc4.bias.data), _p(p["idx"]), k, _p(p["h3"]), _p(seq), t_len * self.n,
+                  self.n, rows, H4, _p(p["cat"]), _p(p["tgt"]), _stream())
+            linear(SeqLinearDesc(rows, 64, K5, K5, ACT_NONE, ACT_NONE, 1, 1, 1), [self.w5], p["cat"], [self.b5], p["pred"])
+            last = k == REG_STEPS - 1
+            _call("vunet_seq_reg_loss", _p(p["pred"]), 64, _p(p["tgt"]), rows, self.n, k, float(weight), _p(p["reg"]), _p(p["dpred"]),
+                  _p(scalars) if last else None, _stream())
+            self._dx_chain(rows, p, p["dzc"])          # on the weights before this step's update
+            self.adam.tick()
+            _call("vunet_seq_dw", _p(p["dw"]["table"]), p["dw"]["n"], 0, p["dw"]["tiles"], rows, hpp, _stream())
+            _call("vunet_seq_reg_fc4_adam", _p(p["dzc"]), p["b_pad"], _p(p["idx"]), k, _p(r.fc4.weight.data), _p(r.fc4.bias.data),
+                  _p(self.m4), _p(self.v4), _p(self.bm4), _p(self.bv4), hpp, _stream())
+        if gmu is None:
+            return
+        # the adversarial term: L_5's input gradient through the updated weights, the fifth forward's masks (torch 1.3.1)
+        self._dx_chain(rows, p, None)
+        s1 = p["S"]["fc1"]
+        d = SeqDxDesc(rows, H, H, 1, s1, 0)
+        _call("vunet_seq_dx", ctypes.byref(d), _p(r.fc1.weight.data), None, _p(p["dz1"]), _p(p["raw"]), _stream())
+        _call("vunet_seq_reg_adv", _p(p["raw"]), s1, rows, H, _p(p["reg"]), _p(gmu), _p(p["adv"]), _stream())
+
+    # ---- checkpoints: the reference's layout (``Regressor_fly`` keys; torch.optim.Adam's state)
+    def write_back(self):
+        self.layers[3].write_back()
+
+    def _params(self):
+        r = self.reg
+        return [r.fc1.weight, r.fc1.bias, r.fc2.weight, r.fc2.bias, r.fc3.weight, r.fc3.bias, r.fc4.weight, r.fc4.bias, r.fc5.weight,
+                r.fc5.bias]
+
+    def state_dict(self) -> dict:
+        self.write_back()
+        return self.reg.state_dict()
+
+    def optimizer_state_dict(self) -> dict:
+        step = self.adam.step
+        n5, k5 = self.reg.fc5.weight.shape
+        moments = []
+        for layer in self.layers[:3]:
+            moments += [(layer.m, layer.v), (layer.bm, layer.bv)]
+        moments += [(self.m4, self.v4), (self.bm4, self.bv4)]
+        f5 = self.layers[3]
+        moments += [(f5.m[:n5, :k5], f5.v[:n5, :k5]), (f5.bm[:n5], f5.bv[:n5])]
+        state = {i: {"step": step, "exp_avg": m.clone(), "exp_avg_sq": v.clone()} for i, (m, v) in enumerate(moments)} if step else {}
+        return {"state": state, "param_groups": [{"lr": self.adam.lr, "betas": self.adam.betas, "eps": self.adam.eps, "weight_decay": 0.0,
+                                                  "amsgrad": False, "params": list(range(10))}]}

@@ -597,7 +597,7 @@ int vunet_p2_pool_bwd(const void* t, const int32_t* tmeta, const void* p, const 
  * computed but never read back).
  *
  *   vunet_seq_linear      y[net][b][m] = act_net(sum_k w_net[m][k] * x_net[b][k] + bias_net[m])   (act 0: none, 1: LeakyReLU(0.01),
- *                         2: tanh).  w: [M][K] row-major, M % 16 == 0, K % 32 == 0 (zero-padded images, vunet_seq_pack_rows);
+ *                         2: tanh, 3: ReLU).  w: [M][K] row-major, M % 16 == 0, K % 32 == 0 (zero-padded images, vunet_seq_pack_rows);
  *                         x: [nets_in][Bp][ldx] with nets_in = 1 (shared_in != 0: both nets read the same operand) or nets;
  *                         y: [nets][Bp][M].  S > 1 (the flow's 512-row head layers, which would otherwise run on 32 workgroups per
  *                         net): K split over S workgroups per row tile, y = [nets][S][Bp][M] RAW partial slabs -- no bias, no

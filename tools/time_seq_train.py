@@ -22,6 +22,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--eager", action="store_true")
     ap.add_argument("--stage", default="flow", choices=["flow", "cvae"])
+    ap.add_argument("--regressor", default="off", choices=["off", "on", "ab"],
+                    help="cvae stage: with use_regressor (on), or both trainers with their timing windows alternated (ab)")
+    ap.add_argument("--windows", type=int, default=1, help="timing windows of --reps steps; the median is reported")
     args = ap.parse_args()
     if args.stage == "cvae":
         return cvae(args)
@@ -57,28 +60,44 @@ def main():
 
 
 def cvae(args):
-    """The first stage's step at config/behavior_net.yaml's sizes: ResidualBehaviorNet 1024 hidden / 51 dims, 50 frames."""
+    """The first stage's step at config/behavior_net.yaml's sizes: ResidualBehaviorNet 1024 hidden / 51 dims, 50 frames;
+    ``--regressor on``: with the adversarial pose regressor (use_regressor, weight_regressor 0.01); ``ab``: both, the timing
+    windows alternated between the two trainers."""
     import copy
+    import statistics
     from behavior_driven_video_synthesis_amd.experiments.behavior_net import BehaviorNet, DEFAULT_CONFIG
-    cfg = copy.deepcopy(DEFAULT_CONFIG)
-    cfg["architecture"].update(n_flows=1, flow_mid_channels_factor=1, flow_hidden_depth=1)
-    torch.manual_seed(0)
-    tr = BehaviorNet(cfg, n_kps=51, hip_graph=not args.eager)
-    tr.net.decoder.n_out.weight.data.mul_(0.05)
+    modes = {"off": [False], "on": [True], "ab": [False, True]}[args.regressor]
+    trainers = {}
+    for reg in modes:
+        cfg = copy.deepcopy(DEFAULT_CONFIG)
+        cfg["architecture"].update(n_flows=1, flow_mid_channels_factor=1, flow_hidden_depth=1)
+        cfg["training"].update(use_regressor=reg)
+        torch.manual_seed(0)
+        tr = BehaviorNet(cfg, n_kps=51, hip_graph=not args.eager)
+        tr.net.decoder.n_out.weight.data.mul_(0.05)
+        trainers[reg] = tr
     batch = {"keypoints": 0.5 * torch.randn(args.rows, 51, 51, device="cuda")}
-    for _ in range(3):
-        tr.train_fn(batch, sync=False)
+    for tr in trainers.values():
+        for _ in range(3):
+            tr.train_fn(batch, sync=False)
     torch.cuda.synchronize()
+    times = {reg: [] for reg in modes}
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(args.reps):
-        tr.train_fn(batch, sync=False)
-    b.record()
-    torch.cuda.synchronize()
-    t = a.elapsed_time(b) / args.reps
-    out = tr.train_fn(batch)
-    print(json.dumps({"stage": "cvae", "rows": args.rows, "frames": 50, "graph": not args.eager, "step_ms": round(t, 4),
-                      "sequences_per_s": round(1e3 * args.rows / t, 1), "loss": round(out["loss"], 5), "kl": round(out["kl_loss"], 4)}))
+    for _ in range(args.windows):
+        for reg, tr in trainers.items():
+            a.record()
+            for _ in range(args.reps):
+                tr.train_fn(batch, sync=False)
+            b.record()
+            torch.cuda.synchronize()
+            times[reg].append(a.elapsed_time(b) / args.reps)
+    for reg, tr in trainers.items():
+        t = statistics.median(times[reg])
+        out = tr.train_fn(batch)
+        print(json.dumps({"stage": "cvae", "rows": args.rows, "frames": 50, "graph": not args.eager, "regressor": reg,
+                          "step_ms": round(t, 4), "windows_ms": [round(x, 4) for x in times[reg]],
+                          "sequences_per_s": round(1e3 * args.rows / t, 1), "loss": round(out["loss"], 5), "kl": round(out["kl_loss"], 4),
+                          **({"loss_regressor": round(out["loss_regressor"], 5)} if reg else {})}))
 
 
 if __name__ == "__main__":
