@@ -1,0 +1,148 @@
+"""Scoring a behaviour model the way the reference does (experiments/behavior_net.py:1112-1301, lib/logging.py:2079-2093):
+sample S behaviours per test sequence, roll them out, and measure their diversity (ASD, FSD, APD) and their best fit to the
+ground-truth future (ADE, FDE); plus the "three characters" transfer numbers (ADE_c, FDE_c, recon / distance of mu).
+
+The reference draws the S samples one after another (a flow reverse and a roll-out on B / 4 rows each), copies every sampled
+sequence to the host, un-normalises it in numpy and builds the distance tables with two host syncs per row.  Here the S samples
+of every sequence are one batched pass through ``FlowEngine`` / ``BehaviorEngine`` (their 64-row chunks and recorded graphs),
+and the un-normalisation, the distance tables and the selections are two HIP launches (csrc/seq_eval.hip,
+include/vunet_seq_eval.h) whose results stay on the device until ``BehaviorEvaluator.summary``.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+
+from .ops import _call, _p, _stream
+
+METRICS = ("APD", "ASD", "FSD", "minADE", "minFDE")      # per sequence, in the kernel's output order
+TRANSFER = ("ADE_c", "FDE_c", "recon_mu", "recon_std", "distance_mu", "distance_std")
+
+
+class PoseStats:
+    """The dataset's normalisation statistics on the device (``data_mean``, ``data_std``, ``dim_to_ignore``: what
+    ``revert_output_format`` / ``unNormalizeData`` take, data/data_conversions_3d.py:178-211).  The statistics' dtype decides the
+    precision of the un-normalisation, as numpy's promotion does: float32 statistics mean float32 arithmetic, anything else
+    float64.  Only the used dimensions are kept: the ignored ones hold ``mean`` in every vector and add 0 to any distance."""
+
+    def __init__(self, data_mean, data_std, dim_to_ignore, device="cuda"):
+        mean, std = np.asarray(data_mean), np.asarray(data_std)
+        if mean.shape != std.shape or mean.ndim != 1:
+            raise ValueError(f"data_mean {mean.shape} and data_std {std.shape}: two vectors of the same length expected")
+        self.f32_math = int(mean.dtype == np.float32 and std.dtype == np.float32)
+        ignore = {int(d) for d in np.asarray(dim_to_ignore).reshape(-1)}
+        use = np.asarray([d for d in range(mean.size) if d not in ignore], dtype=np.int64)
+        self.dim, self.n_use = int(mean.size), int(use.size)
+        self.dims_to_use = torch.as_tensor(use, device=device)
+        self.mean = torch.as_tensor(mean[use].astype(np.float64), device=device)
+        self.std = torch.as_tensor(std[use].astype(np.float64), device=device)
+
+
+def _rows_of(z: torch.Tensor, n: int, s: int) -> torch.Tensor:
+    """[S, N, H] noise in the reference's draw order (one ``randn_like(b[::skip])`` per sample) -> [N S, H], row i S + s = z[s, i]."""
+    if z.dim() != 3 or z.shape[0] != s or z.shape[1] != n:
+        raise ValueError(f"z: [n_samples={s}, N={n}, H] expected, got {tuple(z.shape)}")
+    return z.transpose(0, 1).reshape(n * s, z.shape[2]).contiguous()
+
+
+@torch.no_grad()
+def sample_behaviors(net, flow, start_poses: torch.Tensor, n_samples: int, length: int, start_frame: int = -1,
+                     z: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The sampling loop of experiments/behavior_net.py:1182-1217 as one batched pass: -> [N, S, length, n] normalised poses.
+
+    ``start_poses`` [N, T, n] (the reference passes ``target_s[::skip]``), the roll-out starts from frame ``start_frame`` of each.
+    Behaviour codes b = flow.reverse(z), z ~ N(0, 1) drawn for all N S rows at once (or the given ``z`` [S, N, H]); with ``flow``
+    None, b is the prior noise itself -- the reference's ``net(..., sample=True)`` branch, whose encoder output is discarded and
+    is therefore not computed."""
+    if n_samples < 2:
+        raise ValueError(f"n_samples must be >= 2 (the self-distance comes first in every row), got {n_samples}")
+    n_seq = start_poses.shape[0]
+    h = net.dim_hidden_b
+    if z is None:
+        z = torch.randn(n_samples, n_seq, h, device=start_poses.device, generator=generator)
+    zr = _rows_of(z.to(start_poses.device, torch.float32), n_seq, n_samples)
+    b = flow.reverse(zr).reshape(n_seq * n_samples, h) if flow is not None else zr
+    x = start_poses.repeat_interleave(n_samples, dim=0)           # row i S + s starts from sequence i
+    xs, *_ = net.generate_seq(b, x, len=length, start_frame=start_frame % start_poses.shape[1])
+    return xs.reshape(n_seq, n_samples, length, xs.shape[-1])
+
+
+def sample_metrics(samples: torch.Tensor, future: torch.Tensor, stats: PoseStats) -> Dict[str, torch.Tensor]:
+    """ASD / FSD / APD / min ADE / min FDE per sequence and the batch's ADE / FDE, float64 device tensors, no host sync.
+
+    ``samples`` [N, S, T, n] normalised poses (``sample_behaviors``); ``future`` [N, T + 1, n] the normalised ground truth, of
+    which frames 1 .. T are scored (the reference's ``seq_gt[:, :, 1:]``, :1235)."""
+    if samples.dim() != 4:
+        raise ValueError(f"samples: [N, S, T, n] expected, got {tuple(samples.shape)}")
+    n_seq, s, t, n = samples.shape
+    if s < 2:
+        raise ValueError(f"n_samples must be >= 2, got {s}")
+    if tuple(future.shape) != (n_seq, t + 1, n):
+        raise ValueError(f"future: [N={n_seq}, T + 1={t + 1}, n={n}] expected, got {tuple(future.shape)}")
+    if n != stats.n_use:
+        raise ValueError(f"pose vectors of {stats.n_use} used dimensions expected, got {n}")
+    for name, v in (("samples", samples), ("future", future)):
+        if not v.is_cuda or v.device != stats.mean.device:
+            raise RuntimeError(f"{name} must be on {stats.mean.device} (hand-written gfx950 kernels; no CPU fallback)")
+    x = samples.to(torch.float32).contiguous()
+    g = future.to(torch.float32).contiguous()
+    dev = x.device
+    scratch = torch.empty(n_seq * s * (3 * s + 2), device=dev, dtype=torch.float64)
+    per_seq = torch.empty(len(METRICS), n_seq, device=dev, dtype=torch.float64)
+    batch = torch.empty(2, device=dev, dtype=torch.float64)
+    _call("vunet_seq_eval_pairs", _p(x), _p(g), _p(stats.mean), _p(stats.std), stats.f32_math, n_seq, s, t, n, _p(scratch), _stream())
+    _call("vunet_seq_eval_select", _p(scratch), n_seq, s, _p(per_seq), _p(batch), _stream())
+    out = {k: per_seq[j] for j, k in enumerate(METRICS)}
+    out["ADE"], out["FDE"] = batch[0], batch[1]
+    return out
+
+
+@torch.no_grad()
+def transfer_metrics(net, x_s: torch.Tensor, x_t: torch.Tensor, x_related: torch.Tensor,
+                     eps: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The "three characters" numbers of experiments/behavior_net.py:1262-1278 (printed at :1299-1301), 0-dim device tensors:
+    ``seq_cross`` = net(x_s, x_t) (x_s's behaviour on x_t's start pose; ``eps``: its reparametrisation noise, None: drawn);
+    mu2, mu3 = the encoder's mu of ``seq_cross`` and of ``x_related``.  ADE_c / FDE_c against x_s in normalised space;
+    recon_* over ||mu - mu2||, distance_* over ||mu - mu3|| (``torch.std``: unbiased)."""
+    t = x_s.shape[1]
+    seq_cross, _, _, _, mu, *_ = net(x_s, x_t, t, sample=False, eps=eps)
+    eng = net.engine()
+    mu2 = eng.infer_b(seq_cross.contiguous(), None)[1]       # the encoder alone: mu does not depend on the noise
+    mu3 = eng.infer_b(x_related.contiguous(), None)[1]
+    r, d = torch.norm(mu - mu2, dim=1), torch.norm(mu - mu3, dim=1)
+    return {"ADE_c": torch.mean(torch.norm(seq_cross - x_s, dim=2)), "FDE_c": torch.mean(torch.norm(seq_cross[:, -1] - x_s[:, -1], dim=1)),
+            "recon_mu": torch.mean(r), "recon_std": torch.std(r), "distance_mu": torch.mean(d), "distance_std": torch.std(d)}
+
+
+class BehaviorEvaluator:
+    """The reference's metric lists (experiments/behavior_net.py:1112-1121, lib/logging.py APD): per-sequence ASD, FSD and APD,
+    per-batch ADE, FDE and transfer metrics.  ``add`` keeps device tensors; ``summary`` copies them to the host once and returns
+    ``np.mean`` of every non-empty list."""
+
+    def __init__(self):
+        self.per_seq: Dict[str, List[torch.Tensor]] = {k: [] for k in ("APD", "ASD", "FSD")}
+        self.per_batch: Dict[str, List[torch.Tensor]] = {k: [] for k in ("ADE", "FDE") + TRANSFER}
+
+    def add(self, metrics: Dict[str, torch.Tensor]):
+        for k, v in metrics.items():
+            if k in self.per_seq:
+                self.per_seq[k].append(v.reshape(-1))
+            elif k in self.per_batch:
+                self.per_batch[k].append(v.reshape(1))
+
+    def lists(self) -> Dict[str, np.ndarray]:
+        """Every list as a float64 array (one device-to-host copy)."""
+        parts = [(k, torch.cat(v).to(torch.float64)) for d in (self.per_seq, self.per_batch) for k, v in d.items() if v]
+        if not parts:
+            return {}
+        flat = torch.cat([p for _, p in parts]).cpu().numpy()
+        out, o = {}, 0
+        for k, p in parts:
+            out[k] = flat[o:o + p.numel()]
+            o += p.numel()
+        return out
+
+    def summary(self) -> Dict[str, float]:
+        return {k: float(np.mean(v)) for k, v in self.lists().items()}

@@ -15,6 +15,10 @@
   ``FlowLoss`` -> backward -> ``Adam(flow_lr * batch_size, betas (0.5, 0.9), weight_decay)`` with the weight gradient fused
   into the update (``seq_train.FlowTrainEngine``).
 
+``BehaviorNet.evaluate(batches, stats)`` scores a model as ``run_inference`` does (:1112-1301, APD from lib/logging.py:2079-2093):
+ASD, FSD, APD, ADE and FDE of ``n_samples`` sampled behaviours per scored sequence, and the transfer metrics
+(behavior_eval.py, csrc/seq_eval.hip).
+
 Not on this path, and said here rather than silently dropped:
 * the second pass ``net(seq_2, seq_start_t, seq_len)`` (:600-603): none of its outputs reaches the loss or the log;
 * the action classifiers (:662-690): models/pose_discriminator.py is outside the path and they feed no
@@ -140,6 +144,9 @@ class BehaviorNet:
             self.optimizer.note_replayed_steps(1)
         if update:
             eng._packed_for = None     # the parameters moved: an inference call re-fills the images
+            inf = self.net._engine     # ... the inference engine's too: FusedAdam writes through a kernel, no version counter moves
+            if inf is not None:
+                inf._packed_for = None
         p["reg"] = rp
         return p
 
@@ -183,6 +190,40 @@ class BehaviorNet:
             out = {k: (v.detach().cpu().numpy() if k == "loss_per_seq_recon" else float(v)) if isinstance(v, torch.Tensor) else v
                    for k, v in out.items()}
         return out
+
+    # ---- scoring (experiments/behavior_net.py:1112-1301, lib/logging.py:2079-2093)
+    @torch.no_grad()
+    def evaluate(self, batches, stats, n_samples: int = 50, skip: int = 4, use_flow: bool = True, z=None, eps=None):
+        """The reference's per-batch metric recipe of ``run_inference`` over an iterable of dict batches -> a
+        ``behavior_eval.BehaviorEvaluator`` (``.summary()``: the means the reference prints; ``.lists()``: the lists).
+
+        Batch keys:
+        * ``keypoints`` [B, T + 1, n]: ``prepare_input`` (lib/utils.py:914-917) gives x_s = kps[:, :-1], target_s = kps[:, 1:].
+        * ``future_keypoints`` [B, T + 1, n], one per row: what the dataset's ``_sample_valid_seq_ids`` / ``_get_keypoints`` look
+          up for rows [::skip] (:1162-1179); rows [::skip] are scored against its frames 1 .. T (:1235).
+        * optional ``paired_keypoints`` and ``matched_keypoints`` [B, T + 1, n] (kps2, kps3 of :1137-1143): with both present the
+          transfer metrics of :1262-1278 run too.
+        Sampling (:1182-1217): ``n_samples`` behaviours per scored row, from ``target_s[::skip]`` at start_frame T - 1, through
+        the flow (``use_flow``) or straight from the prior.  ``stats``: ``behavior_eval.PoseStats`` of the dataset.
+        ``z``: the sampling noise, [n_samples, B / skip, H] or a list with one per batch (None: drawn); ``eps``: the transfer
+        metrics' reparametrisation noise [B, H], or a list (None: drawn)."""
+        from .. import behavior_eval as E
+        ev = E.BehaviorEvaluator()
+        flow = self.latent_flow if use_flow else None
+        for bi, batch in enumerate(batches):
+            kps = batch["keypoints"].to(self.device, torch.float32)
+            x_s, target_s = kps[:, :-1].contiguous(), kps[:, 1:].contiguous()
+            t = x_s.shape[1]
+            fut = batch["future_keypoints"].to(self.device, torch.float32)[::skip].contiguous()
+            zb = z[bi] if isinstance(z, (list, tuple)) else z
+            samples = E.sample_behaviors(self.net, flow, target_s[::skip].contiguous(), n_samples, t, start_frame=t - 1, z=zb)
+            ev.add(E.sample_metrics(samples, fut, stats))
+            if "paired_keypoints" in batch and "matched_keypoints" in batch:
+                x_t = batch["paired_keypoints"].to(self.device, torch.float32)[:, :-1].contiguous()
+                x_rel = batch["matched_keypoints"].to(self.device, torch.float32)[:, :-1].contiguous()
+                eb = eps[bi] if isinstance(eps, (list, tuple)) else eps
+                ev.add(E.transfer_metrics(self.net, x_s, x_t, x_rel, eps=eb))
+        return ev
 
     # ---- checkpoints in the reference's layout (:1003-1011: model / optimizer / flow / flow optimizer)
     def state_dict(self) -> dict:

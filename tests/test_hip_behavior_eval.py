@@ -1,0 +1,258 @@
+"""The behaviour model's sampling metrics on the GPU (csrc/seq_eval.hip, behavior_eval.py, BehaviorNet.evaluate): the kernels
+against the fixture the reference's own classes wrote (tests/golden/g13_behavior_eval.npz) and against the float64 restatement
+(tests/behavior_eval_ref.py); batched sampling against the reference's per-sample loop structure; graph replay against eager;
+the reference width against the oracle; and the inference engine after fused training steps."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import behavior_eval_ref as R
+from conftest import load_golden
+from synth import seeded_randn, synth_behavior_state
+
+pytestmark = pytest.mark.gpu
+
+E2E_TOL = dict(rtol=1e-3, atol=1e-4)     # the behaviour tolerance of tests/test_hip_seq.py (fp32 flow + roll-out vs the CPU)
+
+
+def _E():
+    from behavior_driven_video_synthesis_amd import behavior_eval
+    return behavior_eval
+
+
+def _stats(mean, std, ignore):
+    return _E().PoseStats(mean, std, ignore, device="cuda")
+
+
+def _kernel_metrics(samples, future, stats):
+    m = _E().sample_metrics(torch.as_tensor(samples).cuda(), torch.as_tensor(future).cuda(), stats)
+    return {k: v.cpu().numpy() for k, v in m.items()}
+
+
+# ---- 1. the kernels on the fixture's samples
+@pytest.mark.parametrize("tag", ["flow_f64_s8", "flow_f32_s50", "prior_f64_s50", "prior_f32_s8", "tie_f64_s8"])
+def test_kernels_on_the_fixture_samples(tag):
+    meta, arr = load_golden("g13_behavior_eval")
+    c = meta["cases"][tag]
+    samples, future, *_ = R.fixture_inputs(meta, arr, tag)
+    stats = _stats(arr[f"{tag}.mean"], arr[f"{tag}.std"], c["ignore"])
+    assert stats.f32_math == (c["stats_dtype"] == "float32")
+    got = _kernel_metrics(samples, future, stats)
+    tol = dict(rtol=1e-12, atol=0) if c["stats_dtype"] == "float64" else dict(rtol=1e-5, atol=0)
+    for k in ("APD", "ASD", "FSD", "minADE", "minFDE"):
+        np.testing.assert_allclose(got[k], arr[f"{tag}.{k}"], err_msg=k, **tol)
+    np.testing.assert_allclose(got["ADE"], c["ADE"], **tol)
+    np.testing.assert_allclose(got["FDE"], c["FDE"], **tol)
+
+
+# ---- 2. the kernels on random inputs against the restatement
+@pytest.mark.parametrize("s,n_seq,t,f32", [(2, 1, 1, False), (3, 5, 2, True), (50, 16, 50, False), (64, 17, 50, True),
+                                           (64, 1, 2, False), (2, 17, 50, False), (3, 16, 1, True), (50, 5, 2, False)])
+def test_kernels_vs_the_restatement(s, n_seq, t, f32):
+    g = torch.Generator().manual_seed(1000 * s + 10 * n_seq + t)
+    dims, n = 96, 51
+    ignore = sorted(torch.randperm(dims, generator=g)[:dims - n].tolist())
+    mean = (torch.randn(dims, generator=g) * 300).double().numpy()
+    std = (50 + 200 * torch.rand(dims, generator=g)).double().numpy()
+    if f32:
+        mean, std = mean.astype(np.float32), std.astype(np.float32)
+    samples = torch.randn(n_seq, s, t, n, generator=g).numpy()
+    future = torch.randn(n_seq, t + 1, n, generator=g).numpy()
+    if s >= 3:
+        samples[0, 2] = samples[0, 0]                        # a zero-distance duplicate: np.sort(...)[1] is 0 for both rows
+    if s >= 3 and n_seq >= 2:
+        samples[1, 1, t - 1, 3] = np.nan                     # a NaN sample
+        samples[n_seq - 1, s - 1] = samples[n_seq - 1, 0] + 1e-3   # a near tie
+    use = [d for d in range(dims) if d not in set(ignore)]
+    want = R.metrics(samples, future, mean[use], std[use], f32)
+    got = _kernel_metrics(samples, future, _stats(mean, std, ignore))
+    tol = dict(rtol=1e-9, atol=0) if f32 else dict(rtol=1e-12, atol=0)   # (f32: the same float32 un-normalisation and
+    for k in ("APD", "ASD", "FSD", "minADE", "minFDE", "ADE", "FDE"):       #  differences; only the sums' order differs)
+        np.testing.assert_allclose(got[k], want[k], err_msg=k, equal_nan=True, **tol)
+    if s >= 3 and n_seq >= 2:
+        assert np.isnan(got["ASD"][1]) and np.isnan(got["minADE"][1]) and np.isnan(got["ADE"])
+
+
+def _g13_model(meta, arr, hip_graph=True):
+    from behavior_driven_video_synthesis_amd.experiments.behavior_net import BehaviorNet, DEFAULT_CONFIG
+    cfg = copy.deepcopy(DEFAULT_CONFIG)
+    fk = meta["flow_kw"]
+    cfg["architecture"].update(dim_hidden_b=fk["flow_in_channels"], n_flows=fk["n_flows"], flow_hidden_depth=fk["flow_hidden_depth"],
+                               flow_mid_channels_factor=fk["flow_mid_channels"] // fk["flow_in_channels"])
+    bn = BehaviorNet(cfg, n_kps=meta["net_kw"]["n_kps"], device="cuda:0", hip_graph=hip_graph)
+    stored = {k[len("flow.sd."):]: torch.from_numpy(v) for k, v in arr.items() if k.startswith("flow.sd.")}
+    bn.latent_flow.load_state_dict(synth_behavior_state(meta["flow_shapes"], meta["seed"], stored))
+    bn.net.load_state_dict(synth_behavior_state(meta["net_shapes"], meta["seed"], {}))
+    return bn
+
+
+def _g13_noise(meta, tag):
+    c, seed = meta["cases"][tag], meta["seed"]
+    shapes = c["noise_shapes"]
+    idx = list(range(len(shapes)))
+    if c["tie"] is not None:
+        idx[c["tie"][1]] = c["tie"][0]
+    return torch.stack([seeded_randn(f"{tag}.z.eps{j}", tuple(shapes[0]), seed) for j in idx]).cuda()
+
+
+def _g13_batch(meta, tag):
+    c, seed, bsz = meta["cases"][tag], meta["seed"], meta["batch"]
+    shape = (bsz, c["seq_len"] + 1, 51)
+    b = {"keypoints": 0.5 * seeded_randn(f"{tag}.kps", shape, seed), "future_keypoints": 0.5 * seeded_randn(f"{tag}.future", shape, seed)}
+    if meta.get("transfer", {}).get("case") == tag:
+        b["paired_keypoints"] = 0.5 * seeded_randn(f"{tag}.paired", shape, seed)
+        b["matched_keypoints"] = 0.5 * seeded_randn(f"{tag}.matched", shape, seed)
+    return {k: v.cuda() for k, v in b.items()}
+
+
+# ---- 3. end to end
+@pytest.mark.parametrize("tag", ["flow_f64_s8", "flow_f32_s50", "prior_f64_s50", "prior_f32_s8", "tie_f64_s8"])
+def test_evaluate_end_to_end_vs_the_fixture(tag):
+    meta, arr = load_golden("g13_behavior_eval")
+    c = meta["cases"][tag]
+    bn = _g13_model(meta, arr)
+    stats = _stats(arr[f"{tag}.mean"], arr[f"{tag}.std"], c["ignore"])
+    eps = seeded_randn(f"{tag}.xfer.eps0", (meta["batch"], 64), meta["seed"]).cuda()
+    ev = bn.evaluate([_g13_batch(meta, tag)], stats, n_samples=c["n_samples"], skip=meta["skip"], use_flow=c["flow"],
+                     z=_g13_noise(meta, tag), eps=eps)
+    lists = ev.lists()
+    for k in ("APD", "ASD", "FSD"):
+        np.testing.assert_allclose(lists[k], arr[f"{tag}.{k}"], err_msg=k, **E2E_TOL)
+    np.testing.assert_allclose(lists["ADE"], [c["ADE"]], **E2E_TOL)
+    np.testing.assert_allclose(lists["FDE"], [c["FDE"]], **E2E_TOL)
+    summ = ev.summary()
+    if meta["transfer"]["case"] == tag:
+        for k in ("ADE_c", "FDE_c", "recon_mu", "recon_std", "distance_mu", "distance_std"):
+            np.testing.assert_allclose(summ[k], meta["transfer"][k], err_msg=k, **E2E_TOL)
+    else:
+        assert "ADE_c" not in summ
+
+
+# ---- 4. / 5. batched sampling against the reference's loop structure; graph replay against eager
+def test_batched_sampling_equals_the_per_sample_loop():
+    """S passes of flow.reverse + generate_seq on the N scored rows (experiments/behavior_net.py:1182-1217) against one
+    batched pass over the N S rows.  Every kernel of both engines computes a row from that row alone, in the same order,
+    whatever the row count; roll-outs of 48 rows or more hand h on as tiles, fewer as rows (seq.BehaviorEngine._plan), an
+    equally exact fp32 path.  Measured on the MI355X: bit-identical (max |diff| 0); the tolerance is the contract."""
+    meta, arr = load_golden("g13_behavior_eval")
+    tag = "flow_f32_s50"
+    bn = _g13_model(meta, arr)
+    z = _g13_noise(meta, tag)
+    start = _g13_batch(meta, tag)["keypoints"][:, 1:][::meta["skip"]].contiguous()
+    t = start.shape[1]
+    with torch.no_grad():
+        batched = _E().sample_behaviors(bn.net, bn.latent_flow, start, z.shape[0], t, start_frame=t - 1, z=z)
+        loop = []
+        for s in range(z.shape[0]):
+            b = bn.latent_flow.reverse(z[s]).reshape(start.shape[0], -1)
+            xs, *_ = bn.net.generate_seq(b, start, len=t, start_frame=t - 1)
+            loop.append(xs)
+    loop = torch.stack(loop, dim=1)
+    diff = float((batched - loop).abs().max())
+    print(f"batched vs per-sample loop: max |diff| {diff:.3e}, bit-identical: {torch.equal(batched, loop)}")
+    np.testing.assert_allclose(batched.cpu().numpy(), loop.cpu().numpy(), rtol=1e-6, atol=1e-6)
+
+
+def test_graph_replay_equals_eager():
+    meta, arr = load_golden("g13_behavior_eval")
+    tag = "flow_f32_s50"
+    c = meta["cases"][tag]
+    stats = _stats(arr[f"{tag}.mean"], arr[f"{tag}.std"], c["ignore"])
+    out = {}
+    for graph in (False, True):
+        bn = _g13_model(meta, arr)
+        bn.net.engine().graph.enabled = graph
+        bn.latent_flow.flow.engine().graph.enabled = graph
+        runs = [bn.evaluate([_g13_batch(meta, tag)], stats, n_samples=c["n_samples"], z=_g13_noise(meta, tag)).lists()
+                for _ in range(3 if graph else 1)]                       # graph: warm-up, record, replay
+        out[graph] = runs[-1]
+    for k, v in out[False].items():
+        assert np.array_equal(v, out[True][k]), k
+
+
+# ---- 6. the reference width
+def test_reference_width_vs_the_oracle():
+    """H = 1024, flow_mid_channels 2048, 3 blocks, 2 sequences x 50 samples: the batched path against the CPU oracle's flow
+    reverse and roll-out, scored by the restatement."""
+    from oracle import behavior_oracle as B
+    from behavior_driven_video_synthesis_amd.models.flow.simple_flow import UnsupervisedTransformer2
+    from behavior_driven_video_synthesis_amd.models.pose_behavior_rnn import ResidualBehaviorNet
+    torch.manual_seed(7)
+    flow = UnsupervisedTransformer2(flow_in_channels=1024, flow_mid_channels=2048, flow_hidden_depth=2, n_flows=3)
+    fsd = flow.state_dict()
+    fsd = synth_behavior_state({k: list(v.shape) for k, v in fsd.items()}, 7, {k: v for k, v in fsd.items() if k.endswith("_shuffle_idx")})
+    for k in fsd:
+        if ".coupling.s." in k and ".main.6." in k:
+            fsd[k] = fsd[k] * 0.1          # (tests/test_hip_seq.py: an unsaturated flow, conditioned like a trained one)
+    flow.load_state_dict(fsd)
+    net = ResidualBehaviorNet(51, information_bottleneck=True, decoder_arch="lstm", dim_hidden_b=1024)
+    nsd = synth_behavior_state({k: list(v.shape) for k, v in net.state_dict().items()}, 7, {})
+    net.load_state_dict(nsd)
+    flow, net = flow.cuda(), net.cuda()
+    n_seq, s, t = 2, 50, 10
+    z = seeded_randn("width.z", (s, n_seq, 1024), 7)
+    start = 0.5 * seeded_randn("width.start", (n_seq, t, 51), 7)
+    future = 0.5 * seeded_randn("width.future", (n_seq, t + 1, 51), 7)
+    with torch.no_grad():
+        got = _E().sample_behaviors(net, flow, start.cuda(), s, t, start_frame=t - 1, z=z.cuda())
+    zr = z.transpose(0, 1).reshape(n_seq * s, 1024)
+    b_ref = B.flow_reverse(fsd, zr)
+    xs_ref, _ = B.generate_seq(nsd, b_ref, start.repeat_interleave(s, dim=0), t, t - 1)
+    xs_ref = xs_ref.reshape(n_seq, s, t, 51)
+    np.testing.assert_allclose(got.cpu().numpy(), xs_ref.numpy(), rtol=1e-3, atol=5e-4)
+    g = torch.Generator().manual_seed(7)
+    mean, std = (torch.randn(96, generator=g) * 300).double().numpy(), (50 + 200 * torch.rand(96, generator=g)).double().numpy()
+    ignore = list(range(0, 90, 2))[:45]
+    use = [d for d in range(96) if d not in set(ignore)]
+    m = _kernel_metrics(got.cpu().numpy(), future.numpy(), _stats(mean, std, ignore))
+    want = R.metrics(xs_ref.numpy(), future.numpy(), mean[use], std[use], False)
+    for k in ("APD", "ASD", "FSD", "minADE", "minFDE", "ADE", "FDE"):
+        np.testing.assert_allclose(m[k], want[k], err_msg=k, rtol=1e-3, atol=1e-4)
+
+
+def test_full_size_smoke():
+    """config/behavior_net.yaml's model (15 blocks, H = 1024) with its own initialisation: a 64-row batch, skip 4, 50 samples,
+    50 frames.  Finite metrics, and APD >= ASD (the mean over frames of d_t is at most sqrt(sum_t d_t^2) / sqrt(T))."""
+    from behavior_driven_video_synthesis_amd.experiments.behavior_net import BehaviorNet
+    torch.manual_seed(11)
+    bn = BehaviorNet(None, n_kps=51, device="cuda:0")
+    g = torch.Generator().manual_seed(11)
+    kps = (0.5 * torch.randn(64, 51, 51, generator=g)).cuda()
+    fut = (0.5 * torch.randn(64, 51, 51, generator=g)).cuda()
+    mean, std = (torch.randn(96, generator=g) * 300).double().numpy(), (50 + 200 * torch.rand(96, generator=g)).double().numpy()
+    ev = bn.evaluate([{"keypoints": kps, "future_keypoints": fut}], _stats(mean, std, list(range(45))), n_samples=50, skip=4)
+    lists = ev.lists()
+    assert lists["ASD"].shape == (16,) and lists["ADE"].shape == (1,)
+    for k, v in lists.items():
+        assert np.isfinite(v).all(), k
+    assert (lists["APD"] >= lists["ASD"]).all()
+
+
+# ---- 7. the inference engine after fused training steps
+def test_inference_after_fused_training_steps_uses_the_new_weights():
+    """generate_seq, three fused cVAE steps (graph on, update), generate_seq again: equal, bit for bit, to a fresh net loaded
+    with the current state_dict.  FusedAdam writes the parameters through a kernel, so no version counter moves: the
+    inference engine's weight images must be invalidated by the step itself."""
+    from behavior_driven_video_synthesis_amd.experiments.behavior_net import BehaviorNet, DEFAULT_CONFIG
+    from behavior_driven_video_synthesis_amd.models.pose_behavior_rnn import ResidualBehaviorNet
+    cfg = copy.deepcopy(DEFAULT_CONFIG)
+    cfg["architecture"].update(dim_hidden_b=64, n_flows=2, flow_mid_channels_factor=2, flow_hidden_depth=1)
+    cfg["training"].update(batch_size=6, lr_init=1e-2)
+    torch.manual_seed(5)
+    bn = BehaviorNet(cfg, n_kps=51, device="cuda:0", hip_graph=True)
+    b = seeded_randn("stale.b", (6, 64), 5).cuda()
+    x = (0.5 * seeded_randn("stale.x", (6, 7, 51), 5)).cuda()
+    with torch.no_grad():
+        before, *_ = bn.net.generate_seq(b, x, len=6, start_frame=6)
+    for it in range(3):
+        kps = 0.5 * seeded_randn(f"stale.kps{it}", (6, 8, 51), 5)
+        bn.train_fn({"keypoints": kps.cuda()}, eps=seeded_randn(f"stale.eps{it}", (6, 64), 5).cuda(), update=True)
+    fresh = ResidualBehaviorNet(51, information_bottleneck=True, decoder_arch="lstm", dim_hidden_b=64).cuda()
+    fresh.load_state_dict(bn.net.state_dict())
+    with torch.no_grad():
+        after, *_ = bn.net.generate_seq(b, x, len=6, start_frame=6)
+        want, *_ = fresh.generate_seq(b, x, len=6, start_frame=6)
+    assert not torch.equal(before, want)                 # the steps moved the weights
+    assert torch.equal(after, want)
