@@ -13,7 +13,11 @@ stickman input is drawn by the GPU rasteriser from synthetic 17-joint skeletons 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W              # ... or is started as one rank of N
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run does what that line's headline needs and nothing more: it sets up, settles the
+step (records the hipGraph), runs the W warm-up steps, times the K steps, writes --dump-outputs if asked and prints the line.
+  --full        measures everything else as well: the host's issue time per step, the roofline region, the `variants` rows,
+                the render / behaviour rows, the config-1 rows and the CPU baseline (below).  Under --full each of them can
+                still be left out with its --no-* flag; without --full they are all off.
   --gpus N      replaces nn.DataParallel (experiments/shape_and_pose_net.py:213-214,223-224,230-233): one process per GPU,
                 gradient buckets all-reduced over RCCL while backward runs.  Called WITHOUT a torchrun environment and
                 with N > 1, bench.py starts `python -m torch.distributed.run --nproc-per-node N ... bench.py <same args>`
@@ -21,11 +25,11 @@ Rank 0 prints ONE JSON line.
                 0's JSON line and the child's exit code, and fails non-zero if fewer than N GPUs are visible or the line's
                 `n_gpus` / `rccl_world_size` is not N.  `VUNET_DP_FORCE=1 python bench.py --gpus 1` takes the same route
                 with one rank (launcher + one-rank RCCL communicator on a 1-GPU box).
-  roofline      measured live with HIP events around every conv-family launch in an extra instrumented region
+  roofline      (--full) measured live with HIP events around every conv-family launch in an extra instrumented region
                 after the timed one (so the events do not perturb `value`); `traffic` comes from the committed
                 rocprofv3 PMC summary profiles/<round>_pmc_traffic.json (tools/profile.sh), named in
                 `traffic_source` with the commit it was collected at, and is null if the dominant kernel is not in it.
-  cpu_baseline  the CPU oracle (oracle/vunet_oracle.py, a port of the reference path, pinned to the reference by
+  cpu_baseline  (--full) the CPU oracle (oracle/vunet_oracle.py, a port of the reference path, pinned to the reference by
                 tests/golden) timed on this host's cores as BASELINE.md section 4 defines it: the SAME bs-16 256^2
                 step, 1 warm-up + 3 timed steps, median -- on min(host cores, --cpu-threads = 64) threads (with hundreds
                 of threads PyTorch-CPU thrashes on this path: a run with all 256 did not finish in 35 minutes), inside
@@ -78,13 +82,16 @@ def parse():
                     help="replay the step from a captured multi-stream hipGraph (the host then issues one launch per step "
                          "instead of ~600).  auto: on wherever the trainer can capture the configuration, reported in "
                          "config.hip_graph; the config-1 row always reports both")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-config1", action="store_true", help="skip the config-1 (Market 128^2, bs 2) plumbing rows")
-    ap.add_argument("--no-render", action="store_true", help="skip the config-5 render-loop row")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too: host issue time, roofline, variants, render and "
+                         "behaviour rows, config-1 rows, CPU baseline (off: only what the headline needs runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline region")
+    ap.add_argument("--no-config1", action="store_true", help="with --full: skip the config-1 (Market 128^2, bs 2) plumbing rows")
+    ap.add_argument("--no-render", action="store_true", help="with --full: skip the config-5 render-loop and behaviour rows")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip the `variants` rows (the step with the regressor side loop / the adversarial term / both, and the "
-                         "fp32-input-MFMA precision, 10 replayed steps each on this box)")
+                    help="with --full: skip the `variants` rows (the step with the regressor side loop / the adversarial term / "
+                         "both, and the fp32-input-MFMA precision, 10 replayed steps each on this box)")
     ap.add_argument("--cpu-budget", type=float, default=100.0, help="seconds of CPU work allowed for the bs-16 baseline")
     ap.add_argument("--cpu-threads", type=int, default=64, help="cap on the CPU baseline's threads")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -97,6 +104,8 @@ def parse():
         ap.error("--steps must be at least 1 (the timed region is --steps training steps)")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if not args.full:   # a plain run: the headline and nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_config1 = args.no_render = args.no_variants = True
     return args
 
 
@@ -986,16 +995,18 @@ def main():
         sizes = dump_outputs(args.dump_outputs, out, trainer.vunet)
         print(f"bench.py: wrote {len(sizes)} arrays ({sum(sizes.values())} bytes) of the last timed step to {args.dump_outputs}",
               file=sys.stderr)
-    # host time to ISSUE one step: measured on steps that start with an empty device queue (inside the timed loop the host
-    # runs ahead until the launch queue is full and is then throttled to the GPU's pace, which says nothing about the host)
-    issue = []
-    for _ in range(3):
+    # (--full) host time to ISSUE one step: measured on steps that start with an empty device queue (inside the timed loop the
+    # host runs ahead until the launch queue is full and is then throttled to the GPU's pace, which says nothing about the host)
+    host_issue_ms = None
+    if args.full:
+        issue = []
+        for _ in range(3):
+            sync_all()
+            t0 = time.perf_counter()
+            trainer.train_fn(batch)
+            issue.append(time.perf_counter() - t0)
         sync_all()
-        t0 = time.perf_counter()
-        trainer.train_fn(batch)
-        issue.append(time.perf_counter() - t0)
-    sync_all()
-    host_issue_ms = 1e3 * statistics.median(issue)
+        host_issue_ms = 1e3 * statistics.median(issue)
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

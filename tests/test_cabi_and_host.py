@@ -476,6 +476,21 @@ def test_bench_watchdog_kills_a_silent_child_tree_and_keeps_a_talking_one(tmp_pa
     assert rc == 0 and reason is None and phase == "c" and out.strip() == '{"metric": 1}' and "[bench heartbeat] b" in echo.getvalue()
 
 
+def test_bench_plain_run_measures_the_headline_only(monkeypatch):
+    """bench.py without --full runs none of the rows beyond the headline; with --full each row is on unless its --no-* flag
+    leaves it out."""
+    import sys
+    bench = _load_bench()
+    extras = ("no_cpu_baseline", "no_roofline", "no_config1", "no_render", "no_variants")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-render"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, k) for k in extras)
+    assert (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-render"])
+    a = bench.parse()
+    assert a.full and a.no_render and not any(getattr(a, k) for k in extras if k != "no_render")
+
+
 def test_bench_graph_guard_prints_the_eager_line_when_the_replay_never_returns(tmp_path):
     """The in-process net of a multi-rank run: the eager measurement is taken first; if the graph phase does not come back the
     guard writes THAT line (with the reason) and leaves -- exit code 0, one JSON line."""

@@ -12,6 +12,6 @@ python3 tools/time_seq_train.py --reps 20 > $OUT/${TAG}_seq_train_time.json 2>> 
 python3 tools/time_seq_train.py --reps 20 --rows 16 >> $OUT/${TAG}_seq_train_time.json 2>> $OUT/${TAG}_profile.log
 python3 tools/time_seq_train.py --stage cvae --reps 20 > $OUT/${TAG}_seq_train_cvae_time.json 2>> $OUT/${TAG}_profile.log
 python3 tools/aten_in_step.py > $OUT/${TAG}_aten_in_step.txt 2>> $OUT/${TAG}_profile.log
-python3 bench.py > $OUT/${TAG}_bench_h2.json 2> $OUT/${TAG}_bench_h2.err
-VUNET_DP_FORCE=1 python3 bench.py --gpus 1 --no-cpu-baseline --no-config1 --no-render --no-variants > $OUT/${TAG}_bench_dp_forced.json 2> $OUT/${TAG}_bench_dp_forced.err
+python3 bench.py --full > $OUT/${TAG}_bench_h2.json 2> $OUT/${TAG}_bench_h2.err
+VUNET_DP_FORCE=1 python3 bench.py --gpus 1 --full --no-cpu-baseline --no-config1 --no-render --no-variants > $OUT/${TAG}_bench_dp_forced.json 2> $OUT/${TAG}_bench_dp_forced.err
 ls -la $OUT/${TAG}_*
