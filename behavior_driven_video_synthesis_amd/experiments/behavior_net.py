@@ -193,7 +193,8 @@ class BehaviorNet:
 
     # ---- scoring (experiments/behavior_net.py:1112-1301, lib/logging.py:2079-2093)
     @torch.no_grad()
-    def evaluate(self, batches, stats, n_samples: int = 50, skip: int = 4, use_flow: bool = True, z=None, eps=None):
+    def evaluate(self, batches, stats, n_samples: int = 50, skip: int = 4, use_flow: bool = True, z=None, eps=None,
+                 classifier_study: bool = False, study_kwargs=None, study_noise=None):
         """The reference's per-batch metric recipe of ``run_inference`` over an iterable of dict batches -> a
         ``behavior_eval.BehaviorEvaluator`` (``.summary()``: the means the reference prints; ``.lists()``: the lists).
 
@@ -206,11 +207,23 @@ class BehaviorNet:
         Sampling (:1182-1217): ``n_samples`` behaviours per scored row, from ``target_s[::skip]`` at start_frame T - 1, through
         the flow (``use_flow``) or straight from the prior.  ``stats``: ``behavior_eval.PoseStats`` of the dataset.
         ``z``: the sampling noise, [n_samples, B / skip, H] or a list with one per batch (None: drawn); ``eps``: the transfer
-        metrics' reparametrisation noise [B, H], or a list (None: drawn)."""
+        metrics' reparametrisation noise [B, H], or a list (None: drawn).
+
+        ``classifier_study`` (needs ``paired_keypoints`` and ``matched_keypoints``): the second half of ``run_inference``.  While
+        fewer than ``max_rows`` (``study_kwargs``, default 25 000) rows are held, every batch's transfer metrics run and its
+        sequences are collected (:1262-1295): X_orig = x_s, X_prior = net(x_s, target_s, sample=True) from frame T - 1,
+        X_cross / X_self = generate_seq(mu, x_t / x_s) from frame 0, X_flow = generate_seq(flow.reverse(noise), target_s) from
+        frame T - 1 (with the flow), X_embed = mu; the batch after the cap is still scored, then the loop ends.  After the loop
+        ``behavior_eval.classifier_study`` runs on what was collected (the other ``study_kwargs``) and its result is
+        ``ev.study``.  ``study_noise``: per batch (or one for all) {"prior": [B, H], "flow": [B, H]} (None: drawn)."""
         from .. import behavior_eval as E
         ev = E.BehaviorEvaluator()
         flow = self.latent_flow if use_flow else None
+        kw = dict(study_kwargs or {})
+        study = E.StudySet(kw.pop("max_rows", 25000)) if classifier_study else None
         for bi, batch in enumerate(batches):
+            if study is not None and not ("paired_keypoints" in batch and "matched_keypoints" in batch):
+                raise ValueError("classifier_study needs paired_keypoints and matched_keypoints in every batch")
             kps = batch["keypoints"].to(self.device, torch.float32)
             x_s, target_s = kps[:, :-1].contiguous(), kps[:, 1:].contiguous()
             t = x_s.shape[1]
@@ -218,12 +231,46 @@ class BehaviorNet:
             zb = z[bi] if isinstance(z, (list, tuple)) else z
             samples = E.sample_behaviors(self.net, flow, target_s[::skip].contiguous(), n_samples, t, start_frame=t - 1, z=zb)
             ev.add(E.sample_metrics(samples, fut, stats))
-            if "paired_keypoints" in batch and "matched_keypoints" in batch:
+            if study is not None:
+                if study.full:
+                    break
+                self._collect_study(batch, x_s, target_s, flow, study, eps[bi] if isinstance(eps, (list, tuple)) else eps,
+                                    study_noise[bi] if isinstance(study_noise, (list, tuple)) else study_noise, ev)
+            elif "paired_keypoints" in batch and "matched_keypoints" in batch:
                 x_t = batch["paired_keypoints"].to(self.device, torch.float32)[:, :-1].contiguous()
                 x_rel = batch["matched_keypoints"].to(self.device, torch.float32)[:, :-1].contiguous()
                 eb = eps[bi] if isinstance(eps, (list, tuple)) else eps
                 ev.add(E.transfer_metrics(self.net, x_s, x_t, x_rel, eps=eb))
+        if study is not None:
+            ev.study_set = study
+            ev.study = E.classifier_study(study, **kw)
         return ev
+
+    @torch.no_grad()
+    def _collect_study(self, batch, x_s, target_s, flow, study, eps, noise, ev):
+        """One batch of :1262-1295: the transfer metrics (their mu reused) and the five sequence sets."""
+        from .. import behavior_eval as E
+        t = x_s.shape[1]
+        x_t = batch["paired_keypoints"].to(self.device, torch.float32)[:, :-1].contiguous()
+        x_rel = batch["matched_keypoints"].to(self.device, torch.float32)[:, :-1].contiguous()
+        m, mu = E.transfer_metrics(self.net, x_s, x_t, x_rel, eps=eps, return_mu=True)
+        ev.add(m)
+        noise = noise or {}
+        h = self.net.dim_hidden_b
+        zp = noise.get("prior")
+        if zp is None:
+            zp = torch.randn(x_s.shape[0], h, device=x_s.device)
+        prior = self.net(x_s, target_s, t, sample=True, start_frame=t - 1, eps=zp.to(x_s.device, torch.float32))[0]
+        cross = self.net.generate_seq(mu, x_t, t, start_frame=0)[0]
+        self_ = self.net.generate_seq(mu, x_s, t, start_frame=0)[0]
+        xf = None
+        if flow is not None:
+            zf = noise.get("flow")
+            if zf is None:
+                zf = torch.randn(x_s.shape[0], h, device=x_s.device)
+            bf = flow.reverse(zf.to(x_s.device, torch.float32).contiguous()).reshape(x_s.shape[0], h)
+            xf = self.net.generate_seq(bf, target_s, t, start_frame=t - 1)[0]
+        study.add(x_s, prior, cross, self_, mu, flow=xf)
 
     # ---- checkpoints in the reference's layout (:1003-1011: model / optimizer / flow / flow optimizer)
     def state_dict(self) -> dict:
