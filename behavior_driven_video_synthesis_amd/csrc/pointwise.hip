@@ -21,6 +21,22 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// 2x2 max-pool window (e0, e1, e2, e3 in scan order) under ATen's max_pool2d rule: a NaN beats every number and the LAST NaN
+// in scan order is the maximum (its value is the output, its position gets the gradient); without a NaN the value is the
+// maximum and the FIRST element equal to it gets the gradient.
+__device__ __forceinline__ float pool2_max(float e0, float e1, float e2, float e3) {
+  const float m = fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
+  return e3 != e3 ? e3 : (e2 != e2 ? e2 : (e1 != e1 ? e1 : (e0 != e0 ? e0 : m)));
+}
+__device__ __forceinline__ int pool2_route(float e0, float e1, float e2, float e3) {
+  const float m = fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
+  if (e3 != e3) return 3;
+  if (e2 != e2) return 2;
+  if (e1 != e1) return 1;
+  if (e0 != e0) return 0;
+  return e0 == m ? 0 : (e1 == m ? 1 : (e2 == m ? 2 : 3));
+}
+
 // ------------------------------------------------------------------ depth/space shuffles
 // out[n,c,2h+i,2w+j] = in[n,(2i+j)*Cq+c,h,w]
 __global__ void d2s_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int C, int H, int W) {
@@ -106,7 +122,7 @@ __global__ void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ 
   EW_LOOP(i, n) {
     float v = x[i];
     if (act == ACT_ELU) v = elu_f(v);
-    else if (act == ACT_RELU) v = v > 0.f ? v : 0.f;
+    else if (act == ACT_RELU) v = v <= 0.f ? 0.f : v;   // a NaN passes through (torch.relu)
     else if (act == ACT_SIGMOID) v = 1.f / (1.f + __expf(-v));
     else if (act == ACT_LRELU) v = v > 0.f ? v : v * slope;
     y[i] = v;
@@ -120,13 +136,13 @@ extern "C" int vunet_act_fwd(const float* x, float* y, int32_t act, float slope,
 __global__ void act_bwd_out_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dx,
                                    int act, float slope, int64_t n) {
   EW_LOOP(i, n) {
+    // ReLU as ATen's threshold_backward: a select (dy where y is NaN, 0 where y <= 0 whatever dy is)
     const float o = y[i];
     float g = 1.f;
     if (act == ACT_SIGMOID) g = o * (1.f - o);
-    else if (act == ACT_RELU) g = o > 0.f ? 1.f : 0.f;
     else if (act == ACT_LRELU) g = o > 0.f ? 1.f : slope;
     else if (act == ACT_ELU) g = o > 0.f ? 1.f : o + 1.f;
-    dx[i] = dy[i] * g;
+    dx[i] = (act == ACT_RELU && o <= 0.f) ? 0.f : dy[i] * g;
   }
 }
 extern "C" int vunet_act_bwd_from_out(const float* y, const float* dy, float* dx, int32_t act, float slope, int64_t n,
@@ -213,7 +229,7 @@ __global__ __launch_bounds__(256) void l1_pool_fwd_kernel(const float* __restric
     const float2 b0 = *reinterpret_cast<const float2*>(b + i0), b1 = *reinterpret_cast<const float2*>(b + i0 + W);
     const float2 a0 = *reinterpret_cast<const float2*>(a + i0), a1 = *reinterpret_cast<const float2*>(a + i0 + W);
     s += (fabsf(a0.x - b0.x) + fabsf(a0.y - b0.y)) + (fabsf(a1.x - b1.x) + fabsf(a1.y - b1.y));
-    y[o] = fmaxf(fmaxf(b0.x, b0.y), fmaxf(b1.x, b1.y));
+    y[o] = pool2_max(b0.x, b0.y, b1.x, b1.y);
   }
   const float tsum = block_sum_256(s, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = tsum;
@@ -240,7 +256,7 @@ __global__ void l1_bwd_kernel(const float* __restrict__ a, const float* __restri
     const float d = bi - a[i];
     const float g = d > 0.f ? gs : (d < 0.f ? -gs : 0.f);
     float v = (add ? add[i] : 0.f) + g;
-    if (relu_mask && !(bi > 0.f)) v = 0.f;   // b is a ReLU output: the layer that produced it would zero this entry anyway
+    if (relu_mask && bi <= 0.f) v = 0.f;   // b is a ReLU output: the layer that produced it would zero this entry anyway
     db[i] = v;
     vmax = fmaxf(vmax, fabsf(v));
   }
@@ -379,7 +395,7 @@ __global__ void maxpool2_fwd_kernel(const float* __restrict__ x, float* __restri
     const float* r0 = x + (nc * H + 2 * oh) * W + 2 * ow;
     const float2 a = *reinterpret_cast<const float2*>(r0);
     const float2 b = *reinterpret_cast<const float2*>(r0 + W);
-    y[o] = fmaxf(fmaxf(a.x, a.y), fmaxf(b.x, b.y));
+    y[o] = pool2_max(a.x, a.y, b.x, b.y);
   }
 }
 __global__ void maxpool2_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -393,11 +409,10 @@ __global__ void maxpool2_bwd_kernel(const float* __restrict__ x, const float* __
     const int64_t nc = t / Ho;
     const int64_t i0 = (nc * H + 2 * oh) * W + 2 * ow;
     const float m = y[o];
-    const float g = (relu_mask && !(m > 0.f)) ? 0.f : dy[o];   // x is a ReLU output: its layer's backward zeroes x <= 0
+    const float g = (relu_mask && m <= 0.f) ? 0.f : dy[o];   // x is a ReLU output: its layer's backward zeroes x <= 0
     const float2 a = *reinterpret_cast<const float2*>(x + i0);
     const float2 b = *reinterpret_cast<const float2*>(x + i0 + W);
-    // first maximum in window scan order gets the gradient (ATen max_pool2d semantics)
-    const int k = a.x == m ? 0 : (a.y == m ? 1 : (b.x == m ? 2 : 3));
+    const int k = pool2_route(a.x, a.y, b.x, b.y);   // (ATen max_pool2d semantics, NaN included)
     *reinterpret_cast<float2*>(dx + i0) = make_float2(k == 0 ? g : 0.f, k == 1 ? g : 0.f);
     *reinterpret_cast<float2*>(dx + i0 + W) = make_float2(k == 2 ? g : 0.f, k == 3 ? g : 0.f);
   }
@@ -425,16 +440,15 @@ __global__ void l1_pool_bwd_kernel(const float* __restrict__ a, const float* __r
     const int64_t i0 = (nc * H + 2 * oh) * W + 2 * ow;
     const float2 b0 = *reinterpret_cast<const float2*>(b + i0), b1 = *reinterpret_cast<const float2*>(b + i0 + W);
     const float2 a0 = *reinterpret_cast<const float2*>(a + i0), a1 = *reinterpret_cast<const float2*>(a + i0 + W);
-    const float m = fmaxf(fmaxf(b0.x, b0.y), fmaxf(b1.x, b1.y));
     const float g = dyp ? dyp[o] : 0.f;
-    const int k = b0.x == m ? 0 : (b0.y == m ? 1 : (b1.x == m ? 2 : 3));   // first maximum in scan order (ATen max_pool2d)
+    const int k = pool2_route(b0.x, b0.y, b1.x, b1.y);   // (ATen max_pool2d semantics, NaN included)
     const float bv[4] = {b0.x, b0.y, b1.x, b1.y}, av[4] = {a0.x, a0.y, a1.x, a1.y};
     float v[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float d = bv[e] - av[e];
       float r = (k == e ? g : 0.f) + (d > 0.f ? gs : (d < 0.f ? -gs : 0.f));
-      if (relu_mask && !(bv[e] > 0.f)) r = 0.f;
+      if (relu_mask && bv[e] <= 0.f) r = 0.f;
       v[e] = r;
       vmax = fmaxf(vmax, fabsf(r));
     }

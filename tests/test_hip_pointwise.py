@@ -1,0 +1,1076 @@
+"""-m gpu: the glue kernels (csrc/pointwise.hip, the batched weight-norm launches of csrc/weightnorm.hip, the strided GEMM of
+csrc/seq_cls.hip) one op at a time against float64 torch on the CPU computing the same formula.
+
+Every bound is tied to the op's arithmetic (U = 2^-24, the unit roundoff of fp32):
+  * index ops (shuffles, crops, max-pool and its routing): bit-exact;
+  * elementwise fp32 arithmetic: a few U of the float64 value, plus the error of ``__expf`` where the kernel uses it
+    (``__expf(x)`` = exp2(x * log2 e) on the hardware: the rounded product puts ~|x| U into the result's relative error);
+  * reductions: c * U * sum|terms|, c = the depth of the kernel's summation chain (serial per-thread terms + 6 wavefront
+    shuffle levels + the LDS hop), written out at each test.
+Non-finite inputs are held to ATen's (fp32, CPU) NaN / inf pattern.
+
+The census in tests/test_cabi_and_host.py requires every ``extern "C" int vunet_*`` of csrc/pointwise.hip and
+csrc/weightnorm.hip to be named in this file or listed in NOT_HELD with a reason.
+"""
+import ctypes
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -24
+TINY = 2.0 ** -126           # FLT_MIN: results in the denormal range may be flushed
+WRAP = 2048 * 256            # the elementwise grid-stride loops run at most 2048 x 256 threads
+SIZES = [1, 3, 63, 257, 1000, WRAP + 1237]
+
+NOT_HELD = {
+    "vunet_u8_to_unit": "called by nothing in the package",
+    "vunet_set_dropout_step": "stores a device pointer for the dropout kernels; no arithmetic",
+    "vunet_set_tuning": "dispatcher override for tests / tuning; no kernel",
+    "vunet_abi_version": "constant; tests/test_cabi_and_host.py::test_library_exports_every_declared_symbol",
+    "vunet_absmax_partials": "held by tests/test_hip_x6.py (the split-fp16 scale)",
+    "vunet_dropout_mask": "held bit-exactly against the host hash by tests/test_hip_primitives.py",
+    "vunet_unit_sample": "random draw; held by tests/test_hip_primitives.py",
+    "vunet_sum_amax": "held bit-exactly by tests/test_hip_primitives.py",
+    "vunet_l1_mean_fwd": "held by tests/test_hip_primitives.py::test_l1_tap_and_pool_forward_in_one_pass",
+    "vunet_l1_mean_bwd": "held by tests/test_hip_primitives.py::test_l1_tap_and_pool_backward_in_one_pass",
+    "vunet_l1_mean_bwd_amax": "held by tests/test_hip_primitives.py::test_l1_tap_and_pool_backward_in_one_pass",
+    "vunet_total_loss": "one-thread scalar glue; held by the training-step tests against the oracle",
+    "vunet_total_loss_bwd": "one-thread scalar glue; held by the training-step tests against the oracle",
+    "vunet_gamma_update": "one-thread scalar glue; held by the training-step tests against the oracle",
+    "vunet_set_schedule": "stores three host scalars to the device; no arithmetic",
+    "vunet_x6_mtiles": "host geometry helper, mirrored by ops.x6_mtiles",
+    "vunet_x6_image_bytes": "host geometry helper, mirrored by ops.x6_image_units",
+}
+
+
+def _ops():
+    from behavior_driven_video_synthesis_amd import ops
+    return ops
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _f64(t):
+    return t.detach().cpu().double()
+
+
+def assert_ulps(got, ref, bound, name="", aten=None):
+    """|got - ref| <= bound elementwise where ref is finite; where ``aten`` (ATen's fp32 result) or ref is NaN / inf, got
+    must be NaN / the same inf."""
+    got = _f64(got).reshape(-1)
+    ref = ref.double().reshape(-1)
+    pattern = (aten.double().reshape(-1) if aten is not None else ref)
+    nan = torch.isnan(pattern)
+    assert torch.equal(torch.isnan(got), nan), f"{name}: NaN pattern differs at {torch.nonzero(torch.isnan(got) != nan)[:8].tolist()}"
+    inf = torch.isinf(pattern)
+    assert torch.equal(got[inf], pattern[inf]), f"{name}: inf pattern differs"
+    fin = torch.isfinite(pattern) & torch.isfinite(ref)
+    assert torch.isfinite(got[fin]).all(), f"{name}: non-finite where the reference is finite"
+    b = bound.double().reshape(-1) if torch.is_tensor(bound) else torch.full_like(ref, float(bound))
+    err = (got[fin] - ref[fin]).abs()
+    over = err > b[fin]
+    if over.any():
+        i = int(torch.nonzero(over)[0])
+        raise AssertionError(f"{name}: {int(over.sum())} elements over the bound; first: got {float(got[fin][i])!r} ref "
+                             f"{float(ref[fin][i])!r} err {float(err[i]):.3e} bound {float(b[fin][i]):.3e}")
+
+
+def _special():
+    v = [0.0, -0.0, 1e-30, -1e-30, 1.0, -1.0, 88.0, -88.0, 100.0, -100.0, float("inf"), float("-inf"), float("nan"),
+         0.5, -0.5, 3.0, -3.0, 1e-7, -1e-7, 20.0, -20.0]
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def _mixed(n, seed):
+    """n fp32 values: the special values first, then normals of a few scales."""
+    g = _gen(seed)
+    x = torch.randn(n, generator=g) * torch.tensor([0.01, 1.0, 8.0])[torch.randint(0, 3, (n,), generator=g)]
+    s = _special()
+    k = min(n, s.numel())
+    x[:k] = s[:k]
+    return x
+
+
+# ------------------------------------------------------------------------------------------------ index ops: bit-exact
+def _d2s_ref(x):
+    n, c, h, w = x.shape
+    return x.view(n, 2, 2, c // 4, h, w).permute(0, 3, 4, 1, 5, 2).reshape(n, c // 4, 2 * h, 2 * w)
+
+
+def _s2d_ref(x):
+    n, c, h, w = x.shape
+    return x.view(n, c, h // 2, 2, w // 2, 2).permute(0, 3, 5, 1, 2, 4).reshape(n, 4 * c, h // 2, w // 2)
+
+
+def _kernels_run(fn):
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return {e.key for e in prof.key_averages()}
+
+
+@pytest.mark.parametrize("shape", [(1, 4, 1, 1), (2, 12, 3, 5), (1, 8, 17, 2), (3, 16, 64, 48)])
+def test_depth_to_space_bit_exact(shape):
+    """vunet_depth_to_space (ops.DepthToSpace) and its backward (vunet_space_to_depth): index permutations, bit for bit."""
+    ops = _ops()
+    x = torch.randn(*shape, generator=_gen(1))
+    y = ops.DepthToSpace.apply(x.cuda())
+    assert torch.equal(y.cpu(), _d2s_ref(x))
+    back = ops.SpaceToDepth.apply(y)
+    assert torch.equal(back.cpu(), x)
+
+
+@pytest.mark.parametrize("shape,vec", [((1, 1, 2, 2), False), ((2, 3, 6, 10), False), ((1, 5, 4, 8), True),
+                                       ((2, 7, 10, 24), True), ((4, 32, 64, 64), True), ((3, 40, 66, 66), False)])
+def test_space_to_depth_scalar_and_vector_forms(shape, vec):
+    """vunet_space_to_depth: the per-element s2d_kernel (W % 8 != 0) and the 16-byte s2d_vec_kernel (W % 8 == 0), both
+    bit-exact; the profiler shows which one ran.  (4, 32, 64, 64) runs past the grid-stride cap of the scalar form's
+    launch size; (3, 40, 66, 66) does for the scalar form."""
+    ops = _ops()
+    x = torch.randn(*shape, generator=_gen(2))
+    xd = x.cuda()
+    out = {}
+    names = _kernels_run(lambda: out.setdefault("y", ops.SpaceToDepth.apply(xd)))
+    assert torch.equal(out["y"].cpu(), _s2d_ref(x))
+    ran_vec = any("s2d_vec_kernel" in k for k in names)
+    ran_scalar = any("s2d_kernel" in k and "s2d_vec_kernel" not in k for k in names)
+    assert (ran_vec, ran_scalar) == (vec, not vec), names
+    assert torch.equal(ops.DepthToSpace.apply(out["y"]).cpu(), x)
+
+
+def _crop(ops, x, off, p, bwd_dy=None):
+    n, c, h, w = x.shape
+    if bwd_dy is None:
+        y = torch.empty(n, c, p, p, device="cuda")
+        ops._call("vunet_crop_window", ops._p(x), ops._p(y), n * c, h, w, p, ops._p(off), ops._stream())
+        return y
+    dx = torch.zeros(n, c, h, w, device="cuda")
+    ops._call("vunet_crop_window_bwd", ops._p(bwd_dy), ops._p(dx), n * c, h, w, p, ops._p(off), ops._stream())
+    return dx
+
+
+@pytest.mark.parametrize("shape,p", [((1, 1, 5, 5), 5), ((2, 3, 9, 7), 4), ((3, 2, 16, 20), 16), ((130, 1, 70, 66), 64)])
+def test_crop_window_reads_its_corner_from_device_memory(shape, p):
+    """vunet_crop_window / vunet_crop_window_bwd: corner (0, 0), then (H - P, W - P) written into the SAME device buffer
+    between two calls with identical launch arguments; P = H covered; (130, 1, 70, 66) wraps the grid-stride loop.  The
+    backward scatters into zeros: every element outside the window stays 0.  Only valid corners."""
+    ops = _ops()
+    n, c, h, w = shape
+    x = torch.randn(*shape, generator=_gen(3))
+    xd = x.cuda()
+    off = torch.zeros(2, dtype=torch.int32, device="cuda")
+    dy = torch.randn(n, c, p, p, generator=_gen(4))
+    for oy, ox in ((0, 0), (h - p, w - p), ((h - p) // 2, (w - p + 1) // 2)):
+        off.copy_(torch.tensor([oy, ox], dtype=torch.int32))
+        y = _crop(ops, xd, off, p)
+        assert torch.equal(y.cpu(), x[:, :, oy:oy + p, ox:ox + p]), (oy, ox)
+        dx = _crop(ops, xd, off, p, bwd_dy=dy.cuda()).cpu()
+        want = torch.zeros_like(x)
+        want[:, :, oy:oy + p, ox:ox + p] = dy
+        assert torch.equal(dx, want), (oy, ox)
+    # through the autograd wrapper, the same device corner
+    off.copy_(torch.tensor([h - p, 0], dtype=torch.int32))
+    xr = xd.clone().requires_grad_(True)
+    yy = ops.CropWindow.apply(xr, off, p)
+    yy.backward(dy.cuda())
+    want = torch.zeros_like(x)
+    want[:, :, h - p:, :p] = dy
+    assert torch.equal(yy.detach().cpu(), x[:, :, h - p:, :p]) and torch.equal(xr.grad.cpu(), want)
+
+
+def _pool_input(nc, h, w, seed, kind):
+    g = _gen(seed)
+    if kind == "ties":        # small integers: many equal maxima in a window
+        x = torch.randint(-2, 3, (nc, h, w), generator=g).float()
+    elif kind == "relu":      # a ReLU output: all-zero windows and ties at 0
+        x = torch.relu(torch.randint(-3, 2, (nc, h, w), generator=g).float())
+    elif kind == "nonfinite":
+        x = torch.randn(nc, h, w, generator=g)
+        r = torch.rand(nc, h, w, generator=g)
+        x[r < 0.15] = float("nan")
+        x[(r >= 0.15) & (r < 0.2)] = float("inf")
+        x[(r >= 0.2) & (r < 0.25)] = float("-inf")
+    else:
+        x = torch.randn(nc, h, w, generator=g)
+    return x
+
+
+def _pool_ref(x, dy, relu):
+    """ATen's max_pool2d forward and backward on the CPU in fp32 (exact: max and routing), ReLU mask as threshold_backward."""
+    xr = x.clone().unsqueeze(0).requires_grad_(True)
+    y = F.max_pool2d(xr, 2)
+    y.backward(dy.unsqueeze(0))
+    dx = xr.grad[0]
+    if relu:
+        dx = torch.where(x <= 0, torch.zeros_like(dx), dx)
+    return y.detach()[0], dx
+
+
+POOL_SHAPES = [(1, 2, 2), (3, 2, 6), (2, 6, 4), (5, 12, 10), (160, 128, 130)]
+
+
+@pytest.mark.parametrize("shape", POOL_SHAPES)
+@pytest.mark.parametrize("kind", ["randn", "ties", "relu", "nonfinite"])
+def test_maxpool2_forward_and_routing_bit_exact(shape, kind):
+    """vunet_maxpool2_fwd / vunet_maxpool2_bwd / vunet_maxpool2_bwd_relu against ATen's max_pool2d: the pooled values and
+    the routed gradient bit for bit.  Ties: the first maximum in scan order gets the gradient (all-zero windows under the
+    ReLU mask: zero gradient).  NaN: the output is NaN and the LAST NaN in scan order gets the gradient.  (160, 128, 130)
+    wraps the grid-stride loop."""
+    ops = _ops()
+    nc, h, w = shape
+    x = _pool_input(nc, h, w, 10 + h, kind)
+    if kind == "relu":
+        x = torch.where(torch.isnan(x), x, x.clamp_min(0))
+    dy = torch.randn(nc, h // 2, w // 2, generator=_gen(11))
+    xd, dyd = x.cuda(), dy.cuda()
+    y = torch.empty(nc, h // 2, w // 2, device="cuda")
+    ops._call("vunet_maxpool2_fwd", ops._p(xd), ops._p(y), nc, h, w, ops._stream())
+    for relu in (False, True):
+        want_y, want_dx = _pool_ref(x, dy, relu)
+        assert torch.equal(torch.isnan(y.cpu()), torch.isnan(want_y))
+        assert torch.equal(torch.nan_to_num(y.cpu(), nan=7.0), torch.nan_to_num(want_y, nan=7.0))
+        dx = torch.full((nc, h, w), float("nan"), device="cuda")
+        ops._call("vunet_maxpool2_bwd_relu" if relu else "vunet_maxpool2_bwd", ops._p(xd), ops._p(y), ops._p(dyd), ops._p(dx),
+                  nc, h, w, ops._stream())
+        assert torch.equal(dx.cpu(), want_dx), relu
+
+
+def test_maxpool2_nan_window_follows_aten():
+    """The case of the issue: [[1, nan], [nan, 3]] pools to NaN and its gradient goes to position (1, 0); a ReLU is
+    NaN-preserving, so the masked form routes there too.  The fused L1-tap + pool kernels (vunet_l1_pool_fwd /
+    vunet_l1_pool_bwd) follow the same rule."""
+    ops = _ops()
+    x = torch.tensor([[[1.0, float("nan")], [float("nan"), 3.0]]])
+    xd = x.cuda()
+    y = torch.empty(1, 1, 1, device="cuda")
+    ops._call("vunet_maxpool2_fwd", ops._p(xd), ops._p(y), 1, 2, 2, ops._stream())
+    assert torch.isnan(y).all()
+    dy = torch.tensor([[[2.5]]], device="cuda")
+    want = torch.tensor([[[0.0, 0.0], [2.5, 0.0]]])
+    for name in ("vunet_maxpool2_bwd", "vunet_maxpool2_bwd_relu"):
+        dx = torch.empty(1, 2, 2, device="cuda")
+        ops._call(name, ops._p(xd), ops._p(y), ops._p(dy), ops._p(dx), 1, 2, 2, ops._stream())
+        assert torch.equal(dx.cpu(), want), name
+    _, ref_dx = _pool_ref(x, dy.cpu(), False)
+    assert torch.equal(ref_dx, want)
+    # fused tap + pool: pooled y and the routed part of db (gscale 0: no sign term)
+    t = torch.zeros(1, 1, 2, 2, device="cuda")
+    partial = torch.empty(1024, device="cuda")
+    out = torch.zeros(1, device="cuda")
+    y2 = torch.empty(1, 1, 1, 1, device="cuda")
+    ops._call("vunet_l1_pool_fwd", ops._p(t), ops._p(xd), ops._p(partial), ops._p(out), ops._p(y2), 1.0, 1, 2, 2, ops._stream())
+    assert torch.isnan(y2).all()
+    for relu in (0, 1):
+        db = torch.empty(1, 1, 2, 2, device="cuda")
+        ops._call("vunet_l1_pool_bwd", ops._p(t), ops._p(xd), ops._p(dy), ops._p(db), 0.0, None, 1, 2, 2, None, relu, ops._stream())
+        assert torch.equal(db.cpu().reshape(1, 2, 2), want), relu
+
+
+@pytest.mark.parametrize("shape", [(2, 6, 4), (3, 10, 14), (160, 128, 130)])
+def test_l1_pool_kernels_route_like_maxpool(shape):
+    """vunet_l1_pool_fwd's pooled output and vunet_l1_pool_bwd's routed gradient (no sign term) against ATen's max_pool2d
+    on windows with NaN and +-inf, with and without the ReLU mask."""
+    ops = _ops()
+    nc, h, w = shape
+    x = _pool_input(nc, h, w, 30 + h, "nonfinite")
+    dy = torch.randn(nc, h // 2, w // 2, generator=_gen(31))
+    xd, dyd = x.cuda(), dy.cuda()
+    t = torch.zeros_like(xd)
+    partial = torch.empty(1024, device="cuda")
+    out = torch.zeros(1, device="cuda")
+    y = torch.empty(nc, h // 2, w // 2, device="cuda")
+    ops._call("vunet_l1_pool_fwd", ops._p(t), ops._p(xd), ops._p(partial), ops._p(out), ops._p(y), 1.0, nc, h, w, ops._stream())
+    want_y, _ = _pool_ref(x, dy, False)
+    assert torch.equal(torch.nan_to_num(y.cpu(), nan=7.0), torch.nan_to_num(want_y, nan=7.0))
+    assert torch.equal(torch.isnan(y.cpu()), torch.isnan(want_y))
+    for relu in (0, 1):
+        _, want_dx = _pool_ref(x, dy, bool(relu))
+        db = torch.empty_like(xd)
+        ops._call("vunet_l1_pool_bwd", ops._p(t), ops._p(xd), ops._p(dyd), ops._p(db), 0.0, None, nc, h, w, None, relu, ops._stream())
+        assert torch.equal(db.cpu(), want_dx), relu
+
+
+@pytest.mark.parametrize("h,w", [(3, 4), (4, 5), (1, 2)])
+def test_maxpool2_refuses_odd_maps(h, w):
+    """Odd H or W is refused by the C ABI before any launch (RuntimeError from the wrapper), forward and both backwards."""
+    ops = _ops()
+    x = torch.zeros(2, 1, h, w, device="cuda")
+    big = torch.zeros(2 * h * w + 8, device="cuda")
+    with pytest.raises(RuntimeError):
+        ops.MaxPool2.apply(x)
+    for name in ("vunet_maxpool2_bwd", "vunet_maxpool2_bwd_relu"):
+        with pytest.raises(RuntimeError):
+            ops._call(name, ops._p(x), ops._p(big), ops._p(big), ops._p(big), 2, h, w, ops._stream())
+
+
+# ------------------------------------------------------------------------------------------------ bilinear 2x
+@pytest.mark.parametrize("shape", [(1, 1, 1, 1), (2, 3, 1, 5), (1, 2, 2, 1), (2, 2, 2, 2), (1, 3, 7, 2), (2, 2, 256, 256)])
+def test_upsample_bilinear2x_vs_interpolate(shape):
+    """vunet_upsample_bilinear2x_fwd against F.interpolate(scale 2, bilinear, align_corners=False) in float64 and
+    vunet_upsample_bilinear2x_bwd against its float64 autograd.  Forward: two levels of lerps (weights {0, 1/4, 3/4, 1},
+    exact), a product and a sum per level: <= 4 U * sum|w x|.  Backward: two levels of a product and four accumulations:
+    <= 10 U * sum|w dy|."""
+    ops = _ops()
+    x = torch.randn(*shape, generator=_gen(5))
+    x64 = x.double().requires_grad_(True)
+    y64 = F.interpolate(x64, scale_factor=2, mode="bilinear", align_corners=False)
+    xd = x.cuda().requires_grad_(True)
+    y = ops.UpsampleBilinear2x.apply(xd)
+    # sum |w x| = the same interpolation of |x| (all weights are >= 0)
+    absy = F.interpolate(x.double().abs(), scale_factor=2, mode="bilinear", align_corners=False)
+    assert_ulps(y, y64.detach(), 4 * U * absy + TINY, "bilinear fwd")
+    dy = torch.randn(*y.shape, generator=_gen(6))
+    y64.backward(dy.double())
+    y.backward(dy.cuda())
+    x_abs = x.double().requires_grad_(True)
+    F.interpolate(x_abs, scale_factor=2, mode="bilinear", align_corners=False).backward(dy.double().abs())
+    assert_ulps(xd.grad, x64.grad, 10 * U * x_abs.grad + TINY, "bilinear bwd")
+
+
+# ------------------------------------------------------------------------------------------------ activations
+ACTS = {"elu": 1, "relu": 2, "sigmoid": 3, "lrelu": 4}
+SLOPE = 0.2
+
+
+def _act_ref(name, x64):
+    if name == "elu":
+        return torch.where(x64 > 0, x64, torch.expm1(x64))
+    if name == "relu":
+        return torch.where(x64 <= 0, torch.zeros_like(x64), x64)
+    if name == "sigmoid":
+        return torch.sigmoid(x64)
+    return torch.where(x64 > 0, x64, x64 * SLOPE)
+
+
+def _act_aten(name, x):
+    return {"elu": F.elu, "relu": torch.relu, "sigmoid": torch.sigmoid,
+            "lrelu": lambda t: F.leaky_relu(t, SLOPE)}[name](x)
+
+
+def _act_bound(name, x64, ref):
+    ax = x64.abs().nan_to_num(posinf=0.0)
+    if name == "relu":
+        return torch.zeros_like(ref)                                  # a select: exact
+    if name == "lrelu":
+        return 2 * U * ref.abs()                                      # one product (U) and fp32's 0.2 (U / 4)
+    if name == "elu":
+        # __expf(x) - 1: relative error of __expf ~(|x| + 2) U on e^x, then the subtraction's rounding; c = 4
+        expx = torch.where(x64 > 0, torch.zeros_like(x64), torch.exp(x64)).nan_to_num(nan=0.0)
+        return 4 * U * (ref.abs() + (ax + 1) * expx) + TINY
+    # sigmoid 1 / (1 + __expf(-x)): (|x| + 2) U from __expf, the add and the division: c = 4
+    return 4 * U * (ax + 2) * ref.abs() + TINY
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("name", list(ACTS))
+def test_activation_forward(name, n):
+    """vunet_act_fwd (ops.Activation) for ELU, ReLU, sigmoid and leaky ReLU (slope 0.2) on +-0, +-1e-30, +-88, +-100,
+    +-inf, NaN and normals; NaN / inf as ATen's fp32 result (ReLU passes NaN through)."""
+    ops = _ops()
+    x = _mixed(n, 7 + n)
+    y = ops.Activation.apply(x.cuda(), ACTS[name], SLOPE)
+    x64 = x.double()
+    ref = _act_ref(name, x64)
+    assert_ulps(y, ref, _act_bound(name, x64, ref), f"{name} fwd", aten=_act_aten(name, x))
+
+
+def _act_bwd_aten(name, dy, y):
+    a = torch.ops.aten
+    if name == "elu":
+        return a.elu_backward(dy, 1.0, 1.0, 1.0, True, y)
+    if name == "relu":
+        return a.threshold_backward(dy, y, 0.0)
+    if name == "sigmoid":
+        return a.sigmoid_backward(dy, y)
+    return a.leaky_relu_backward(dy, y, SLOPE, True)
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("name", list(ACTS))
+def test_activation_backward_from_output(name, n):
+    """vunet_act_bwd_from_out: dx from the saved OUTPUT y as ATen forms it (threshold_backward selects -- 0 where y <= 0
+    whatever dy is, dy where y is NaN; elu_backward(is_result) dy unless y > 0, else dy * (y + 1); sigmoid_backward
+    dy (1 - y) y; leaky_relu_backward).  Bounds: sigmoid three roundings (c = 3), ELU (y + 1) and the product (c = 2), leaky
+    ReLU one product and fp32's 0.2 (c = 2), ReLU exact."""
+    ops = _ops()
+    g = _gen(8 + n)
+    x = _mixed(n, 9 + n)
+    y = _act_aten(name, x)                     # outputs in the activation's range, NaN / inf included
+    dy = torch.randn(n, generator=g)
+    if n >= 4:
+        dy[0], dy[1], dy[2] = float("nan"), float("inf"), -float("inf")   # at y = 0 / -0 / 1e-30
+    ops_dx = torch.empty(n, device="cuda")
+    yd, dyd = y.cuda(), dy.cuda()           # (held in names: a temporary's memory could be handed to the next one)
+    ops._call("vunet_act_bwd_from_out", ops._p(yd), ops._p(dyd), ops._p(ops_dx), ACTS[name], SLOPE, n, ops._stream())
+    y64, dy64 = y.double(), dy.double()
+    if name == "sigmoid":
+        ref, c = dy64 * (1 - y64) * y64, 3
+    elif name == "elu":
+        ref, c = torch.where(y64 > 0, dy64, dy64 * (y64 + 1)), 2
+    elif name == "relu":
+        ref, c = torch.where(y64 <= 0, torch.zeros_like(dy64), dy64), 0
+    else:
+        ref, c = torch.where(y64 > 0, dy64, dy64 * SLOPE), 2
+    # (ELU: ATen's vectorised CPU loop gives NaN where y is NaN, its scalar tail gives dy; the kernel follows the vectorised
+    #  form, which is the reference's formula -- the pattern is taken from it)
+    aten = None if name == "elu" else _act_bwd_aten(name, dy, y)
+    assert_ulps(ops_dx, ref, c * U * ref.abs() + TINY, f"{name} bwd", aten=aten)
+
+
+# ------------------------------------------------------------------------------------------------ other elementwise ops
+@pytest.mark.parametrize("n", SIZES + [64 * 2 ** 20 + 5])
+def test_axpby(n):
+    """vunet_axpby: y = a x (+ b y_in).  Two products and a sum (possibly one fma): <= 2 U * (|a x| + |b y_in|); without
+    y_in one product, <= 1 U * |a x|.  (n = 64 Mi + 5: the largest case of this file.)"""
+    ops = _ops()
+    g = _gen(12)
+    x, yin = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    a, b = 0.75, -1.3125                      # exact in fp32 (they cross the ABI as float)
+    xd, yd = x.cuda(), yin.cuda()
+    out = torch.empty(n, device="cuda")
+    ops._call("vunet_axpby", ops._p(xd), ops._p(yd), ops._p(out), a, b, n, ops._stream())
+    ref = a * x.double() + b * yin.double()
+    assert_ulps(out, ref, 2 * U * (abs(a) * x.double().abs() + abs(b) * yin.double().abs()), "axpby")
+    ops._call("vunet_axpby", ops._p(xd), None, ops._p(out), a, b, n, ops._stream())
+    ref = a * x.double()
+    assert_ulps(out, ref, 1 * U * ref.abs(), "axpby no y_in")
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_reparam_forward_and_backward(n):
+    """vunet_reparam_fwd (ops.Reparam): z = eps e^ls + mu; __expf's (|ls| + 2) U, the product and the sum: <= 4 U *
+    ((|ls| + 2) |eps| e^ls + |mu|).  vunet_reparam_bwd: dmu = dz exactly, dls = dz eps e^ls, <= 4 U (|ls| + 2) |dls|."""
+    ops = _ops()
+    g = _gen(13)
+    mu, ls, eps, dz = (torch.randn(n, generator=g) * s for s in (2.0, 1.5, 1.0, 1.0))
+    mud, lsd = mu.cuda().requires_grad_(True), ls.cuda().requires_grad_(True)
+    z = ops.Reparam.apply(mud, lsd, eps.cuda())
+    e = torch.exp(ls.double())
+    ref = eps.double() * e + mu.double()
+    assert_ulps(z, ref, 4 * U * ((ls.double().abs() + 2) * eps.double().abs() * e + mu.double().abs()) + TINY, "reparam")
+    z.backward(dz.cuda())
+    assert torch.equal(mud.grad.cpu(), dz)
+    dls = dz.double() * eps.double() * e
+    assert_ulps(lsd.grad, dls, 4 * U * (ls.double().abs() + 2) * dls.abs() + TINY, "reparam dls")
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 1000, WRAP + 77])
+def test_vgg_preprocess_forward_and_backward(n):
+    """vunet_vgg_preprocess: ((x + 1) / 2 - mean_c) / std_c with ImageNet's constants (rounded to fp32 in the kernel);
+    x + 1, - mean, / std and the constants each round once: <= 4 U * (|x + 1| / 2 + mean) / std.
+    vunet_vgg_preprocess_bwd: dx = [add] + dy (0.5 / std): fp32's std, the division, the product and the sum round once
+    each, <= 4 U * (|add| + |dy| 0.5 / std)."""
+    ops = _ops()
+    hw = n
+    N = 2
+    g = _gen(14)
+    x = torch.rand(N, 3, 1, hw, generator=g) * 2 - 1
+    x[0, 0, 0, 0] = -1.0
+    mean = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float64).view(1, 3, 1, 1)
+    std = torch.tensor([0.229, 0.224, 0.225], dtype=torch.float64).view(1, 3, 1, 1)
+    y = torch.empty(N, 3, 1, hw, device="cuda")
+    xd = x.cuda()
+    ops._call("vunet_vgg_preprocess", ops._p(xd), ops._p(y), N, 1, hw, ops._stream())
+    x64 = x.double()
+    ref = ((x64 + 1) / 2 - mean) / std
+    assert_ulps(y, ref, 4 * U * ((x64 + 1).abs() / 2 + mean) / std, "vgg pre")
+    dy, add = torch.randn(N, 3, 1, hw, generator=g), torch.randn(N, 3, 1, hw, generator=g)
+    dyd, addd = dy.cuda(), add.cuda()
+    for with_add in (False, True):
+        dx = torch.empty(N, 3, 1, hw, device="cuda")
+        ops._call("vunet_vgg_preprocess_bwd", ops._p(dyd), ops._p(addd if with_add else None), ops._p(dx), N, 1,
+                  hw, ops._stream())
+        a64 = add.double() if with_add else torch.zeros_like(dy.double())
+        ref = a64 + dy.double() * (0.5 / std)
+        assert_ulps(dx, ref, 4 * U * (a64.abs() + dy.double().abs() * (0.5 / std)) + TINY, f"vgg pre bwd add={with_add}")
+
+
+@pytest.mark.parametrize("n", [1, 300, WRAP + 5])
+@pytest.mark.parametrize("with_gout", [False, True])
+def test_kl_and_sqdiff_backward(n, with_gout):
+    """vunet_kl_bwd: dmu = gs mu, dls = gs (e^{2 ls} - 1) with gs = gscale [* gout[0]] and e = __expf(ls): gs rounds once,
+    e * e carries 2 (|ls| + 2) U, the subtraction and the product once more: <= 4 U |gs| ((|ls| + 2) e^{2 ls} + |e^{2 ls} - 1|);
+    dmu <= 2 U |dmu|.  vunet_sqdiff_bwd: dp = gs (p - q), dq = -dp: <= 2 U |dp| (also with dp = NULL)."""
+    ops = _ops()
+    g = _gen(15)
+    mu, ls, p, q = (torch.randn(n, generator=g) for _ in range(4))
+    gscale, gout = 0.3125, torch.tensor([-1.75])
+    gs = gscale * (float(gout) if with_gout else 1.0)
+    goutd = gout.cuda() if with_gout else None
+    dmu, dls = torch.empty(n, device="cuda"), torch.empty(n, device="cuda")
+    mud, lsd, pd, qd = mu.cuda(), ls.cuda(), p.cuda(), q.cuda()
+    ops._call("vunet_kl_bwd", ops._p(mud), ops._p(lsd), ops._p(dmu), ops._p(dls), gscale, ops._p(goutd), n,
+              ops._stream())
+    e2 = torch.exp(2 * ls.double())
+    assert_ulps(dmu, gs * mu.double(), 2 * U * abs(gs) * mu.double().abs() + TINY, "kl dmu")
+    assert_ulps(dls, gs * (e2 - 1), 4 * U * abs(gs) * ((ls.double().abs() + 2) * e2 + (e2 - 1).abs()) + TINY, "kl dls")
+    dp, dq = torch.empty(n, device="cuda"), torch.empty(n, device="cuda")
+    ops._call("vunet_sqdiff_bwd", ops._p(pd), ops._p(qd), ops._p(dp), ops._p(dq), gscale, ops._p(goutd), n,
+              ops._stream())
+    ref = gs * (p.double() - q.double())
+    assert_ulps(dp, ref, 2 * U * ref.abs() + TINY, "sqdiff dp")
+    assert torch.equal(dq.cpu(), -dp.cpu())
+    dq2 = torch.full((n,), 5.0, device="cuda")
+    ops._call("vunet_sqdiff_bwd", ops._p(pd), ops._p(qd), None, ops._p(dq2), gscale, ops._p(goutd), n, ops._stream())
+    assert torch.equal(dq2.cpu(), dq.cpu())
+
+
+# ------------------------------------------------------------------------------------------------ reductions
+def _pair_depth(n):
+    """Summation depth of pair_sum: serial terms per thread (<= 256 workgroups of 256 threads, grid-stride), 6 shuffle
+    levels and the LDS hop per stage, the finishing stage's serial terms, the scale and the offset."""
+    nb = min(256, max(1, (n + 2047) // 2048))
+    return math.ceil(n / (nb * 256)) + 8 + math.ceil(nb / 256) + 8 + 2
+
+
+@pytest.mark.parametrize("N,D", [(1, 1), (1, 1000), (4, 4096), (3, 200001)])
+@pytest.mark.parametrize("at_prior", [False, True])
+def test_kl_forward(N, D, at_prior):
+    """vunet_kl_fwd (ops.KLPrior): out[0] += w ((1/N) sum (-ls + (e^{2 ls} + mu^2) / 2) - D / 2).  Bound: c U (|w| / N)
+    sum(|ls| + e^{2 ls} (|ls| + 3) + mu^2) + 2 U |w| D / 2, c = the summation depth (_pair_depth).  At the prior (mu = 0,
+    ls = 0) the true value is 0 and the bound is the cancellation's.  The output scalar is accumulated, not overwritten."""
+    ops = _ops()
+    g = _gen(16)
+    if at_prior:
+        mu, ls = torch.zeros(N, D), torch.zeros(N, D)
+    else:
+        mu, ls = torch.randn(N, D, generator=g), 0.5 * torch.randn(N, D, generator=g)
+    w = 0.375
+    out = torch.tensor([1.25], device="cuda")
+    partial = torch.empty(256, device="cuda")
+    mud, lsd = mu.cuda(), ls.cuda()
+    ops._call("vunet_kl_fwd", ops._p(mud), ops._p(lsd), ops._p(partial), ops._p(out), w, N, D, ops._stream())
+    m64, l64 = mu.double(), ls.double()
+    e2 = torch.exp(2 * l64)
+    kl = w * ((-l64 + 0.5 * (e2 + m64 ** 2)).sum() / N - 0.5 * D)
+    c = _pair_depth(N * D)
+    bound = c * U * (w / N) * float((l64.abs() + e2 * (l64.abs() + 3) + m64 ** 2).sum()) + 2 * U * w * 0.5 * D + U * 1.25
+    assert abs(float(out) - (1.25 + float(kl))) <= bound, (float(out), 1.25 + float(kl), bound)
+    # through the wrapper (a fresh zero scalar)
+    got = ops.KLPrior.apply(mud, lsd, w)
+    assert abs(float(got) - float(kl)) <= bound
+
+
+@pytest.mark.parametrize("N,D", [(1, 1), (1, 1000), (5, 777), (2, 300000)])
+def test_sqdiff_forward(N, D):
+    """vunet_sqdiff_fwd (ops.SqDiff): out[0] += (w / N) sum (p - q)^2 / 2.  All terms >= 0: c U |result| with c =
+    _pair_depth + 3 (the difference, the square and the half each round once).  Accumulates into out[0]."""
+    ops = _ops()
+    g = _gen(17)
+    p, q = torch.randn(N, D, generator=g), torch.randn(N, D, generator=g)
+    w = 1.5
+    out = torch.tensor([-0.5], device="cuda")
+    partial = torch.empty(256, device="cuda")
+    pd, qd = p.cuda(), q.cuda()
+    ops._call("vunet_sqdiff_fwd", ops._p(pd), ops._p(qd), ops._p(partial), ops._p(out), w, N, D, ops._stream())
+    ref = w / N * float((0.5 * (p.double() - q.double()) ** 2).sum())
+    c = _pair_depth(N * D) + 3
+    assert abs(float(out) - (-0.5 + ref)) <= c * U * ref + U * 0.5 + TINY, (float(out), ref)
+    got = ops.SqDiff.apply(pd, qd, w)
+    assert abs(float(got) - ref) <= c * U * ref + TINY
+
+
+def _instnorm_case(kind, nc, hw, seed):
+    g = _gen(seed)
+    if kind == "constant":
+        return torch.full((nc, hw), 0.37) + torch.arange(nc).view(nc, 1) * 0.5
+    if kind == "offset":
+        return 1e4 + torch.randn(nc, hw, generator=g)
+    return torch.randn(nc, hw, generator=g) * 2 + 0.3
+
+
+@pytest.mark.parametrize("hw", [1, 7, 200, 256, 1000, 65536])
+@pytest.mark.parametrize("kind", ["randn", "constant", "offset"])
+def test_instance_norm_forward_and_backward(hw, kind):
+    """vunet_instnorm_fwd / vunet_instnorm_bwd (ops.InstanceNorm, affine False) against float64 instance norm and its
+    autograd.  One workgroup per plane; each sum has depth cm = ceil(HW / 256) + 9 (serial terms, 6 shuffle levels, the LDS
+    hop, the division).  Propagated bounds:
+      mean   em = cm U sum|x| / HW
+      var    ev = (cm + 3) U var + em^2          (two passes: the mean's error enters squared)
+      rstd   er = ev / (2 (var + eps)) + 2 U      (relative; rsqrtf ~1 ulp)
+      y      rstd (em + U |x - mean|) + |y| (er + U)
+      dx     rstd (e1 + |y| e2 + |m2| ey + 3 U (|dy| + |m1| + |y m2|)) + |dx| er, e1 / e2 the two sums' bounds.
+    Planes: HW = 1 (y = dx = 0), HW < 256, HW = 65536; a constant plane (var 0: rstd = 1 / sqrt(eps)); mean 1e4, std 1."""
+    ops = _ops()
+    nc = 3
+    eps = 1e-5
+    x = _instnorm_case(kind, nc, hw, 20 + hw)
+    dy = torch.randn(nc, hw, generator=_gen(21))
+    xd = x.cuda().view(1, nc, 1, hw).requires_grad_(True)
+    y = ops.InstanceNorm.apply(xd, eps)
+    y.backward(dy.cuda().view(1, nc, 1, hw))
+    stats = torch.empty(nc, 2, device="cuda")
+    y2 = torch.empty(nc, hw, device="cuda")
+    x2 = x.cuda()
+    ops._call("vunet_instnorm_fwd", ops._p(x2), ops._p(y2), ops._p(stats), nc, hw, eps, ops._stream())
+    assert torch.equal(y2.cpu(), y.detach().cpu().view(nc, hw))
+    x64, dy64 = x.double(), dy.double()
+    mu = x64.mean(1, keepdim=True)
+    var = ((x64 - mu) ** 2).mean(1, keepdim=True)
+    rstd = 1 / torch.sqrt(var + eps)
+    yref = (x64 - mu) * rstd
+    if hw > 1:   # the explicit formula is F.instance_norm's (which refuses HW = 1)
+        assert torch.allclose(yref, F.instance_norm(x64.view(1, nc, 1, hw), eps=eps).view(nc, hw), rtol=1e-12, atol=1e-12)
+    cm = math.ceil(hw / 256) + 9
+    em = cm * U * x64.abs().sum(1, keepdim=True) / hw
+    ev = (cm + 3) * U * var + em ** 2
+    er = ev / (2 * (var + eps)) + 2 * U
+    assert_ulps(stats[:, 0], mu.view(-1), em.view(-1), f"mean {kind}")
+    assert_ulps(stats[:, 1], rstd.view(-1), (er * rstd).view(-1), f"rstd {kind}")
+    ey = rstd * (em + U * (x64 - mu).abs()) + yref.abs() * (er + U)
+    assert_ulps(y, yref, ey + TINY, f"y {kind}")
+    # backward: dx = rstd (dy - mean(dy) - y mean(dy y))
+    m1 = dy64.mean(1, keepdim=True)
+    m2 = (dy64 * yref).mean(1, keepdim=True)
+    dxref = rstd * (dy64 - m1 - yref * m2)
+    if hw > 1:
+        xa = x64.view(1, nc, 1, hw).clone().requires_grad_(True)
+        F.instance_norm(xa, eps=eps).backward(dy64.view(1, nc, 1, hw))
+        assert torch.allclose(dxref, xa.grad.view(nc, hw), rtol=1e-9, atol=1e-9 * float(rstd.max()))
+    e1 = cm * U * dy64.abs().sum(1, keepdim=True) / hw
+    e2 = cm * U * (dy64 * yref).abs().sum(1, keepdim=True) / hw + (dy64.abs() * ey).sum(1, keepdim=True) / hw
+    edx = (rstd * (e1 + yref.abs() * e2 + m2.abs() * ey + 3 * U * (dy64.abs() + m1.abs() + (yref * m2).abs()))
+           + dxref.abs() * er)
+    assert_ulps(xd.grad.view(nc, hw), dxref, edx + TINY, f"dx {kind}")
+
+
+# ------------------------------------------------------------------------------------------------ Adam
+def _adam_ref(p, g, m, v, lr, b1, b2, eps, wd, step, gs):
+    """torch.optim.Adam's update (torch/optim/adam.py, single-tensor form) in float64 from fp32 state -> (p, m, v, aux).
+    beta1 / beta2 / eps / weight_decay / grad_scale cross the C ABI as float: the reference uses those fp32 values (exact in
+    float64); lr is used exactly -- its rounding to fp32 is part of the kernel's error."""
+    f = lambda s: float(torch.tensor(s, dtype=torch.float32))
+    b1, b2, eps, wd, gs = f(b1), f(b2), f(eps), f(wd), f(gs)
+    p, g, m0, v0 = (t.detach().cpu().double() for t in (p, g, m, v))
+    gt = g * gs + wd * p
+    m = b1 * m0 + (1 - b1) * gt
+    v = b2 * v0 + (1 - b2) * gt * gt
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    step_size = lr / bc1
+    denom = v.sqrt() / math.sqrt(bc2) + eps
+    upd = step_size * m / denom
+    aux = dict(ga=(g * gs).abs() + wd * p.abs(), m0=m0, v0=v0, b1=b1, b2=b2, bc2=bc2, denom=denom, upd=upd,
+               step_size=step_size)
+    return p - upd, m, v, aux
+
+
+def _adam_check(got, ref, tag):
+    """Bounds from the kernel's arithmetic, ga = |gs g| + wd |p| (the terms of the effective gradient g'):
+      m = b1 m0 + (1 - b1) g'           4 U (b1 |m0| + (1 - b1) ga)
+      v = b2 v0 + (1 - b2) g'^2         6 U (b2 v0 + (1 - b2) ga^2)
+      denom = sqrt(v) / sqrt(bc2) + eps relative 4 U plus v's error through the square root (min(ev / 2 sqrt v, sqrt ev))
+      p - step_size m / denom           U |p| + |upd| (8 U + rel(denom)) + step_size em / denom
+    (8 U: lr's rounding to fp32, step_size, the division, the product and the subtraction's half ulp, with room.)"""
+    pn, mn, vn = got
+    p_r, m_r, v_r, a = ref
+    em = 4 * U * (a["b1"] * a["m0"].abs() + (1 - a["b1"]) * a["ga"]) + TINY
+    ev = 6 * U * (a["b2"] * a["v0"] + (1 - a["b2"]) * a["ga"] ** 2) + TINY
+    assert_ulps(mn, m_r, em, f"{tag} m")
+    assert_ulps(vn, v_r, ev, f"{tag} v")
+    sv = v_r.sqrt()
+    dsv = torch.minimum(ev / (2 * sv.clamp_min(TINY)), ev.sqrt())
+    rel_den = dsv / math.sqrt(a["bc2"]) / a["denom"] + 4 * U
+    ep = U * p_r.abs() + a["upd"].abs() * (8 * U + rel_den) + a["step_size"] * em / a["denom"] + TINY
+    assert_ulps(pn, p_r, ep, f"{tag} p")
+
+
+def _adam_state(n, seed, zero_grad=False):
+    g = _gen(seed)
+    p = torch.randn(n, generator=g)
+    grad = torch.zeros(n) if zero_grad else torch.randn(n, generator=g) * 1e-2
+    m = torch.randn(n, generator=g) * 1e-3
+    v = torch.rand(n, generator=g) * 1e-4
+    if zero_grad:
+        v[: n // 2] = 0.0                      # v = 0: eps is the whole denominator
+    return p, grad, m, v
+
+
+def _run_adam(ops, dev, state, lr, b1, b2, eps, wd, step, gs):
+    p, g, m, v = (t.cuda() for t in state)
+    if dev:
+        ops.adam_step_flat_dev(p, g, m, v, torch.tensor([lr], dtype=torch.float64, device="cuda"), b1, b2, eps, wd,
+                               torch.tensor([step], dtype=torch.int64, device="cuda"), gs)
+    else:
+        ops.adam_step_flat(p, g, m, v, lr, b1, b2, eps, wd, step, gs)
+    return p, m, v
+
+
+@pytest.mark.parametrize("step", [1, 10, 10 ** 4, 10 ** 6])
+@pytest.mark.parametrize("hp", [(0.9, 0.999, 1e-8, 0.0, 1.0), (0.5, 0.9, 1e-8, 1e-4, 1.0), (0.9, 0.999, 1e-6, 0.0, 0.125)])
+@pytest.mark.parametrize("zero_grad", [False, True])
+def test_adam_single_step(step, hp, zero_grad):
+    """vunet_adam_step (ops.adam_step_flat) and vunet_adam_step_dev (ops.adam_step_flat_dev) at steps 1, 10, 1e4, 1e6 set
+    directly, against the float64 restatement (_adam_ref); lr = 1e-3 / 3 is not representable in fp32.  The two entry points
+    form their bias corrections the same way (double, lr rounded to float) and agree bit for bit."""
+    ops = _ops()
+    b1, b2, eps, wd, gs = hp
+    lr = 1e-3 / 3
+    n = 1000 + 4099
+    state = _adam_state(n, 30 + step % 97, zero_grad)
+    host = _run_adam(ops, False, state, lr, b1, b2, eps, wd, step, gs)
+    devr = _run_adam(ops, True, state, lr, b1, b2, eps, wd, step, gs)
+    for a, b in zip(host, devr):
+        assert torch.equal(a.cpu(), b.cpu())
+    ref = _adam_ref(*state, lr, b1, b2, eps, wd, step, gs)
+    _adam_check(host, ref, f"step {step}")
+
+
+@pytest.mark.parametrize("hp", [(0.9, 0.999, 0.0), (0.5, 0.9, 1e-4)])
+def test_adam_2000_steps(hp):
+    """2 000 steps of both entry points side by side (betas (0.9, 0.999), and the flow stage's (0.5, 0.9) with weight
+    decay), fresh gradients every step: the two agree bit for bit throughout, and every step's update is held to the float64
+    restatement taken from the state the step started from (the single-step bounds of _adam_check)."""
+    ops = _ops()
+    b1, b2, wd = hp
+    lr, eps = 2e-3 / 7, 1e-8
+    n = 3001
+    p, _, m, v = (t.cuda() for t in _adam_state(n, 40))
+    p2, m2, v2 = p.clone(), m.clone(), v.clone()
+    gen = torch.Generator(device="cuda").manual_seed(41)
+    lr_dev = torch.tensor([lr], dtype=torch.float64, device="cuda")
+    step_dev = torch.zeros(1, dtype=torch.int64, device="cuda")
+    check = set(range(1, 21)) | set(range(20, 2001, 37)) | {2000}
+    for t in range(1, 2001):
+        grad = torch.randn(n, device="cuda", generator=gen) * (1e-2 if t % 5 else 0.0)
+        before = (p.cpu(), m.cpu(), v.cpu()) if t in check else None
+        ops.adam_step_flat(p, grad, m, v, lr, b1, b2, eps, wd, t)
+        step_dev.fill_(t)
+        ops.adam_step_flat_dev(p2, grad, m2, v2, lr_dev, b1, b2, eps, wd, step_dev)
+        if before is not None:
+            ref = _adam_ref(before[0], grad, before[1], before[2], lr, b1, b2, eps, wd, t, 1.0)
+            _adam_check((p, m, v), ref, f"step {t}")
+    for a, b in ((p, p2), (m, m2), (v, v2)):
+        assert torch.equal(a, b)
+
+
+# ------------------------------------------------------------------------------------------------ weight-norm batched launches
+# (Cout, C1, C2, k, kind): fan-in 27 .. 4608, Cout 3 / 16 / 35 / 128; kind 0 NormConv2d, 1 plain, 2 L2NormConv2d
+WN_LAYERS = [(3, 3, 0, 3, 0), (16, 16, 16, 3, 0), (35, 20, 0, 1, 1), (128, 512, 0, 3, 0), (35, 17, 6, 3, 2),
+             (16, 32, 0, 3, 1), (128, 16, 0, 1, 0), (16, 64, 64, 3, 2)]
+WN_MAX = 64        # the largest item table ops issues (ops._WN_GROUP)
+
+
+def _r2(x):
+    return (x + 1) // 2 * 2
+
+
+def _r32(x):
+    return (x + 31) // 32 * 32
+
+
+def _wn_params(spec, seed):
+    cout, c1, c2, k, kind = spec
+    g = _gen(seed)
+    v = torch.randn(cout, c1 + c2, k, k, generator=g).cuda()
+    gg = (torch.rand(cout, generator=g) + 0.5).cuda() if kind == 0 else None
+    bias = torch.randn(cout, generator=g).cuda() if kind != 2 else None
+    gamma = (torch.rand(cout, generator=g) + 0.5).cuda() if kind != 1 else None
+    beta = torch.randn(cout, generator=g).cuda() if kind != 1 else None
+    return v, gg, bias, gamma, beta
+
+
+def _wn_outputs(spec, split, dev="cuda"):
+    ops = _ops()
+    cout, c1, c2, k, kind = spec
+    t, ctot = k * k, c1 + c2
+    o = {"wt_f": torch.zeros(t * (_r2(c1) + _r2(c2)), _r32(cout), device=dev),
+         "wt_d": torch.zeros(t * _r2(cout), _r32(ctot), device=dev),
+         "small": torch.zeros(4, cout, device=dev)}
+    for name, dg in (("wx_f", False), ("wx_d", True)):
+        units = ops.x6_image_units(cout, c1, c2, k, dg, split) if k == 3 else 0
+        o[name] = torch.zeros(units * 4, dtype=torch.int32, device=dev) if units else None
+    return o
+
+
+def _wn_item(ops, spec, split, prm, o):
+    it = ops.WnItem()
+    p = lambda x: None if x is None else x.data_ptr()
+    it.v, it.g, it.bias, it.gamma, it.beta = (p(x) for x in prm)
+    it.wt_f, it.wt_d, it.wx_f, it.wx_d = p(o["wt_f"]), p(o["wt_d"]), p(o["wx_f"]), p(o["wx_d"])
+    it.scale, it.shift, it.invnorm, it.wmax = (o["small"][i].data_ptr() for i in range(4))
+    cout, c1, c2, k, kind = spec
+    it.d = ops.WnDesc(cout, c1, c2, k, k, kind, split)
+    return it
+
+
+def _table(ops, items):
+    arr = (type(items[0]) * len(items))(*items)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
+
+
+def _wn_rows(w, c1, c2, mpad):
+    """[M, C1+C2, k, k] -> rows (source, tap, channel) x columns m (pitch Mpad): wt_f of vunet_weightnorm_fwd."""
+    m, _, k, _ = w.shape
+    t = k * k
+    c1p, c2p = _r2(c1), _r2(c2)
+    out = torch.zeros(t * (c1p + c2p), mpad, dtype=w.dtype)
+    wf = w.reshape(m, c1 + c2, t)
+    for tap in range(t):
+        out[tap * c1p:tap * c1p + c1, :m] = wf[:, :c1, tap].T
+        if c2:
+            out[t * c1p + tap * c2p:t * c1p + tap * c2p + c2, :m] = wf[:, c1:, tap].T
+    return out
+
+
+def _wn_drows(w, mpad):
+    """rows (tap, co) x columns ci (pitch Mpad): wt_d."""
+    m, ctot, k, _ = w.shape
+    t = k * k
+    out = torch.zeros(t * _r2(m), mpad, dtype=w.dtype)
+    wf = w.reshape(m, ctot, t)
+    for tap in range(t):
+        out[tap * _r2(m):tap * _r2(m) + m, :ctot] = wf[:, :, tap]
+    return out
+
+
+def _wn_fwd_ref(spec, prm):
+    cout, c1, c2, k, kind = spec
+    v, gg, bias, gamma, beta = (None if x is None else x.detach().cpu().double() for x in prm)
+    nrm = v.flatten(1).norm(dim=1)
+    if kind == 2:
+        nrm = nrm.clamp_min(1e-12)
+    gm = gamma if gamma is not None else torch.ones(cout, dtype=torch.float64)
+    if kind == 1:
+        scale = torch.ones(cout, dtype=torch.float64)
+    else:
+        scale = gm * (gg if kind == 0 else 1.0) / nrm
+    shift = (gm if kind != 1 else 1.0) * (bias if bias is not None else 0.0) + (beta if (beta is not None and kind != 1) else 0.0)
+    return scale, torch.as_tensor(shift, dtype=torch.float64).expand(cout), 1 / nrm
+
+
+@pytest.mark.parametrize("count", [1, WN_MAX])
+@pytest.mark.parametrize("split", [0, 2])
+def test_weightnorm_fwd_multi_matches_per_layer_and_float64(count, split):
+    """vunet_weightnorm_fwd_multi (the table ops.prepacked builds) == vunet_weightnorm_fwd per layer with the same split,
+    every output bit for bit (K-major matrices, split images, scale / shift / invnorm / row maxima), for a table of 1 layer
+    and of WN_MAX layers of mixed geometry.  Both against float64 g v / ||v||: ||v||^2 sums K / 64 terms per lane and 6
+    shuffle levels, sqrt / reciprocal / the products round once each: |scale| relative <= (K / 128 + 8) U, w_eff one more U."""
+    ops = _ops()
+    specs = [WN_LAYERS[i % len(WN_LAYERS)] for i in range(count)] if count > 1 else [WN_LAYERS[3]]
+    prms = [_wn_params(s, 50 + i) for i, s in enumerate(specs)]
+    single, multi, items = [], [], []
+    for s, prm in zip(specs, prms):
+        o = _wn_outputs(s, split)
+        d = ops.WnDesc(s[0], s[1], s[2], s[3], s[3], s[4], split)
+        sm = o["small"]
+        ops._call("vunet_weightnorm_fwd", ctypes.byref(d), *[ops._p(x) for x in prm], ops._p(o["wt_f"]), ops._p(o["wt_d"]),
+                  ops._p(o["wx_f"]), ops._p(o["wx_d"]), ops._p(sm[0]), ops._p(sm[1]), ops._p(sm[2]), ops._p(sm[3]), ops._stream())
+        single.append(o)
+        o2 = _wn_outputs(s, split)
+        multi.append(o2)
+        items.append(_wn_item(ops, s, split, prm, o2))
+    table = _table(ops, items)
+    ops._call("vunet_weightnorm_fwd_multi", ops._p(table), len(items), max(s[0] for s in specs), ops._stream())
+    for i, (a, b) in enumerate(zip(single, multi)):
+        for key in a:
+            if a[key] is not None:
+                assert torch.equal(a[key], b[key]), (i, specs[i], key)
+    for s, prm, o in zip(specs, prms, single):
+        cout, c1, c2, k, kind = s
+        K = (c1 + c2) * k * k
+        scale, shift, invn = _wn_fwd_ref(s, prm)
+        rel = (K / 128 + 8) * U
+        assert_ulps(o["small"][0], scale, rel * scale.abs(), f"scale {s}")
+        assert_ulps(o["small"][1], shift, 2 * U * (shift.abs() + 1) + TINY, f"shift {s}")
+        if kind != 1:
+            assert_ulps(o["small"][2], invn, rel * invn, f"invnorm {s}")
+        w = scale.view(-1, 1, 1, 1) * prm[0].detach().cpu().double()
+        ref_f = _wn_rows(w, c1, c2, _r32(cout))
+        bound_f = _wn_rows((rel + U) * w.abs(), c1, c2, _r32(cout))
+        assert_ulps(o["wt_f"], ref_f, bound_f + TINY, f"wt_f {s}")
+        assert_ulps(o["wt_d"], _wn_drows(w, _r32(c1 + c2)), _wn_drows((rel + U) * w.abs(), _r32(c1 + c2)) + TINY, f"wt_d {s}")
+
+
+def _wn_bwd_ref(spec, prm, slabs, dshift, ns):
+    """float64 autograd of w_eff = gamma g v / ||v|| and shift = gamma bias + beta (kind rules as the kernel) with the
+    reduced slab gradient.  Slabs: [ns][Coutp32][K] in (tap, ci) order; dshift: [ns][Coutp32]."""
+    cout, c1, c2, k, kind = spec
+    ctot, t = c1 + c2, k * k
+    coutp = _r32(cout)
+    K = ctot * t
+    S = slabs.detach().cpu().double().view(ns, coutp, K)[:, :cout]
+    dW = S.sum(0).view(cout, t, ctot).permute(0, 2, 1).reshape(cout, ctot, k, k)
+    dW_abs = S.abs().sum(0).view(cout, t, ctot).permute(0, 2, 1).reshape(cout, ctot, k, k)
+    dsh = dshift.detach().cpu().double().view(ns, coutp)[:, :cout]
+    leaves = [None if x is None else x.detach().cpu().double().requires_grad_(True) for x in prm]
+    v, gg, bias, gamma, beta = leaves
+    nrm = v.flatten(1).norm(dim=1)
+    if kind == 2:
+        nrm = nrm.clamp_min(1e-12)
+    if kind == 1:
+        w = v
+        shift = bias
+    else:
+        sc = gamma * (gg if kind == 0 else 1.0) / nrm
+        w = sc.view(-1, 1, 1, 1) * v
+        shift = gamma * (bias if bias is not None else 0.0) + beta
+    loss = (w * dW).sum() + (shift * dsh.sum(0)).sum()
+    loss.backward()
+    return [None if x is None else x.grad for x in leaves], dW, dW_abs, dsh
+
+
+@pytest.mark.parametrize("count", [1, WN_MAX])
+def test_weightnorm_bwd_multi_matches_per_layer_and_float64(count):
+    """vunet_weightnorm_bwd_multi == vunet_weightnorm_bwd per layer, every gradient bit for bit (fresh and accumulating
+    outputs), for tables of 1 and WN_MAX layers; and both against float64 autograd of g v / ||v|| and the affine.
+    Bounds: the slab sum has depth ns / 4 + 3 (c_s = ns + 3 on sum|slab|); D = <dW, v> depth K / 256 + 9 on sum|dW v| plus
+    the slab sums' error through v; every parameter gradient then carries (K / 128 + 16) U relative for ||v|| and its
+    products."""
+    ops = _ops()
+    specs = [WN_LAYERS[i % len(WN_LAYERS)] for i in range(count)] if count > 1 else [WN_LAYERS[4]]
+    ns = 5
+    rows = []
+    for i, s in enumerate(specs):
+        cout, c1, c2, k, kind = s
+        K = (c1 + c2) * k * k
+        prm = _wn_params(s, 70 + i)
+        g = _gen(90 + i)
+        slabs = torch.randn(ns * _r32(cout) * K, generator=g).cuda()
+        dshift = torch.randn(ns * _r32(cout), generator=g).cuda()
+        invn = 1.0 / prm[0].flatten(1).norm(dim=1)
+        outs = lambda: [torch.zeros_like(prm[0])] + [torch.zeros(cout, device="cuda") for _ in range(4)]
+        rows.append((s, prm, slabs, dshift, invn, outs(), outs(), torch.empty(cout * (K + 1), device="cuda"),
+                     torch.empty(cout * (K + 1), device="cuda")))
+    for accumulate in (0, 1):
+        items = []
+        for s, prm, slabs, dshift, invn, o1, o2, w1, w2 in rows:
+            v, gg, bias, gamma, beta = prm
+            d = ops.WnDesc(s[0], s[1], s[2], s[3], s[3], s[4], 0)
+            ops._call("vunet_weightnorm_bwd", ctypes.byref(d), ops._p(slabs), ops._p(dshift), ns, ops._p(v), ops._p(gg),
+                      ops._p(bias), ops._p(gamma), ops._p(invn), *[ops._p(x) for x in o1], ops._p(w1), accumulate, ops._stream())
+            it = ops.WnBwdItem()
+            p = lambda x: None if x is None else x.data_ptr()
+            it.slabs, it.dshift, it.v, it.g, it.bias, it.gamma, it.invnorm = (p(x) for x in (slabs, dshift, v, gg, bias, gamma, invn))
+            it.dv, it.dg, it.dbias, it.dgamma, it.dbeta = (p(x) for x in o2)
+            it.workspace = p(w2)
+            it.d = d
+            it.nsplit, it.accumulate = ns, accumulate
+            items.append(it)
+        table = _table(ops, items)
+        max_blocks = max(s[0] * ((s[3] * s[3] * (s[1] + s[2]) + 63) // 64) for s in specs)
+        ops._call("vunet_weightnorm_bwd_multi", ops._p(table), len(items), max(s[0] for s in specs), max_blocks, ops._stream())
+        for i, r in enumerate(rows):
+            for a, b in zip(r[5], r[6]):
+                assert torch.equal(a, b), (i, specs[i], accumulate)
+    # after the accumulating pass the outputs hold twice the gradient (fresh + accumulated: one more rounding, exact x2)
+    for s, prm, slabs, dshift, invn, o1, o2, w1, w2 in rows:
+        cout, c1, c2, k, kind = s
+        K = (c1 + c2) * k * k
+        grads, dW, dW_abs, dsh = _wn_bwd_ref(s, prm, slabs, dshift, ns)
+        v64 = prm[0].detach().cpu().double()
+        e_dw = (ns + 3) * U * dW_abs
+        D_abs = (dW.abs() * v64.abs()).flatten(1).sum(1)
+        e_D = (K / 256 + 9) * U * D_abs + (e_dw * v64.abs()).flatten(1).sum(1)
+        rel = (K / 128 + 16) * U
+        nrm = v64.flatten(1).norm(dim=1)
+        e_sh = (ns / 64 + 9) * U * dsh.abs().sum(0)
+        gm = prm[3].detach().cpu().double() if prm[3] is not None else torch.ones(cout, dtype=torch.float64)
+        gg = prm[1].detach().cpu().double() if prm[1] is not None else torch.ones(cout, dtype=torch.float64)
+        b = prm[2].detach().cpu().double() if prm[2] is not None else torch.zeros(cout, dtype=torch.float64)
+        names = ["dv", "dg", "dbias", "dgamma", "dbeta"]
+        if kind == 1:
+            bounds = {"dv": e_dw, "dbias": e_sh}
+        else:
+            c0 = (gm * gg / nrm).view(-1, 1, 1, 1)
+            c1v = (dW * v64).flatten(1).sum(1) / nrm ** 2
+            bounds = {"dv": c0.abs() * (e_dw + (e_D / nrm ** 2).view(-1, 1, 1, 1) * v64.abs()
+                                        + rel * (dW.abs() + c1v.abs().view(-1, 1, 1, 1) * v64.abs())),
+                      "dg": (gm / nrm).abs() * (e_D + rel * D_abs),
+                      "dgamma": (gg / nrm).abs() * (e_D + rel * D_abs) + b.abs() * e_sh + rel * (b * dsh.sum(0)).abs(),
+                      "dbeta": e_sh, "dbias": gm.abs() * e_sh + rel * (gm * dsh.sum(0)).abs()}
+        for name, got, ref in zip(names, o1, grads if kind != 1 else [grads[0], None, grads[2], None, None]):
+            if name not in bounds or ref is None:
+                continue
+            assert_ulps(got / 2, ref, bounds[name] + U * ref.abs() + TINY, f"{name} {s}")
+
+
+# ------------------------------------------------------------------------------------------------ strided GEMM (seq_cls)
+def _gemm_case(M, N, K, split, at, nets=3, bias=False, acc=False, relu=False, mask=False, seed=0):
+    from behavior_driven_video_synthesis_amd import seq_cls
+    g = _gen(seed)
+    a_net, b_net = M * K + 13, K * N + 29
+    c_sl = M * N + 3
+    c_net = split * c_sl + 17
+    A = torch.randn(nets * a_net, generator=g)
+    B = torch.randn(nets * b_net, generator=g)
+    C0 = torch.randn(nets * c_net, generator=g)
+    bias_t = torch.randn(nets * (N + 2), generator=g) if bias else None
+    mask_t = torch.randn(nets * (M * (N + 1) + 4), generator=g) if mask else None
+    a_str = (a_net, 1, M) if at else (a_net, K, 1)          # at: A column-major (a transposed operand)
+    b_str = (b_net, N, 1)
+    c_str = (c_net, N, 1)
+    Ad, Bd, Cd = A.cuda(), B.cuda(), C0.cuda()
+    bd = bias_t.cuda() if bias else None
+    md = mask_t.cuda() if mask else None
+    seq_cls.gemm(seq_cls._ptr(Ad), seq_cls._ptr(Bd), seq_cls._ptr(Cd), M, N, K, nets, a_str, b_str, c_str, split=split,
+                 c_split=c_sl, bias=None if bd is None else seq_cls._ptr(bd), bias_net=N + 2,
+                 mask=None if md is None else seq_cls._ptr(md), mask_net=M * (N + 1) + 4, mask_m=N + 1, relu=int(relu),
+                 accumulate=int(acc))
+    got = Cd.cpu().double()
+    kc = ((K + split - 1) // split + 3) & ~3
+    ok = torch.ones(nets * c_net, dtype=torch.bool)
+    want = C0.double().clone()
+    bound = torch.zeros(nets * c_net, dtype=torch.float64)
+    A64, B64 = A.double(), B.double()
+    for net in range(nets):
+        if at:
+            Am = A64[net * a_net:net * a_net + M * K].view(K, M).T
+        else:
+            Am = A64[net * a_net:net * a_net + M * K].view(M, K)
+        Bm = B64[net * b_net:net * b_net + K * N].view(K, N)
+        for s in range(split):
+            kb, ke = s * kc, min(K, (s + 1) * kc)
+            if kb < ke:
+                prod, absprod = Am[:, kb:ke] @ Bm[kb:ke], Am[:, kb:ke].abs() @ Bm[kb:ke].abs()
+            else:
+                prod, absprod = torch.zeros(M, N, dtype=torch.float64), torch.zeros(M, N, dtype=torch.float64)
+            r = prod.clone()
+            extra = torch.zeros(M, N, dtype=torch.float64)
+            if bias and s == 0:
+                bv = bias_t.double()[net * (N + 2):net * (N + 2) + N].view(1, N)
+                r = r + bv
+                extra = extra + bv.abs()
+            base = net * c_net + s * c_sl
+            if acc:
+                c0 = C0.double()[base:base + M * N].view(M, N)
+                r = c0 + r
+                extra = extra + c0.abs() + r.abs()
+            if relu:
+                r = r.clamp_min(0)
+            if mask:
+                mv = mask_t.double()[net * (M * (N + 1) + 4):].view(-1)[:M * (N + 1)].view(M, N + 1)[:, :N]
+                keep = mv > 0
+                r = torch.where(keep, r, torch.zeros_like(r))
+                absprod = torch.where(keep, absprod, torch.zeros_like(absprod))
+                extra = torch.where(keep, extra, torch.zeros_like(extra))
+            want[base:base + M * N] = r.reshape(-1)
+            # k-ascending fp32 accumulation (exact products): <= (ke - kb) U sum|a b|; bias / accumulate round once each
+            bound[base:base + M * N] = ((ke - kb) * U * absprod + 2 * U * extra).reshape(-1)
+    assert_ulps(got, want, bound + TINY, f"gemm M{M} N{N} K{K} split{split} at{at}")
+
+
+@pytest.mark.parametrize("M,N,K", [(1, 1, 1), (3, 31, 2), (33, 65, 3), (65, 3, 31), (31, 33, 65), (65, 65, 33),
+                                   (1, 65, 65), (33, 1, 1)])
+@pytest.mark.parametrize("split", [1, 3, 8])
+@pytest.mark.parametrize("at", [False, True])
+def test_seq_cls_gemm_shapes(M, N, K, split, at):
+    """vunet_seq_cls_gemm_run (seq_cls.gemm, cls_gemm_kernel) against float64 matmul over 3 nets at their own net strides:
+    M, N, K from {1, 3, 31, 33, 65}, K < 4, split 1 / 3 / 8 (trailing slices empty where ceil(K / split) rounded up to 4
+    leaves none: they hold 0), A row- and column-major.  Elements of C outside the written slices keep their values."""
+    _gemm_case(M, N, K, split, at, seed=M * 7 + N * 3 + K + split)
+
+
+@pytest.mark.parametrize("flags", [dict(bias=True), dict(acc=True), dict(relu=True), dict(mask=True),
+                                   dict(bias=True, acc=True, relu=True, mask=True)])
+@pytest.mark.parametrize("split", [1, 4])
+def test_seq_cls_gemm_epilogue(flags, split):
+    """cls_gemm_kernel's epilogue: bias on slice 0 only, accumulate (C +=), ReLU, the mask (mask > 0 keeps), combined."""
+    _gemm_case(33, 31, 65, split, True, seed=5 + split, **flags)
+    _gemm_case(3, 65, 7, split, False, seed=6 + split, **flags)
