@@ -25,6 +25,8 @@ __host__ __device__ __forceinline__ uint32_t vunet_hash_u32(uint32_t x) {
 
 __device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : (__expf(x) - 1.f); }
 __device__ __forceinline__ float elu_grad_f(float x) { return x > 0.f ? 1.f : __expf(x); }
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }   // (expf, not __expf: the sequence kernels)
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // input-side activation (+ optional dropout keep/scale) used as the conv prologue
 struct InAct {

@@ -145,10 +145,8 @@ bool vunet_conv_1x1_applicable(const vunet_conv_desc* d, int pro) {
 // r03); with fewer m-tiles per workgroup x is re-read from L2, which at these sizes costs nothing
 static int mt_of(const vunet_conv_desc* d) {
   int MT = d->M <= 32 ? 1 : d->M <= 64 ? 2 : 4;
-#ifndef VUNET_AB_1X1_MT_BY_M   // (A/B baseline, tools/ab_build.sh)
   const long groups = ((long)d->N * d->Hs * d->Ws / 32 + 3) / 4;
   while (MT > 1 && groups * ((d->M + 32 * MT - 1) / (32 * MT)) < 1024) MT >>= 1;
-#endif
   return MT;
 }
 

@@ -137,11 +137,7 @@ __device__ __forceinline__ float store_tile_side(const GatherArgs& a, const PixG
   float vmax = 0.f;
   if (d.d2s) {  // sub-pixel store (up-convs, lib/modules.py: Upsample + DepthToSpace): scattered addresses
     const int Cq = d.M >> 2;
-#ifdef VUNET_AB_NO_D2S_FAST   // (A/B baseline, tools/ab_build.sh)
-    if (false) {
-#else
     if ((Cq & 31) == 0 && m_tile0 + 32 <= d.M && g.valid && (d.out_act == ACT_NONE || d.out_act == ACT_RELU)) {
-#endif
       // a 32-channel m-tile lies inside ONE sub-pixel block: (dy, dx) and the first output channel are tile-uniform,
       // so the per-element work is an add and a store (store_out divides by the runtime Cq for every element: the
       // up-conv layers ran 20 - 25 % below their stride-1 neighbours, r03 profiles/r03_layers_1stream.txt)
@@ -255,9 +251,6 @@ __device__ __forceinline__ void load_tile_side4(const GatherArgs& a, const PixGe
 //   2 data gradient * ELU'(aux); 3 the same with the dropout mask of the forward pass
 template <int MODE>
 __device__ __forceinline__ int side4_form(const GatherArgs& a) {
-#ifdef H2_EPI_GENERIC   // (A/B baseline for tools/ab_build.sh: always the general form)
-  return 0;
-#endif
   if (MODE == 0) return (a.d.out_act == ACT_NONE || a.d.out_act == ACT_RELU) ? 1 : 0;
   if (a.aux == nullptr) return 1;
   if (a.auxa.act == ACT_ELU) return a.auxa.thresh ? 3 : 2;
@@ -290,9 +283,7 @@ __device__ __forceinline__ float store_tile_side4(const GatherArgs& a, const Pix
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
       float v[4] = {acc[4 * q4], acc[4 * q4 + 1], acc[4 * q4 + 2], acc[4 * q4 + 3]};
-#ifndef H2_ABL_EPI_NOTRANSPOSE
       quad_transpose(v[0], v[1], v[2], v[3], k);
-#endif
       const int ch = m_tile0 + 8 * q4 + 4 * h + k;
       const size_t o = (size_t)(g.n * d.M + ch) * a.HoWo + pix0;
       const float4 rs = has_res ? s.res[q4] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -315,9 +306,6 @@ __device__ __forceinline__ float store_tile_side4(const GatherArgs& a, const Pix
         v[0] += r2[q4].x; v[1] += r2[q4].y; v[2] += r2[q4].z; v[3] += r2[q4].w;
       }
       if (ch < d.M) {
-#ifdef H2_ABL_EPI_NOSTORE
-        if (v[0] == 12345.f)
-#endif
         *reinterpret_cast<float4*>(a.y + o) = make_float4(v[0], v[1], v[2], v[3]);
         vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
       }

@@ -37,43 +37,14 @@
 
 #include "split_h2.h"
 
-// One LDS-DMA wave-instruction: 64 lanes x 16 bytes from per-lane global addresses to 1 KiB of LDS starting at the
-// wave-uniform byte address `lds_addr`.  Issued as inline assembly so that the compiler does not track it: the builtin
-// form makes hipcc wait vmcnt(0) before the NEXT ds_read (it cannot tell the read from the DMA's destination), i.e.
-// before the MFMA block the transfer is meant to hide behind.  The kernel retires the DMA itself (h2_dma_wait) before the
-// barrier that publishes the slab.  M0 is saved and restored (compiler-reserved).
-__device__ __forceinline__ void h2_dma16(const void* gsrc, uint32_t lds_addr) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_addr)
-               : "memory");
-}
-__device__ __forceinline__ void h2_dma_wait() {
-#ifndef H2_ABL_NOWAIT   // (timing ablations for tools/ab_build.sh: results are wrong with any H2_ABL_* defined)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
+// The weight slabs travel by LDS-DMA (split_h2.h: h2_dma16, untracked by the compiler): the kernel retires the DMA itself
+// before the barrier that publishes the slab.
+__device__ __forceinline__ void h2_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 union H2Unit {
   uint4 u;
   h2_f16x8 b;
 };
-
-// Timing-only builds (tools/ab_build.sh -DH2_ABL_* / -DH2_PROBE_* / -DH2_SINGLE / -DH2_PIPE) compile parts of the kernel out or
-// change its arithmetic: their results are WRONG by construction.  Such a library refuses every launch of this kernel unless
-// the process says it knows (VUNET_ALLOW_TIMING_BUILD=1, set by the timing tools) -- a product build defines none of them.
-#if defined(H2_ABL_NOX) || defined(H2_ABL_NOW) || defined(H2_ABL_NOSTORE) || defined(H2_ABL_NOWAIT) || \
-    defined(H2_PROBE_VLOAD) || defined(H2_SINGLE) || defined(H2_PIPE) || defined(H2_NO_TAP_BARRIER)
-#define VUNET_H2_TIMING_BUILD 1
-#else
-#define VUNET_H2_TIMING_BUILD 0
-#endif
-static inline bool h2_launch_allowed() {
-  if (!VUNET_H2_TIMING_BUILD) return true;
-  static const bool ok = [] { const char* e = getenv("VUNET_ALLOW_TIMING_BUILD"); return e && e[0] == '1'; }();
-  return ok;
-}
 
 // (diagnostic, tools/ab_build.sh -DH2_TSTAMP=<export name>: wave 0 of every workgroup records the 100 MHz wall clock at its
 // phase boundaries; tools/h2_timeline.py reads them back through the exported function.  Results are unchanged.)
@@ -131,15 +102,11 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
   // PIPE (16-wide maps): the fragment reads of tap kw + 1 are issued before the MFMAs of tap kw.  VGG19 conv5_x at bs 16 is
   // 256 workgroups -- one wave per SIMD, no partner whose MFMAs cover this wave's LDS latency -- and the compiler's schedule
   // is read -> wait -> MFMA: 93 -> 82 us forward, 113 -> 103 us data gradient (r03).  With two waves per SIMD (every other
-  // form) the same pipelining was 3 - 16 % SLOWER (r02, r03: -DH2_PIPE; conv3_x 242 -> 278 us), so it is tied to the tile width
+  // form) the same pipelining was 3 - 16 % SLOWER (r02, r03; conv3_x 242 -> 278 us), so it is tied to the tile width
   // (the 128-channel 32^2 layers, 256 workgroups of the 8-row tile, would gain 8 % -- 2 us on 14 launches: not instantiated).  Requesting all
   // staging rounds at the start of a chunk, dropping the weight-DMA wait (timing only) and one m-tile per workgroup (512
   // workgroups) each changed nothing here: the chunk time of this form is its fragment-read latency.
-#ifdef H2_PIPE
-  constexpr bool PIPE = PHW < 0;
-#else
   constexpr bool PIPE = TW == 16 && PHW < 0;
-#endif
   constexpr int PH = (PHW >= 0 && !ALLP) ? (PHW >> 1) : 0, PW = (PHW >= 0 && !ALLP) ? (PHW & 1) : 0;
   constexpr int NKH = (PHW < 0 || ALLP) ? 3 : (PH ? 2 : 1);   // kernel rows visited per chunk
   constexpr int NTHR = 64 * NWV;
@@ -192,15 +159,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
     vbits |= (ok ? 1u : 0u) << i;
   }
 
-#ifdef H2_SINGLE   // (experiment, tools/ab_build.sh: one accumulator set, low terms at natural scale)
-  f32x16 acc[MT][NQ];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][q][r] = 0.f;
-#else
   f32x16 acc[MT][NQ], acx[MT][NQ];   // leading term / the two cross terms (scaled by 2^11)
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
@@ -208,7 +166,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
     for (int q = 0; q < NQ; ++q)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mt][q][r] = acx[mt][q][r] = 0.f;
-#endif
 
   const int nch1 = d.C1 / 16, nch = nch1 + d.C2 / 16;
   float xv[NX][8];
@@ -223,20 +180,10 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
     const int cs = second ? (ch - nch1) * 16 : ch * 16;
     const int C = second ? d.C2 : d.C1;
     const float* __restrict__ xs = (second ? a.x2 : a.x1) + (size_t)(n * C + cs) * HW;
-#ifdef H2_PROBE_VLOAD   // (timing probe, tools/ab_build.sh: two 16-byte loads instead of eight dword loads; WRONG data)
-    {
-      const float4 va = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(xs) + 4u * (rel[i] & ~3u));
-      const float4 vb = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(xs) +
-                                                         4u * ((rel[i] & ~3u) + (((vbits >> i) & 1u) ? (unsigned)(4 * HW) : 0u)));
-      xv[i][0] = va.x; xv[i][1] = va.y; xv[i][2] = va.z; xv[i][3] = va.w;
-      xv[i][4] = vb.x; xv[i][5] = vb.y; xv[i][6] = vb.z; xv[i][7] = vb.w;
-    }
-#else
 #pragma unroll
     for (int k = 0; k < 8; ++k)
       xv[i][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(xs) +
                                                  4u * (rel[i] + (((vbits >> i) & 1u) ? (unsigned)(k * HW) : 0u)));
-#endif
   };
   // PRO 4: the ReLU mask travels separately and late (after the MFMA block, when the fragment registers are free)
   auto issue_mask = [&](int ch, int i) {
@@ -262,17 +209,10 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
     float v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-#ifdef H2_SELECT_AFTER   // (A/B, tools/ab_build.sh: the form before round 4 -- same values)
-      float t_ = xv[i][k];
-      if constexpr (PRO == 4) t_ = mk[0][k] > 0.f ? t_ : 0.f;
-      else if constexpr (PRO != 0) t_ = prologue<PRO>(ia, t_, (uint32_t)gbase + rel[i] + (uint32_t)(k * HW));
-      v[k] = ok ? t_ * sx : 0.f;
-#else
       float t_ = ok ? xv[i][k] : 0.f;
       if constexpr (PRO == 4) t_ = mk[0][k] > 0.f ? t_ : 0.f;
       else if constexpr (PRO != 0) t_ = prologue<PRO>(ia, t_, (uint32_t)gbase + rel[i] + (uint32_t)(k * HW));
       v[k] = t_ * sx;
-#endif
     }
     uint4 ph, pl;
     h2_split2(v[0], v[1], ph.x, pl.x);
@@ -358,16 +298,12 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
       const bool stage_begin = g == 0, stage_end = g == GS - 1;
       const bool more_w = !(LAST && ki == NKH - 1);            // another stage follows this step's
       const uint4* const xB = xB0 + (ch & 1) * 4 * PIX;
-#ifndef H2_ABL_NOX
       if constexpr (!LAST) {
 #pragma unroll
         for (int i = 0; i < NX; ++i)
           if (i * NKH / NX == ki) issue_x(ch + 1, i);
       }
-#endif
-#ifndef H2_ABL_NOW
       if (stage_begin && !(LAST && GS == NKH) && (GS == NKH || more_w)) issue_w(stage + 1, buf ^ 1);
-#endif
       // row / column of the staged tile (origin row0-1, col0-1) that tap (kh, kw) reads for output row q, column j
       const int dr = PHW >= 0 ? (ph_t + 1 - kh) / 2 + 1 : (MODE == 0 ? kh : 2 - kh);
       // fragment reads software-pipelined inside the phase: tap kw + 1 is read while tap kw multiplies (PIPE above)
@@ -393,19 +329,11 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
           for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int q = 0; q < NT; ++q) {
-#ifdef H2_SINGLE
-              f32x16 cx = acc[mt][q];
-              cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[kw & 1][1][mt].b, fb[kw & 1][0][q].b, cx, 0, 0, 0);
-              cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[kw & 1][0][mt].b, fb[kw & 1][1][q].b, cx, 0, 0, 0);
-              cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[kw & 1][0][mt].b, fb[kw & 1][0][q].b, cx, 0, 0, 0);
-              acc[mt][q] = cx;
-#else
               f32x16 cx = acx[mt][q];   // same products, same order and same accumulators as the plain loop below
               cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[kw & 1][1][mt].b, fb[kw & 1][0][q].b, cx, 0, 0, 0);
               cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[kw & 1][0][mt].b, fb[kw & 1][1][q].b, cx, 0, 0, 0);
               acx[mt][q] = cx;
               acc[mt][q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[kw & 1][0][mt].b, fb[kw & 1][0][q].b, acc[mt][q], 0, 0, 0);
-#endif
             }
         }
       } else
@@ -416,9 +344,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
         const int par = ph_t * 2 + pw_t;   // (fused parities) the accumulator tile of this tap
         // two waves share a SIMD: the partner's MFMAs cover this wave's fragment reads, so nothing is gained by
         // letting the scheduler hoist the next tap's 4*(MT+NT) fragment registers above this tap's MFMAs
-#ifndef H2_NO_TAP_BARRIER
         if constexpr (MT * NT < 8) __builtin_amdgcn_sched_barrier(0);
-#endif
         const int dc = PHW >= 0 ? (pw_t + 1 - kw) / 2 + 1 : (MODE == 0 ? kw : 2 - kw);
         H2Unit av[2][MT], bv[2][NT];
 #pragma unroll
@@ -428,34 +354,19 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
 #pragma unroll
           for (int q = 0; q < NT; ++q) bv[p][q].u = xB[p * 2 * PIX + (q * RPQ + dr) * IW + dc];
         }
-#ifdef H2_SETPRIO   // (experiment, tools/ab_build.sh: raised issue priority around the tap's MFMA cluster)
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
           for (int q = 0; q < NT; ++q) {
             const int qa = ALLP ? par : q;   // accumulator tile (compile-time after unrolling)
-#ifdef H2_SINGLE
-            f32x16 cx = acc[mt][qa];
-            cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[1][mt].b, bv[0][q].b, cx, 0, 0, 0);
-            cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][mt].b, bv[1][q].b, cx, 0, 0, 0);
-            cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][mt].b, bv[0][q].b, cx, 0, 0, 0);
-            acc[mt][qa] = cx;
-#else
             f32x16 cx = acx[mt][qa];
             cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[1][mt].b, bv[0][q].b, cx, 0, 0, 0);
             cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][mt].b, bv[1][q].b, cx, 0, 0, 0);
             acx[mt][qa] = cx;
             acc[mt][qa] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][mt].b, bv[0][q].b, acc[mt][qa], 0, 0, 0);
-#endif
           }
-#ifdef H2_SETPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
       }
       __builtin_amdgcn_sched_barrier(0);
-#ifndef H2_ABL_NOX
       if constexpr (!LAST) {
 #pragma unroll
         for (int i = 0; i < NX; ++i)
@@ -464,7 +375,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
             write_x(ch + 1, i);
           }
       }
-#endif
       if (stage_end && more_w) {
         h2_dma_wait();
         __syncthreads();
@@ -480,7 +390,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
   chunk(nch - 1, std::true_type{});
   H2_STAMP(3);
 
-  // What the output store costs (r02, tools/time_conv.py with -DH2_ABL_NOSTORE): without it every layer runs at ~305
+  // What the output store costs (r02, tools/time_conv.py on a build that skipped the store): without it every layer runs at ~305
   // TFLOP/s whatever its K; with 4-byte stores (lane = pixel, one store instruction per accumulator register) the
   // short-K layers paid 15 % (C = 128) to 36 % (C = 32 at 256^2: 135 us, 87 us without the store) -- ~2.8 TB/s of output
   // wherever the stores were placed in time.  It is the per-CU memory path, ~40 cycles per store INSTRUCTION whatever
@@ -489,7 +399,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
   // store_tile_side4; conv2_2 281 -> 270 us, conv1_2 353 -> 335, the 64-channel RNB conv 82 -> 74, C = 32 131 -> 121).
   // Measured and discarded on the way (no gain): persistent workgroups prefetching the next tile's first chunk across
   // the epilogue; 512-thread workgroups with whole-chunk weight stages; starting the first round of workgroups in eight
-  // phases spread over a tile period; non-temporal stores; s_setprio 1 around every tap's MFMA cluster (-DH2_SETPRIO, r03:
+  // phases spread over a tile period; non-temporal stores; s_setprio 1 around every tap's MFMA cluster (r03:
   // within +-3 % on every layer shape of tools/time_conv.py).
   // r03, tools/h2_timeline.py (wall-clock stamps per workgroup): a tile of the 64 x 8 form spends 2.5 us reducing the maxima
   // behind its first loads, ~1 us converting them, 5.3 - 5.6 us per 16-channel chunk and 7 - 8 us in the epilogue below --
@@ -517,11 +427,7 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
     constexpr int t = decltype(tc)::value, q = t / MT, mt = t % MT;
     f32x16 c;
 #pragma unroll
-#ifdef H2_SINGLE
-    for (int r = 0; r < 16; ++r) c[r] = acc[mt][q][r] * descale * descale2;
-#else
     for (int r = 0; r < 16; ++r) c[r] = (acc[mt][q][r] + acx[mt][q][r] * (1.f / 2048.f)) * descale * descale2;
-#endif
     return c;
   };
   float ymax = 0.f;   // max |y| over what this lane stores (published below if the caller asked for it)
@@ -540,13 +446,8 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
         f32x16 c0, c1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-#ifdef H2_SINGLE
-          c0[r] = acc[mt][2 * ph][r] * descale * descale2;
-          c1[r] = acc[mt][2 * ph + 1][r] * descale * descale2;
-#else
           c0[r] = (acc[mt][2 * ph][r] + acx[mt][2 * ph][r] * (1.f / 2048.f)) * descale * descale2;
           c1[r] = (acc[mt][2 * ph + 1][r] + acx[mt][2 * ph + 1][r] * (1.f / 2048.f)) * descale * descale2;
-#endif
         }
         ymax = fmaxf(ymax, store_tile_pair(a, n, 2 * orow + ph, 2 * ocol, m0 + 32 * mt, h, c0, c1));
       }
@@ -561,9 +462,6 @@ __global__ __launch_bounds__(64 * NWV, (NWV == 8 || MT * NT >= 8) ? 1 : 2) void 
       if constexpr (t == 0) load_tile_side4<MODE, FORM>(a, geo(0), m0, h, k, side[0]);
       if constexpr (t + 1 < MT * NT)
         load_tile_side4<MODE, FORM>(a, geo((t + 1) / MT), m0 + 32 * ((t + 1) % MT), h, k, side[(t + 1) & 1]);
-#ifdef H2_ABL_NOSTORE   // timing ablation (tools/ab_build.sh): the output is not written
-      if (descale == 12345.f)
-#endif
       ymax = fmaxf(ymax, store_tile_side4<MODE, FORM>(a, geo(q), m0 + 32 * mt, h, k, combined(tc), side[t & 1]));
     };
     auto tiles = [&](auto form_c) {
@@ -627,7 +525,6 @@ static int launch_h2_one(const GatherArgs& ga, const void* wx, int mtiles_pad, c
   constexpr size_t lds = (size_t)(8 * PIX + 2 * H2_SLAB * MT * (NWV == 8 ? NKH : 1)) * 16;
   const vunet_conv_desc& d = ga.d;
   const int blocks = d.N * (d.Hs / (NWV * NT * RPQ)) * (d.Ws / TW) * ((d.M + 32 * MT - 1) / (32 * MT));
-  if (!h2_launch_allowed()) return VUNET_ERR_UNSUPPORTED;
   auto kern = conv_h2_kernel<MT, NT, MODE, PRO, PHW, NWV, TW>;
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)

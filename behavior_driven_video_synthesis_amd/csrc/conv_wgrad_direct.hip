@@ -37,21 +37,6 @@ struct WgradDirectArgs {
 typedef uint32_t wd_u32x4 __attribute__((ext_vector_type(4)));
 typedef float wd_f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void wd_split2(float a, float b, uint32_t& h, uint32_t& l) {   // low term at natural scale
-  h2_f16x2 ph, pl;
-  ph[0] = (_Float16)a;
-  ph[1] = (_Float16)b;
-  pl[0] = (_Float16)(a - (float)ph[0]);
-  pl[1] = (_Float16)(b - (float)ph[1]);
-  h = __builtin_bit_cast(uint32_t, ph);
-  l = __builtin_bit_cast(uint32_t, pl);
-}
-
-__device__ __forceinline__ h2_f16x8 wd_frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  wd_u32x4 u = {a, b, c, d};
-  return __builtin_bit_cast(h2_f16x8, u);
-}
-
 // S: stride (1, 2).  W4: output maps 4 wide (an octet is two output rows of 4).  T: 9 (3x3, pad 1) or 1 (1x1, S = 1), or
 // 3: the three taps of ONE kernel row -- a wave then owns (co tile, kernel row kh): it loads one input row per octet instead
 // of three and keeps three accumulators instead of nine (~110 VGPRs instead of 243), so four waves per SIMD cover the
@@ -136,12 +121,12 @@ __device__ __forceinline__ void wgrad_direct_body(WgradDirectArgs& a, const int 
       if (!(ov && co_ok)) { d0 = wd_f32x4{0.f, 0.f, 0.f, 0.f}; d1 = d0; }
       dsum += ((d0[0] + d0[1]) + (d0[2] + d0[3])) + ((d1[0] + d1[1]) + (d1[2] + d1[3]));
       uint32_t ah[4], al[4];
-      wd_split2(d0[0] * sdy, d0[1] * sdy, ah[0], al[0]);
-      wd_split2(d0[2] * sdy, d0[3] * sdy, ah[1], al[1]);
-      wd_split2(d1[0] * sdy, d1[1] * sdy, ah[2], al[2]);
-      wd_split2(d1[2] * sdy, d1[3] * sdy, ah[3], al[3]);
-      Ah = wd_frag(ah[0], ah[1], ah[2], ah[3]);
-      Al = wd_frag(al[0], al[1], al[2], al[3]);
+      h2_split2_nat(d0[0] * sdy, d0[1] * sdy, ah[0], al[0]);
+      h2_split2_nat(d0[2] * sdy, d0[3] * sdy, ah[1], al[1]);
+      h2_split2_nat(d1[0] * sdy, d1[1] * sdy, ah[2], al[2]);
+      h2_split2_nat(d1[2] * sdy, d1[3] * sdy, ah[3], al[3]);
+      Ah = h2_frag(ah[0], ah[1], ah[2], ah[3]);
+      Al = h2_frag(al[0], al[1], al[2], al[3]);
     }
 
     // ---- B source: R input rows x L columns of channel ci, prologue applied, scaled; seg[rr][0] is input column
@@ -201,11 +186,11 @@ __device__ __forceinline__ void wgrad_direct_body(WgradDirectArgs& a, const int 
         else f[e] = seg[kh][e * S + kw];
       }
       uint32_t bh[4], bl[4];
-      wd_split2(f[0], f[1], bh[0], bl[0]);
-      wd_split2(f[2], f[3], bh[1], bl[1]);
-      wd_split2(f[4], f[5], bh[2], bl[2]);
-      wd_split2(f[6], f[7], bh[3], bl[3]);
-      const h2_f16x8 Bh = wd_frag(bh[0], bh[1], bh[2], bh[3]), Bl = wd_frag(bl[0], bl[1], bl[2], bl[3]);
+      h2_split2_nat(f[0], f[1], bh[0], bl[0]);
+      h2_split2_nat(f[2], f[3], bh[1], bl[1]);
+      h2_split2_nat(f[4], f[5], bh[2], bl[2]);
+      h2_split2_nat(f[6], f[7], bh[3], bl[3]);
+      const h2_f16x8 Bh = h2_frag(bh[0], bh[1], bh[2], bh[3]), Bl = h2_frag(bl[0], bl[1], bl[2], bl[3]);
       f32x16 cc = acc[t];
       cc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, cc, 0, 0, 0);
       cc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, cc, 0, 0, 0);
@@ -427,8 +412,8 @@ __global__ __launch_bounds__(64 * NWAVE) void conv_wgrad_s2_kernel(const WgradDi
 #pragma unroll
       for (int e = 0; e < 4; ++e) f[e] = ok ? in_act_form<PRO>(ia, xv[K_][i][e], idx + e) * sx : 0.f;
       uint32_t eh, el, oh, ol;
-      wd_split2(f[0], f[2], eh, el);                      // even input columns -> E[2q], E[2q + 1]
-      wd_split2(f[1], f[3], oh, ol);                      // odd input columns  -> O[2q + 1], O[2q + 2]
+      h2_split2_nat(f[0], f[2], eh, el);                      // even input columns -> E[2q], E[2q + 1]
+      h2_split2_nat(f[1], f[3], oh, ol);                      // odd input columns  -> O[2q + 1], O[2q + 2]
       unsigned char* base = xL + (size_t)rr * 4 * S2Lds::XPLANE + ci * S2Lds::PITCH;
       *reinterpret_cast<uint32_t*>(base + 0 * S2Lds::XPLANE + 4 * q) = eh;
       *reinterpret_cast<uint32_t*>(base + 1 * S2Lds::XPLANE + 4 * q) = el;
@@ -446,7 +431,7 @@ __global__ __launch_bounds__(64 * NWAVE) void conv_wgrad_s2_kernel(const WgradDi
       const uint32_t idx = (uint32_t)(n * Cs + cl0 + ci) * (uint32_t)HW + (uint32_t)((ok ? ih : 0) * W + (ok ? 2 * cb - 1 : 0));
       const float f0 = ok ? in_act_form<PRO>(ia, xhalo[K_], idx) * sx : 0.f;
       uint32_t hh, hl;
-      wd_split2(f0, 0.f, hh, hl);
+      h2_split2_nat(f0, 0.f, hh, hl);
       unsigned char* base = xL + (size_t)rr * 4 * S2Lds::XPLANE + ci * S2Lds::PITCH;
       *reinterpret_cast<uint16_t*>(base + 2 * S2Lds::XPLANE) = (uint16_t)(hh & 0xffffu);
       *reinterpret_cast<uint16_t*>(base + 3 * S2Lds::XPLANE) = (uint16_t)(hl & 0xffffu);
@@ -458,8 +443,8 @@ __global__ __launch_bounds__(64 * NWAVE) void conv_wgrad_s2_kernel(const WgradDi
       if (cot >= NCOT) continue;
       dsum[i] += (dv[K_][i][0] + dv[K_][i][1]) + (dv[K_][i][2] + dv[K_][i][3]);
       uint32_t h0, l0, h1, l1;
-      wd_split2(dv[K_][i][0] * sdy, dv[K_][i][1] * sdy, h0, l0);
-      wd_split2(dv[K_][i][2] * sdy, dv[K_][i][3] * sdy, h1, l1);
+      h2_split2_nat(dv[K_][i][0] * sdy, dv[K_][i][1] * sdy, h0, l0);
+      h2_split2_nat(dv[K_][i][2] * sdy, dv[K_][i][3] * sdy, h1, l1);
       unsigned char* base = dL + (size_t)cot * S2Lds::DYCOT + co * S2Lds::PITCH + 8 * q4;
       *reinterpret_cast<uint2*>(base) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(base + 32 * S2Lds::PITCH) = make_uint2(l0, l1);

@@ -21,7 +21,7 @@
 // alternate pixel tiles half a step apart: while group 0 multiplies its tile, group 1 loads, converts and writes its next
 // one, and vice versa -- one barrier per half step.  A SIMD holds one wave of each group (waves w and w + 4), so its
 // matrix pipe always has a wave in the MFMA phase beside one in the staging phase; the phases overlap by construction,
-// not by luck.  The groups' accumulators meet in the fixed-order fold at the end.  -DWG_H2_ONE_GROUP: the round-3 shape.
+// not by luck.  The groups' accumulators meet in the fixed-order fold at the end.
 // With the phases in antiphase the exposed latencies are what is left (tools/wgrad_timeline.py, profiles/r04_wgrad_timeline.txt:
 // f(x) loads 2.0 us, conversion 1.5 - 2.3, dy loads 1.4 - 2.0, the 108 MFMAs 2.4 - 2.7), so both load streams left the phase
 // that consumes them.  The raw fp32 tile of a group's NEXT step is copied global -> LDS by LDS-DMA (global_load_lds_dwordx4 /
@@ -30,7 +30,7 @@
 // destination is the conversion's read order, [wave][unit i][half][lane], linear and conflict-free -- so the raw buffer
 // needs no barrier of its own: a wave retires its copy (s_waitcnt vmcnt) at the top of its next staging phase and overwrites
 // it only after it has consumed it.  dy is requested at the top of the staging phase and lands during the conversion: the
-// multiply phase starts with everything in registers / LDS and is the 108 MFMAs.  -DWG_H2_NO_DMA: register staging (A/B).
+// multiply phase starts with everything in registers / LDS and is the 108 MFMAs.
 //
 // Edge plane (round 4).  The +-1 column fragments need, per (row, ci, octet), the pixel left of the octet and the pixel right
 // of it.  Rounds 2-3 read them as the last dword of the previous unit and the first dword of the next one: 64 lanes reading
@@ -78,16 +78,9 @@ extern "C" int WG_TSTAMP(unsigned long long* out, int nblocks) {
 #define WG_STAMP_AT(slot_)
 #endif
 
-// One LDS-DMA wave-instruction (see conv_h2_kernel.h: h2_dma16): 64 lanes x 16 (4) bytes from per-lane global addresses
-// to 1 KiB (256 B) of LDS at the wave-uniform byte address `lds_addr`; inline assembly (the compiler does not track it: the
-// kernel retires it itself with s_waitcnt vmcnt), M0 saved and restored.
-__device__ __forceinline__ void wg_dma16(const void* gsrc, uint32_t lds_addr) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_addr)
-               : "memory");
-}
+// The 4-byte form of split_h2.h's h2_dma16: one LDS-DMA wave-instruction, 64 lanes x 4 bytes from per-lane global addresses
+// to 256 B of LDS at the wave-uniform byte address `lds_addr`; inline assembly (the compiler does not track it: the kernel
+// retires it itself with s_waitcnt vmcnt), M0 saved and restored.
 __device__ __forceinline__ void wg_dma4(const void* gsrc, uint32_t lds_addr) {
   uint32_t keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
@@ -114,41 +107,16 @@ struct WgradH2Args {
   const float* amax_dy;   // 1024 partial maxima of |dy| (second half zeros)
 };
 
-// (a, b), already scaled -> packed fp16 pairs of the two terms, the low one at its natural scale
-__device__ __forceinline__ void wg_split2(float a, float b, uint32_t& h, uint32_t& l) {
-  h2_f16x2 ph, pl;
-  ph[0] = (_Float16)a;
-  ph[1] = (_Float16)b;
-  pl[0] = (_Float16)(a - (float)ph[0]);
-  pl[1] = (_Float16)(b - (float)ph[1]);
-  h = __builtin_bit_cast(uint32_t, ph);
-  l = __builtin_bit_cast(uint32_t, pl);
-}
-
-__device__ __forceinline__ wg_bf16x8 wg_frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  wg_u32x4 u = {a, b, c, d};
-  return __builtin_bit_cast(wg_bf16x8, u);
-}
-
-#ifdef WG_H2_ONE_GROUP
-constexpr int WG_GROUPS = 1;
-#else
-constexpr int WG_GROUPS = 2;
-#endif
+constexpr int WG_GROUPS = 2;   // groups of four waves per workgroup, in antiphase (one group: the round-3 shape)
 
 template <int MTW>
-__global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_wgrad_h2_kernel(const WgradH2Args a_in) {
+__global__ __launch_bounds__(256 * WG_GROUPS, 1) void conv_wgrad_h2_kernel(const WgradH2Args a_in) {
   WgradH2Args a = a_in;
   WG_STAMP_AT(7);    // (slot 7 of group 0: kernel entry; slot 15: the tile loop is over; slot 14: exit)
   inact_resolve(a.in1);
   inact_resolve(a.in2);
   constexpr int TH = 4;
-  // optional register prefetch of the next tile's f(x) across the MFMA block
-#ifdef WG_H2_PREFETCH
-  constexpr bool PREFETCH = true;
-#else
-  constexpr bool PREFETCH = false;   // measured: no gain from the register prefetch (r02), and two m-tiles spill with it
-#endif
+  // (a register prefetch of the next tile's f(x) across the MFMA block: no gain (r02), and two m-tiles spilled with it)
   constexpr int WP = 4 / MTW;        // waves sharing one m-tile (they split the tile rows)
   constexpr int RW = TH / WP;        // tile rows per wave
   constexpr int ENT = 6 * 32;        // (row, ci) entries of the staged tile
@@ -157,14 +125,8 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
   // The raw-tile DMA keeps dy live across the conversion: one m-tile per workgroup (RW = 1: 16 dy registers) has the room,
   // two m-tiles (RW = 2: 32) spill 18 registers in the staging phase and lose what the copy gains (same box, sustained
   // launches, profiles/r04_time_wgrad.txt: Cout = 32 at 256^2 112 -> 96 us with the copy; 64 channels at 256^2 333 -> 366 us,
-  // 64 + 64 -> 64 at 128^2 136 -> 160 us): DMA for the one-m-tile form only.  -DWG_H2_NO_DMA / -DWG_H2_DMA_ALL: A/B.
-#if defined(WG_H2_NO_DMA)
-  constexpr bool DMA = false;
-#elif defined(WG_H2_DMA_ALL)
-  constexpr bool DMA = true;
-#else
+  // 64 + 64 -> 64 at 128^2 136 -> 160 us): DMA for the one-m-tile form only.
   constexpr bool DMA = MTW == 1;
-#endif
   constexpr int SU = 2 * PL + 2 * EPL / 4;   // 16-byte units of one group's staged tile (two planes + two edge planes)
   constexpr int RU = ENT * 8 + 2 * ENT / 4;  // ... of its raw fp32 tile [48 groups][2 halves][16] + the halo columns [2][ENT]
   constexpr int GU = SU + (DMA ? RU : 0);
@@ -233,8 +195,8 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
   const int t_begin = split * a.tps;
   const int t_end = min(t_begin + a.tps, a.ntiles);
 
-  // ---- f(x) staging, register-prefetched one tile ahead: the loads of tile t+1 are issued before the MFMA block of
-  //      tile t and split / written to LDS after it (the input tile is single-buffered: two barriers per tile)
+  // ---- f(x) staging through registers (the form without the raw-tile DMA): loaded at the top of the staging phase, split
+  //      and written to LDS behind it (the input tile is single-buffered: two barriers per tile)
   wg_f32x4 xv[3][2];      // main units: 8 consecutive columns each
   float hv[2];            // halo columns -1 / 32 of entry `tid` (tid < 192)
   uint32_t gidx[3], hidx = 0;
@@ -285,8 +247,8 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
       const int ih = row0 - 1 + s_row[i];
       const bool ok = (unsigned)ih < (unsigned)H;
       const float* src = xs + (size_t)((n * Cs + cbase + s_ci[i]) * H + (ok ? ih : 0)) * W + col0 + 8 * s_oct[i];
-      wg_dma16(src, raw_addr + (uint32_t)(((wave_u * 3 + i) * 2 + 0) * 64) * 16u);
-      wg_dma16(src + 4, raw_addr + (uint32_t)(((wave_u * 3 + i) * 2 + 1) * 64) * 16u);
+      h2_dma16(src, raw_addr + (uint32_t)(((wave_u * 3 + i) * 2 + 0) * 64) * 16u);
+      h2_dma16(src + 4, raw_addr + (uint32_t)(((wave_u * 3 + i) * 2 + 1) * 64) * 16u);
     }
     if (wave_u < 3) {   // entries tid = 64 wave + lane < ENT
       const int ih = row0 - 1 + (tid >> 5);
@@ -333,10 +295,10 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
         f[e] = in_act_form<PRO>(ia, ok ? t : 0.f, gidx[i] + e) * sxk;
       }
       uint32_t ph[4], pl[4];
-      wg_split2(f[0], f[1], ph[0], pl[0]);
-      wg_split2(f[2], f[3], ph[1], pl[1]);
-      wg_split2(f[4], f[5], ph[2], pl[2]);
-      wg_split2(f[6], f[7], ph[3], pl[3]);
+      h2_split2_nat(f[0], f[1], ph[0], pl[0]);
+      h2_split2_nat(f[2], f[3], ph[1], pl[1]);
+      h2_split2_nat(f[4], f[5], ph[2], pl[2]);
+      h2_split2_nat(f[6], f[7], ph[3], pl[3]);
       const int unit = (s_row[i] * 32 + s_ci[i]) * 5 + 1 + s_oct[i];
       xL[unit] = wg_u32x4{ph[0], ph[1], ph[2], ph[3]};
       xL[PL + unit] = wg_u32x4{pl[0], pl[1], pl[2], pl[3]};
@@ -358,7 +320,7 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
       const float fl = in_act_form<PRO>(ia, okl ? hv[0] : 0.f, hidx - 1) * (okl ? sx : 0.f);
       const float fr = in_act_form<PRO>(ia, okr ? hv[1] : 0.f, hidx + 32) * (okr ? sx : 0.f);
       uint32_t ph, pl;
-      wg_split2(fr, fl, ph, pl);   // low half = right halo, high = left
+      h2_split2_nat(fr, fl, ph, pl);   // low half = right halo, high = left
       unsigned short* const eb = reinterpret_cast<unsigned short*>(eL);
       const int r = tid >> 5, c = tid & 31;
       eb[2 * ((r * 4 + 0) * 32 + c) + 1] = (unsigned short)(ph >> 16);           // left of octet 0: column -1
@@ -409,9 +371,6 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
     WG_STAMP(0);
     // ---- staging phase: the tile's f(x) -> two fp16 planes + edge plane
     if (valid) {
-#ifdef WG_ABL_NOX   // (timing ablations for tools/ab_build.sh: results are WRONG with any WG_ABL_* defined)
-      if (step == 0 || descale == 12345.f) {
-#endif
       if constexpr (DMA) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's copy of the tile (issued a phase ago) has landed
         load_dy(mtile);                                      // lands during the conversion
@@ -430,9 +389,6 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[RW - 1][1][1]) :: "memory");
         if (more) dma_x(mtile + G);                          // this wave is done with its raw units: the next tile's
       }
-#ifdef WG_ABL_NOX
-      }
-#endif
     }
     WG_STAMP(2);
     __syncthreads();
@@ -477,12 +433,12 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
         const wg_f32x4 d0 = dyv[rr][s][0], d1 = dyv[rr][s][1];
         dsum += ((d0[0] + d0[1]) + (d0[2] + d0[3])) + ((d1[0] + d1[1]) + (d1[2] + d1[3]));
         uint32_t ah[4], al[4];
-        wg_split2(d0[0] * sdy, d0[1] * sdy, ah[0], al[0]);
-        wg_split2(d0[2] * sdy, d0[3] * sdy, ah[1], al[1]);
-        wg_split2(d1[0] * sdy, d1[1] * sdy, ah[2], al[2]);
-        wg_split2(d1[2] * sdy, d1[3] * sdy, ah[3], al[3]);
-        Ah = wg_frag(ah[0], ah[1], ah[2], ah[3]);
-        Al = wg_frag(al[0], al[1], al[2], al[3]);
+        h2_split2_nat(d0[0] * sdy, d0[1] * sdy, ah[0], al[0]);
+        h2_split2_nat(d0[2] * sdy, d0[3] * sdy, ah[1], al[1]);
+        h2_split2_nat(d1[0] * sdy, d1[1] * sdy, ah[2], al[2]);
+        h2_split2_nat(d1[2] * sdy, d1[3] * sdy, ah[3], al[3]);
+        Ah = h2_frag(ah[0], ah[1], ah[2], ah[3]);
+        Al = h2_frag(al[0], al[1], al[2], al[3]);
       }
       // one plane of f(x) at a time, smallest terms first: only three shifted fragments are live
       //   plane l: Ah*Bl ; plane h: Al*Bh, Ah*Bh
@@ -493,9 +449,9 @@ __global__ __launch_bounds__(256 * WG_GROUPS, WG_GROUPS == 2 ? 1 : 2) void conv_
         const uint32_t s01 = __builtin_amdgcn_alignbit(c.y, c.x, 16), s12 = __builtin_amdgcn_alignbit(c.z, c.y, 16),
                        s23 = __builtin_amdgcn_alignbit(c.w, c.z, 16);
         wg_bf16x8 B[3];
-        B[0] = wg_frag(__builtin_amdgcn_alignbit(c.x, cur.e[p], 16), s01, s12, s23);   // columns p - 1
+        B[0] = h2_frag(__builtin_amdgcn_alignbit(c.x, cur.e[p], 16), s01, s12, s23);   // columns p - 1
         B[1] = __builtin_bit_cast(wg_bf16x8, c);                                        // columns p
-        B[2] = wg_frag(s01, s12, s23, __builtin_amdgcn_alignbit(cur.e[p], c.w, 16));   // columns p + 1
+        B[2] = h2_frag(s01, s12, s23, __builtin_amdgcn_alignbit(cur.e[p], c.w, 16));   // columns p + 1
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
           f32x16 cc = acc[kh * 3 + kw];
@@ -618,13 +574,7 @@ int vunet_wgrad_h2_launch(const vunet_wgrad_desc* d, const float* x1, const floa
   // form that stages by LDS-DMA]; the fold through LDS reuses 16 KiB per group of it
   constexpr size_t staged = (size_t)2 * (6 * 32 * 5 + 1) * 16 + (size_t)2 * 6 * 4 * 32 * 4;
   constexpr size_t raw_bytes = (size_t)6 * 32 * 8 * 16 + (size_t)2 * 6 * 32 * 4;
-#if defined(WG_H2_NO_DMA)
-  constexpr size_t lds1 = WG_GROUPS * staged, lds2 = lds1;
-#elif defined(WG_H2_DMA_ALL)
-  constexpr size_t lds1 = WG_GROUPS * (staged + raw_bytes), lds2 = lds1;
-#else
   constexpr size_t lds1 = WG_GROUPS * (staged + raw_bytes), lds2 = WG_GROUPS * staged;
-#endif
   static const bool attr_ok = [] {
     return (lds1 <= 64 * 1024 || hipFuncSetAttribute((const void*)conv_wgrad_h2_kernel<1>,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1) == hipSuccess) &&

@@ -57,8 +57,6 @@ struct SeqLinearArgs {
   int H, hoff, n, B;
 };
 
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
 __device__ __forceinline__ float seq_act(float v, int act) {
   if (act == 1) return fmaxf(v, 0.01f * v);   // nn.LeakyReLU() default slope 0.01 (lib/modules.py:244)
   if (act == 2) return tanhf(v);              // the scale nets' head (lib/modules.py:252-253)
@@ -69,15 +67,11 @@ __device__ __forceinline__ float seq_act(float v, int act) {
 // The weight stream is the cost and a wave has few chunks (2 - 8), so what matters is bytes in flight: a group of U chunks
 // issues all of its loads (weights of RT tiles, the operand of NB batch tiles) before the first MFMA.  The scheduling barrier
 // keeps it that way: without it the scheduler interleaves loads and uses to save registers and keeps ~7 loads in flight.
-#ifdef SEQ_W_NO_NT   // (timing-ablation build, tools/ab_build.sh)
-__device__ __forceinline__ float4 seq_w_load(const float* p) { return *reinterpret_cast<const float4*>(p); }
-#else
 typedef float seq_f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 seq_w_load(const float* p) {
   const seq_f4v t = __builtin_nontemporal_load(reinterpret_cast<const seq_f4v*>(p));
   return make_float4(t.x, t.y, t.z, t.w);
 }
-#endif
 
 // LAY (include/vunet_seq_tiled.h): bit 0 -- the weights are tile-major images, bit 1 -- the operand is: a chunk is then 2 KB
 // contiguous, [half][lane] float4, and each of a wave's loads covers 1 KB contiguous.
@@ -98,7 +92,7 @@ __device__ __forceinline__ void seq_group_load(const SeqLinearArgs& a, const flo
         const float* wp = w + (size_t)rt * 16 * a.K + 512 * (c0 + WAVES * u);
         r.wv[rt][u][0] = *reinterpret_cast<const float4*>(wp);
         r.wv[rt][u][1] = *reinterpret_cast<const float4*>(wp + 256);
-      } else if constexpr (LAY & 1) {   // (read once per pass by this one workgroup: streamed past the caches' retention, SEQ_W_NT)
+      } else if constexpr (LAY & 1) {   // (read once per pass by this one workgroup: streamed past the caches' retention, seq_w_load)
         const float* wp = w + (size_t)rt * 16 * a.K + 512 * (c0 + WAVES * u);
         r.wv[rt][u][0] = seq_w_load(wp);
         r.wv[rt][u][1] = seq_w_load(wp + 256);
@@ -169,8 +163,6 @@ __device__ __forceinline__ void seq_linear_group(const SeqLinearArgs& a, const f
   seq_group_mfma<NB, RT, U>(r, acc);
 }
 
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-
 // grid (M / 16, S, nets), 64 WAVES threads.  Lane l of a wave: i = l & 15 (weight row / batch row), kq = l >> 4; in a K chunk of 32
 // it holds k = 8 kq .. 8 kq + 7 of its row -- the same k for the A (weights) and B (batch) operand of MFMA step j = 0..7.
 // D: lane holds batch row n = l & 15 of its tile, output rows 4 (l >> 4) + r of the weight tile.
@@ -202,16 +194,11 @@ __global__ __launch_bounds__(64 * WAVES) void seq_linear_kernel(SeqLinearArgs a)
   // (four-wave form at 3 - 4 batch tiles with groups of 4 instead of 2: 6.96 -> 7.10 ms per flow training step)
   constexpr int UMAX = WAVES == 16 ? (NB == 1 ? 4 : 2) : ((NB + RT <= 3) ? 4 : 2);
   // Four-wave workgroups at 3 - 4 batch tiles are one wave per SIMD (256 workgroups on 256 CUs): nothing else runs while a wave
-  // waits for its loads, so the wave itself keeps a RING of SEQ_RING stages (of SEQ_RING_U chunks) in flight -- the loads of stage
-  // i + SEQ_RING - 1 are issued before the matrix steps of stage i (the compiler's counted vmcnt waits retire them in order).
-  // Same chunks, same order, same sums as the plain loop.  (flow training step at 64 rows: see DESIGN.md section 5.R6.)
-#ifndef SEQ_RING
-#define SEQ_RING 2
-#endif
-#ifndef SEQ_RING_U
-#define SEQ_RING_U 1
-#endif
-  if constexpr (WAVES == 4 && NB >= 3 && SEQ_RING == 2 && SEQ_RING_U == 1) {
+  // waits for its loads, so the wave itself keeps a RING of two stages (of one chunk) in flight -- the loads of stage i + 1 are
+  // issued before the matrix steps of stage i (the compiler's counted vmcnt waits retire them in order).  Same chunks, same
+  // order, same sums as the plain loop.  (flow training step at 64 rows, and the deeper / wider rings that lost: DESIGN.md
+  // section 5.R6, profiles/retired_knobs.md.)
+  if constexpr (WAVES == 4 && NB >= 3) {
     // depth 2, any number of chunks (an odd count -- 34 chunks over four waves: 9, 9, 8, 8 -- keeps its last chunk in the ring)
     const int nw = c < nchunk ? (nchunk - c + WAVES - 1) / WAVES : 0;   // this wave's chunks
     if (nw > 0) {
@@ -238,33 +225,6 @@ __global__ __launch_bounds__(64 * WAVES) void seq_linear_kernel(SeqLinearArgs a)
         seq_group_mfma<NB, RT, 1>(ra, acc);
       }
       c += WAVES * nw;
-    }
-  } else if constexpr (WAVES == 4 && NB >= 3 && SEQ_RING > 1) {
-    constexpr int D = SEQ_RING, SU = SEQ_RING_U;   // D stages of SU chunks each
-    const int nw = c < nchunk ? (nchunk - c + WAVES - 1) / WAVES : 0;   // this wave's chunks
-    const int ns = nw / SU, n_main = ns - ns % D;                        // ... stages, and those the ring takes
-    if (n_main > 0) {
-      SeqGroupRegs<NB, RT, SU> ring[D];
-#pragma unroll
-      for (int dd = 0; dd < D - 1; ++dd) seq_group_load<NB, RT, SU, WAVES, LAY>(a, w, x, c + WAVES * SU * dd, ring[dd]);
-      int base = 0;
-      for (; base + D < n_main; base += D) {   // steady state: every stage requests the one D - 1 ahead of the one it multiplies
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          seq_group_load<NB, RT, SU, WAVES, LAY>(a, w, x, c + WAVES * SU * (base + dd + D - 1), ring[(dd + D - 1) % D]);
-          __builtin_amdgcn_sched_barrier(0);
-          seq_group_mfma<NB, RT, SU>(ring[dd], acc);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      // the last D stages: only the very last one is still to be requested
-      seq_group_load<NB, RT, SU, WAVES, LAY>(a, w, x, c + WAVES * SU * (n_main - 1), ring[D - 1]);
-#pragma unroll
-      for (int dd = 0; dd < D; ++dd) {
-        __builtin_amdgcn_sched_barrier(0);
-        seq_group_mfma<NB, RT, SU>(ring[dd], acc);
-      }
-      c += WAVES * SU * n_main;
     }
   }
   for (; c + WAVES * (UMAX - 1) < nchunk; c += WAVES * UMAX) seq_linear_group<NB, RT, UMAX, WAVES, LAY>(a, w, x, c, acc);

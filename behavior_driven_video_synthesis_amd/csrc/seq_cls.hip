@@ -87,8 +87,6 @@ __global__ __launch_bounds__(256) void cls_gather_kernel(const float* const* __r
   dst[g * dst_net + e] = v;
 }
 
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-
 __global__ __launch_bounds__(256) void cls_cell_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh,
                                                            float* __restrict__ gates, float* __restrict__ h, int R, int t, int64_t gi_net,
                                                            int64_t h_net) {

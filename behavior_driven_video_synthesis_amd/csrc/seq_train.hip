@@ -26,15 +26,9 @@
 
 namespace {
 
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
 __device__ __forceinline__ float comp4(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 
 // weights and moments are streamed: each byte is touched once per kernel by one workgroup
-#ifdef VUNET_SEQ_NO_NT   // (timing-ablation build, tools/ab_build.sh)
-#define SEQ_NT_LOAD(ptr) (*reinterpret_cast<const float4*>(ptr))
-#define SEQ_NT_STORE(ptr, val) (*reinterpret_cast<float4*>(ptr) = (val))
-#else
 typedef float seq_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 seq_nt_load(const float* p) {
   const seq_f4 t = __builtin_nontemporal_load(reinterpret_cast<const seq_f4*>(p));
@@ -44,9 +38,6 @@ __device__ __forceinline__ void seq_nt_store(float* p, const float4& v) {
   seq_f4 t = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(t, reinterpret_cast<seq_f4*>(p));
 }
-#define SEQ_NT_LOAD(ptr) seq_nt_load(ptr)
-#define SEQ_NT_STORE(ptr, val) seq_nt_store(ptr, val)
-#endif
 
 // ------------------------------------------------------------------------------------------------ dX = dZ . W
 struct SeqDxArgs {
@@ -82,105 +73,63 @@ __global__ __launch_bounds__(64 * WAVES) void seq_dx_kernel(SeqDxArgs a) {
   for (int e = 0; e < 4; ++e)
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) acc[e][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifndef SEQ_DX_RING
-#define SEQ_DX_RING 2
-#endif
-#ifndef SEQ_DX_RING_U
-#define SEQ_DX_RING_U 1
-#endif
-  constexpr int SU = (WAVES <= 8 && SEQ_DX_RING > 1) ? SEQ_DX_RING_U : 1;   // row groups per stage of the ring below
-  struct Stage {
-    float4 wv[SU][4], dv[SU][NB];
+  struct Stage {   // one 16-row group
+    float4 wv[4], dv[NB];
   };
-  auto load = [&](int g, auto nu_c, Stage& r) {
-    constexpr int NU = decltype(nu_c)::value;
+  auto load = [&](int g, Stage& r) {
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
+    for (int e2 = 0; e2 < 4; ++e2)
+      r.wv[e2] = *reinterpret_cast<const float4*>(w + (size_t)(16 * g + e2) * a.ldw);   // (default policy: the sweep re-reads W)
 #pragma unroll
-      for (int e2 = 0; e2 < 4; ++e2)
-        r.wv[u][e2] = *reinterpret_cast<const float4*>(w + (size_t)(16 * (g + WAVES * u) + e2) * a.ldw);   // (default policy: the sweep re-reads W)
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) r.dv[u][nb] = *reinterpret_cast<const float4*>(dz + (size_t)16 * nb * a.M + 16 * (g + WAVES * u));
-    }
+    for (int nb = 0; nb < NB; ++nb) r.dv[nb] = *reinterpret_cast<const float4*>(dz + (size_t)16 * nb * a.M + 16 * g);
   };
-  auto mfma = [&](auto nu_c, const Stage& r) {
-    constexpr int NU = decltype(nu_c)::value;
+  auto mfma = [&](const Stage& r) {
 #pragma unroll
-    for (int u = 0; u < NU; ++u)
+    for (int e2 = 0; e2 < 4; ++e2)
 #pragma unroll
-      for (int e2 = 0; e2 < 4; ++e2)
+      for (int e = 0; e < 4; ++e)
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            acc[e][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp4(r.wv[u][e2], e), comp4(r.dv[u][nb], e2), acc[e][nb], 0, 0, 0);
+        for (int nb = 0; nb < NB; ++nb)
+          acc[e][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp4(r.wv[e2], e), comp4(r.dv[nb], e2), acc[e][nb], 0, 0, 0);
   };
-  constexpr std::integral_constant<int, SU> su_c{};
-  constexpr std::integral_constant<int, 1> one_c{};
   int g = wave;
-  // Four- / eight-wave workgroups (48 - 64 batch rows) are one or two waves per SIMD: the wave keeps a ring of SEQ_DX_RING stages (of SEQ_DX_RING_U
-  // row groups) in flight, the loads of stage i + SEQ_DX_RING - 1 issued before the matrix steps of stage i (csrc/seq.hip:
-  // seq_linear_kernel's ring).  Same groups, same order, same sums as the plain loop below.
-  if constexpr (WAVES <= 8 && SEQ_DX_RING == 2 && SEQ_DX_RING_U == 1) {
+  // Four- / eight-wave workgroups (48 - 64 batch rows) are one or two waves per SIMD: the wave keeps a ring of two stages (of one
+  // row group) in flight, the loads of stage i + 1 issued before the matrix steps of stage i (csrc/seq.hip: seq_linear_kernel's
+  // ring).  Same groups, same order, same sums as the plain loop below.
+  if constexpr (WAVES <= 8) {
     // depth 2, any number of row groups (uneven slabs leave a wave 4 or 5 of them: the last one stays in the ring)
     const int nw = g < ngrp ? (ngrp - g + WAVES - 1) / WAVES : 0;
     if (nw > 0) {
       Stage ra, rb;
-      load(g, su_c, ra);
+      load(g, ra);
       int k = 0;
       for (; k + 2 < nw; k += 2) {   // ra holds group k
-        load(g + WAVES * (k + 1), su_c, rb);
+        load(g + WAVES * (k + 1), rb);
         __builtin_amdgcn_sched_barrier(0);
-        mfma(su_c, ra);
+        mfma(ra);
         __builtin_amdgcn_sched_barrier(0);
-        load(g + WAVES * (k + 2), su_c, ra);
+        load(g + WAVES * (k + 2), ra);
         __builtin_amdgcn_sched_barrier(0);
-        mfma(su_c, rb);
+        mfma(rb);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (nw - k == 2) {
-        load(g + WAVES * (k + 1), su_c, rb);
+        load(g + WAVES * (k + 1), rb);
         __builtin_amdgcn_sched_barrier(0);
-        mfma(su_c, ra);
+        mfma(ra);
         __builtin_amdgcn_sched_barrier(0);
-        mfma(su_c, rb);
+        mfma(rb);
       } else {
-        mfma(su_c, ra);
+        mfma(ra);
       }
       g += WAVES * nw;
-    }
-  } else if constexpr (WAVES <= 8 && SEQ_DX_RING > 1) {
-    constexpr int D = SEQ_DX_RING;
-    const int nw = g < ngrp ? (ngrp - g + WAVES - 1) / WAVES : 0;
-    const int ns = nw / SU, n_main = ns - ns % D;
-    if (n_main > 0) {
-      Stage ring[D];
-#pragma unroll
-      for (int dd = 0; dd < D - 1; ++dd) load(g + WAVES * SU * dd, su_c, ring[dd]);
-      int base = 0;
-      for (; base + D < n_main; base += D) {
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          load(g + WAVES * SU * (base + dd + D - 1), su_c, ring[(dd + D - 1) % D]);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma(su_c, ring[dd]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      load(g + WAVES * SU * (n_main - 1), su_c, ring[D - 1]);
-#pragma unroll
-      for (int dd = 0; dd < D; ++dd) {
-        __builtin_amdgcn_sched_barrier(0);
-        mfma(su_c, ring[dd]);
-      }
-      g += WAVES * SU * n_main;
     }
   }
   for (; g < ngrp; g += WAVES) {
     Stage r;
-    load(g, one_c, r);
+    load(g, r);
     __builtin_amdgcn_sched_barrier(0);
-    mfma(one_c, r);
+    mfma(r);
   }
   // the waves' partial sums meet in LDS, one batch tile per round; waves 0..3 (thread t: r = t >> 6) add them in wave order
   float* out = a.raw + ((size_t)net * a.S + s) * a.Bp * a.K;
@@ -388,11 +337,8 @@ __global__ __launch_bounds__(256) void seq_dw_kernel(const vunet_seq_dw_layer* _
     for (int r = 0; r < 4; ++r) dws[dw_swo(16 * wave + 4 * q + r, 16 * blk + i)] = acc[blk][r];
   __syncthreads();
   // the tile leaves in rounds of GRP float4 per thread: the round's W / exp_avg / exp_avg_sq requested together, then updated and
-  // stored (-DSEQ_DW_GRP=1: one float4 at a time, =4: the whole tile at once -- 140 registers, three workgroups per CU)
-#ifndef SEQ_DW_GRP
-#define SEQ_DW_GRP 2
-#endif
-  constexpr int GRP = ADAM ? SEQ_DW_GRP : 1;
+  // stored (two per round; four, the whole tile at once, took 140 registers -- three workgroups per CU)
+  constexpr int GRP = ADAM ? 2 : 1;
 #pragma unroll
   for (int it0 = 0; it0 < 4; it0 += GRP) {
     float4 g[GRP], p[GRP], m[GRP], v[GRP];
@@ -403,9 +349,9 @@ __global__ __launch_bounds__(256) void seq_dw_kernel(const vunet_seq_dw_layer* _
       off[u] = (size_t)(m0 + row) * L.K + k0 + 4 * c4;
       if constexpr (ADAM) {
         // (each of these bytes is touched once per step: keep them out of the L2 that holds the operand rows)
-        p[u] = SEQ_NT_LOAD(L.w + off[u]);
-        m[u] = SEQ_NT_LOAD(L.m + off[u]);
-        v[u] = SEQ_NT_LOAD(L.v + off[u]);
+        p[u] = seq_nt_load(L.w + off[u]);
+        m[u] = seq_nt_load(L.m + off[u]);
+        v[u] = seq_nt_load(L.v + off[u]);
       }
       g[u] = *reinterpret_cast<const float4*>(&dws[dw_swo(row, 4 * c4)]);
       if (k0 + 4 * c4 + 3 >= L.kv) {   // (padding columns of the image: only where K is not the layer's own width)
@@ -423,9 +369,9 @@ __global__ __launch_bounds__(256) void seq_dw_kernel(const vunet_seq_dw_layer* _
         adam_update(h, g[u].y, p[u].y, m[u].y, v[u].y);
         adam_update(h, g[u].z, p[u].z, m[u].z, v[u].z);
         adam_update(h, g[u].w, p[u].w, m[u].w, v[u].w);
-        SEQ_NT_STORE(L.w + off[u], p[u]);
-        SEQ_NT_STORE(L.m + off[u], m[u]);
-        SEQ_NT_STORE(L.v + off[u], v[u]);
+        seq_nt_store(L.w + off[u], p[u]);
+        seq_nt_store(L.m + off[u], m[u]);
+        seq_nt_store(L.v + off[u], v[u]);
       } else {
         *reinterpret_cast<float4*>(L.g + off[u]) = g[u];
       }
@@ -527,15 +473,15 @@ __global__ __launch_bounds__(256) void seq_dwx_kernel(const vunet_seq_dw_layer* 
       }
       const size_t off = (size_t)(m0 + row) * L.K + k0 + 4 * c4;
       if constexpr (ADAM) {
-        float4 p = SEQ_NT_LOAD(L.w + off), m = SEQ_NT_LOAD(L.m + off), v = SEQ_NT_LOAD(L.v + off);
+        float4 p = seq_nt_load(L.w + off), m = seq_nt_load(L.m + off), v = seq_nt_load(L.v + off);
         pold[it] = p;
         adam_update(h, g.x, p.x, m.x, v.x);
         adam_update(h, g.y, p.y, m.y, v.y);
         adam_update(h, g.z, p.z, m.z, v.z);
         adam_update(h, g.w, p.w, m.w, v.w);
-        SEQ_NT_STORE(L.w + off, p);
-        SEQ_NT_STORE(L.m + off, m);
-        SEQ_NT_STORE(L.v + off, v);
+        seq_nt_store(L.w + off, p);
+        seq_nt_store(L.m + off, m);
+        seq_nt_store(L.v + off, v);
       } else {
         pold[it] = L.dx_raw ? *reinterpret_cast<const float4*>(L.w + off) : make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4*>(L.g + off) = g;

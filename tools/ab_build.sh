@@ -1,7 +1,8 @@
 #!/bin/bash
-# Build a variant of libvunet_hip.so for A/B timing of kernel changes without touching the shipped library:
+# Build a variant of libvunet_hip.so beside the shipped library (a timestamp build for the timeline tools, or an edited
+# source for A/B timing of a kernel change):
 #     tools/ab_build.sh <tag> <source.hip> [extra hipcc flags ...]
-# recompiles ONE source with the extra flags (e.g. -DH2_NO_TAP_BARRIER) and links it with the shipped objects of all the
+# recompiles ONE source with the extra flags (e.g. -DH2_TSTAMP=vunet_debug_h2_ts) and links it with the shipped objects of all the
 # others into behavior_driven_video_synthesis_amd/build/libvunet_hip_<tag>.so.  Use:  VUNET_HIP_LIB=<that path> python tools/time_conv.py
 set -eu
 TAG=$1; SRC=$2; shift 2

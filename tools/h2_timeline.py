@@ -10,7 +10,6 @@ import ctypes
 import os
 import sys
 
-os.environ.setdefault("VUNET_ALLOW_TIMING_BUILD", "1")
 import numpy as np
 import torch
 

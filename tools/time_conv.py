@@ -9,8 +9,6 @@ import ctypes
 import os
 import sys
 
-os.environ.setdefault("VUNET_ALLOW_TIMING_BUILD", "1")   # A/B libraries of tools/ab_build.sh may be timing-only builds
-
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
