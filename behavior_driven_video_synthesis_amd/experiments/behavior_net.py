@@ -194,7 +194,7 @@ class BehaviorNet:
     # ---- scoring (experiments/behavior_net.py:1112-1301, lib/logging.py:2079-2093)
     @torch.no_grad()
     def evaluate(self, batches, stats, n_samples: int = 50, skip: int = 4, use_flow: bool = True, z=None, eps=None,
-                 classifier_study: bool = False, study_kwargs=None, study_noise=None):
+                 classifier_study: bool = False, study_kwargs=None, study_noise=None, euler=None):
         """The reference's per-batch metric recipe of ``run_inference`` over an iterable of dict batches -> a
         ``behavior_eval.BehaviorEvaluator`` (``.summary()``: the means the reference prints; ``.lists()``: the lists).
 
@@ -215,9 +215,20 @@ class BehaviorNet:
         X_cross / X_self = generate_seq(mu, x_t / x_s) from frame 0, X_flow = generate_seq(flow.reverse(noise), target_s) from
         frame T - 1 (with the flow), X_embed = mu; the batch after the cap is still scored, then the loop ends.  After the loop
         ``behavior_eval.classifier_study`` runs on what was collected (the other ``study_kwargs``) and its result is
-        ``ev.study``.  ``study_noise``: per batch (or one for all) {"prior": [B, H], "flow": [B, H]} (None: drawn)."""
+        ``ev.study``.  ``study_noise``: per batch (or one for all) {"prior": [B, H], "flow": [B, H]} (None: drawn).
+
+        ``euler`` (a model trained on ``keypoint_type: angle_world_expmap``): ``(stats, horizons)`` or ``(stats, horizons, actions,
+        max_len)`` with ``stats`` a ``pose_angles.AngleStats``.  Every batch's reconstruction ``net(x_s, x_s, T)`` (``eps``, when
+        given, is its noise too) is scored against ``target_s`` with ``pose_angles.euler_error`` (``mse_euler``, lib/metrics.py:321-357)
+        into ``ev.euler``, a ``pose_angles.EulerErrorTable``: per action -- the batch's optional ``actions``, one name per row;
+        without it every row counts as ``"all"`` -- and horizon.  None: nothing of this runs."""
         from .. import behavior_eval as E
         ev = E.BehaviorEvaluator()
+        if euler is not None:
+            import sys
+            from .. import pose_angles as A
+            angle_stats, horizons = euler[0], euler[1]
+            ev.euler = A.EulerErrorTable(euler[2] if len(euler) > 2 else None, horizons, euler[3] if len(euler) > 3 else sys.maxsize)
         flow = self.latent_flow if use_flow else None
         kw = dict(study_kwargs or {})
         study = E.StudySet(kw.pop("max_rows", 25000)) if classifier_study else None
@@ -231,6 +242,9 @@ class BehaviorNet:
             zb = z[bi] if isinstance(z, (list, tuple)) else z
             samples = E.sample_behaviors(self.net, flow, target_s[::skip].contiguous(), n_samples, t, start_frame=t - 1, z=zb)
             ev.add(E.sample_metrics(samples, fut, stats))
+            if euler is not None:
+                rec = self.net(x_s, x_s, t, eps=eps[bi] if isinstance(eps, (list, tuple)) else eps)[0]
+                ev.euler.add(A.euler_error(rec, target_s, angle_stats, horizons), batch.get("actions") or ["all"] * x_s.shape[0])
             if study is not None:
                 if study.full:
                     break

@@ -155,6 +155,50 @@ class PoseCamera:
         return kps
 
 
+class AnglePoseCamera:
+    """``PoseCamera`` for a model trained on ``keypoint_type: angle_world_expmap``: its pose vectors are a root translation and
+    exponential-map joint rotations, not joint positions, so between the un-normalisation and the camera sits the forward
+    kinematics over ``tree`` (a ``pose_angles.KinematicTree`` or the dict the reference's dataset holds), as the reference's
+    ``convert_to_3d`` in front of its plots and videos (data/data_conversions_3d.py:1047-1066; ``swap_yz`` is its flag).  Two
+    launches: un-normalise + kinematics (csrc/pose_angles.hip), then the projection kernel ``PoseCamera`` uses, on the 3-D joints."""
+
+    def __init__(self, data_mean, data_std, dim_to_use, tree, extrinsics, intrinsics, image_size, spatial_size, swap_yz=False,
+                 device="cuda"):
+        import numpy as np
+        from .pose_angles import AngleStats, KinematicTree
+        self.stats = AngleStats.from_dim_to_use(data_mean, data_std, dim_to_use, device=device)
+        self.tree = KinematicTree.of(tree, device)
+        self.n_use, self.dim, self.swap_yz = self.stats.n_use, self.stats.dim, bool(swap_yz)
+        j3 = 3 * self.tree.n_joints
+        # the projection kernel un-normalises what it reads: identity statistics over the 3 J coordinates leave them as they are
+        self._dims = torch.arange(j3, dtype=torch.int32, device=device)
+        self._zero = torch.zeros(j3, dtype=torch.float64, device=device)
+        self._one = torch.ones(j3, dtype=torch.float64, device=device)
+        ext = np.asarray(extrinsics, dtype=np.float64).reshape(3, 4)
+        fx, x0, fy, y0 = [float(v) for v in intrinsics]
+        scale = [float(spatial_size) / float(image_size[0]), float(spatial_size) / float(image_size[1])]
+        self.cam = torch.as_tensor(np.concatenate([ext.reshape(-1), [fx, x0, fy, y0], scale]), device=device)
+        self.spatial_size = int(spatial_size)
+
+    def joints(self, poses: torch.Tensor) -> torch.Tensor:
+        """[T, n_use] decoded (normalised) pose vectors -> [T, J, 3] world joint positions."""
+        from .pose_angles import convert_to_3d
+        ops._dev(poses)
+        x = poses.reshape(-1, poses.shape[-1])
+        if x.shape[1] != self.n_use:
+            raise ValueError(f"pose vectors of {self.n_use} used dimensions expected, got {tuple(poses.shape)}")
+        return convert_to_3d(x, self.tree, self.swap_yz, stats=self.stats)
+
+    def project(self, poses: torch.Tensor) -> torch.Tensor:
+        """[T, n_use] decoded (normalised) pose vectors -> [T, J, 2] pixel keypoints at the synthesis resolution."""
+        xyz = self.joints(poses)
+        t, j = xyz.shape[0], xyz.shape[1]
+        kps = torch.empty(t, j, 2, device=xyz.device, dtype=torch.float32)
+        ops._call("vunet_seq_pose_project", ops._p(xyz), 3 * j, ops._p(self._dims), ops._p(self._zero), ops._p(self._one), 3 * j, 0,
+                  ops._p(self.cam), ops._p(kps), t, j, ops._stream())
+        return kps
+
+
 @torch.no_grad()
 def behavior_video(flow, net, vunet, app_img: torch.Tensor, start_poses: torch.Tensor, length: int, camera: PoseCamera,
                    z: Optional[torch.Tensor] = None, start_frame: int = -1, joint_model=H36M_JOINT_MODEL, dtype: str = "bf16",
