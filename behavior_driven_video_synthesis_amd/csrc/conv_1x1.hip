@@ -15,7 +15,7 @@
 // epilogue  y = acc * act'(aux) + res  (store_out, shared with the other kernels).
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_route.h"
 
 template <int MT, int MODE, int PRO>
 __global__ __launch_bounds__(256, 3) void conv_1x1_kernel(const GatherArgs a_in, const int ntiles, const int tiles_per_img) {
@@ -143,15 +143,11 @@ bool vunet_conv_1x1_applicable(const vunet_conv_desc* d, int pro) {
 // m-tiles per workgroup: all of M (x is then read once) unless that leaves the chip short of workgroups -- the 128-channel
 // layers of the 32^2 / 64^2 levels are 128 / 512 workgroups of four chunk-serial steps each (56 us for 0.5 GFLOP at 32^2,
 // r03); with fewer m-tiles per workgroup x is re-read from L2, which at these sizes costs nothing
-static int mt_of(const vunet_conv_desc* d) {
+int vunet_conv_1x1_mt(const vunet_conv_desc* d) {
   int MT = d->M <= 32 ? 1 : d->M <= 64 ? 2 : 4;
   const long groups = ((long)d->N * d->Hs * d->Ws / 32 + 3) / 4;
   while (MT > 1 && groups * ((d->M + 32 * MT - 1) / (32 * MT)) < 1024) MT >>= 1;
   return MT;
-}
-
-int vunet_conv_1x1_name(const vunet_conv_desc* d, int pro, char* name, int len) {
-  return snprintf(name, len, "conv_1x1_kernel<%d, %d, %d>", mt_of(d), d->mode, d->mode == 1 ? 0 : pro);
 }
 
 template <int MT, int MODE>
@@ -173,8 +169,8 @@ static int launch_1x1(const GatherArgs& ga, int pro, hipStream_t st) {
   return vunet_check_launch();
 }
 
-int vunet_conv_1x1_launch(const GatherArgs& ga, int pro, hipStream_t st) {
-  const int MT = mt_of(&ga.d);
+int vunet_conv_1x1_launch(const ConvRoute& r, const GatherArgs& ga, hipStream_t st) {
+  const int MT = r.MT, pro = r.pro;
   if (ga.d.mode == 1) return MT == 1 ? launch_1x1<1, 1>(ga, pro, st) : MT == 2 ? launch_1x1<2, 1>(ga, pro, st) : launch_1x1<4, 1>(ga, pro, st);
   return MT == 1 ? launch_1x1<1, 0>(ga, pro, st) : MT == 2 ? launch_1x1<2, 0>(ga, pro, st) : launch_1x1<4, 0>(ga, pro, st);
 }

@@ -396,8 +396,26 @@ __device__ __forceinline__ void store_tile16(const GatherArgs& a, const PixGeo& 
   if (a.amax_out) publish_amax(a, vmax);   // (wave-uniform branch; the 1x1 / LDS-tiled kernels publish through here)
 }
 
-// vunet_conv2d_gather with the optional |y| maxima output: set for the kernels that publish (1x1, LDS-tiled), ignored by
-// the others -- vunet_conv2d_publishes_amax tells the caller which it will be
-int vunet_conv2d_gather_amax(const vunet_conv_desc* d, const float* x1, const float* x2, const float* wt, const float* shift,
-                             const float* res, const float* aux, float* y, float* amax_out, void* stream);
-bool vunet_conv2d_gather_publishes(const vunet_conv_desc* d, bool has_aux, bool has_res);
+// Host: the launch arguments of one problem.  `wide_geometry` is the caller's own rule for the 16-byte epilogue (which
+// pixels its tiles walk); alignment of y / res / aux and the depth-to-space store are checked here.  amax_out, amax2 and
+// res2 start unset.
+static inline void fill_gather_args(GatherArgs& ga, const vunet_conv_desc* d, const float* x1, const float* x2, const float* wt,
+                                    const float* shift, const float* res, const float* aux, const float* mask, float* y,
+                                    bool wide_geometry) {
+  ga.d = *d;
+  ga.x1 = x1; ga.x2 = x2; ga.wt = wt; ga.shift = shift; ga.res = res; ga.aux = aux; ga.y = y;
+  ga.NP = d->N * d->Ho * d->Wo;
+  ga.HoWo = d->Ho * d->Wo;
+  ga.HsWs = d->Hs * d->Ws;
+  ga.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
+  ga.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
+  ga.auxa = make_inact(d->aux_act, d->aux_slope, d->aux_drop_p, d->aux_drop_seed);
+  ga.ph = ga.pw = -1;
+  ga.subW = ga.subHW = 0;
+  ga.mask = mask;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(aux);
+  ga.wide = wide_geometry && (al & 15) == 0 && !d->d2s;
+  ga.amax_out = nullptr;
+  ga.amax2 = nullptr;
+  ga.res2 = nullptr;
+}

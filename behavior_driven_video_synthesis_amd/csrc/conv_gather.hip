@@ -18,7 +18,7 @@
 // tiles, long K) go to the split-K variant: 16 waves of one workgroup share one 32x32 output tile,
 // each sums a strided subset of the channel pairs, partial tiles are reduced through LDS in a fixed
 // order (deterministic).
-#include "conv_common.h"
+#include "conv_route.h"
 
 // per-lane geometry of one 32-pixel tile: source base offsets and the tap validity bits
 struct TileGeo {
@@ -320,120 +320,21 @@ static int launch_splitk(const GatherArgs& ga, int pro, hipStream_t st) {
   return vunet_check_launch();
 }
 
-// Few output tiles and a long K: share each tile's K loop between 16 waves.  Up to 768 tiles (3 per CU) any layer
-// with >= 64 input channels; up to 2048 tiles only when K is at least 576 deep (3x3 over >= 64 channels) -- there
-// the one-wave-per-tile kernel is latency bound (25 x 256->128 @ 16^2: 582 us vs ~60 us split).
-static bool want_splitk(long ntiles, long mtiles, int kpairs, int taps) {
-  const long tiles = ntiles * mtiles;
-  return (tiles <= 768 && kpairs >= 32) || (tiles <= 2048 && (long)kpairs * taps >= 288);
-}
-
+// CONV_SPLITK / CONV_GATHER as conv_route_gather_form picked them
 template <int KS>
-static int dispatch_gather(const GatherArgs& ga_in, int pro, hipStream_t st, float* amax_out = nullptr) {
-  GatherArgs ga = ga_in;
-  const vunet_conv_desc& d = ga.d;
-  const int ntiles = (ga.NP + 31) / 32, mtiles = (d.M + 31) / 32;
-  const int kpairs = (((d.C1 + 1) >> 1) + ((d.C2 + 1) >> 1));
-  if (want_splitk(ntiles, mtiles, kpairs, d.KH * d.KW)) {
-    ga.amax_out = amax_out;   // the split-K kernel publishes |y| maxima (the others of this dispatcher do not)
-    return launch_splitk<KS>(ga, pro, st);
-  }
-  if (d.M <= 32) return launch_gather<1, 4, KS>(ga, pro, st);
-  return launch_gather<2, 2, KS>(ga, pro, st);
-}
-
-static bool gather_uses_splitk(const vunet_conv_desc* d) {
-  const long ntiles = ((long)d->N * d->Ho * d->Wo + 31) / 32, mtiles = (d->M + 31) / 32;
-  const int kpairs = ((d->C1 + 1) >> 1) + ((d->C2 + 1) >> 1);
-  return want_splitk(ntiles, mtiles, kpairs, d->KH * d->KW);
-}
-
-// conv_tiled.hip: LDS-tiled kernel for the 3x3 / stride-1 layers on maps at least 32 wide
-bool vunet_conv_tiled_applicable(const vunet_conv_desc* d);
-int vunet_conv_tiled_pick(const vunet_conv_desc* d, int* MT, bool valu_heavy);
-int vunet_conv_tiled_launch(const GatherArgs& ga, int pro, hipStream_t st);
-
-int vunet_conv_tiled_name(const vunet_conv_desc* d, int pro, bool has_aux, char* name, int len);
-
-// conv_thin.hip: VALU kernels for the layers with <= 4 channels on one side
-int vunet_conv_thin_kind(const vunet_conv_desc* d, int pro, bool has_aux, bool has_res);
-int vunet_conv_thin_launch(const GatherArgs& ga, int kind, hipStream_t st);
-int vunet_conv_thin_name(const vunet_conv_desc* d, int kind, char* name, int len);
-
-// conv_1x1.hip: streaming kernel for the 1x1 / stride-1 layers
-bool vunet_conv_1x1_applicable(const vunet_conv_desc* d, int pro);
-int vunet_conv_1x1_launch(const GatherArgs& ga, int pro, hipStream_t st);
-int vunet_conv_1x1_name(const vunet_conv_desc* d, int pro, char* name, int len);
-
-VUNET_ENV_FLAG(env_no_tiled, "VUNET_NO_TILED")
-VUNET_ENV_FLAG(env_no_phase, "VUNET_NO_PHASE")
-
-static int prologue_code(const vunet_conv_desc* d) {
-  if (d->in_act == ACT_NONE && d->drop_p <= 0.f) return 0;
-  if (d->in_act == ACT_ELU && d->drop_p <= 0.f) return 1;
-  if (d->in_act == ACT_ELU) return 2;
-  return 3;
-}
-
-// the streaming 1x1 kernel, unless the problem is so small that splitting K over 16 waves is the better plan
-static bool use_1x1(const vunet_conv_desc* d, int pro) {
-  const long ntiles = ((long)d->N * d->Ho * d->Wo + 31) / 32, mtiles = (d->M + 31) / 32;
-  const int kpairs = ((d->C1 + 1) >> 1) + ((d->C2 + 1) >> 1);
-  return vunet_conv_1x1_applicable(d, pro) && !want_splitk(ntiles, mtiles, kpairs, 1);
-}
-
-static bool use_tiled(const vunet_conv_desc* d, int pro) {
-  int mt_unused;
-  return !env_no_tiled() && vunet_conv_tiled_applicable(d) &&
-         (d->mode == 0 ? pro != 4 : (pro == 0 || (pro == 4 && d->stride == 1))) && pro != 3 &&
-         vunet_conv_tiled_pick(d, &mt_unused, true) > 0;
-}
-
-// Name (rocprofv3 spelling) of the kernel vunet_conv2d_gather would launch for this problem.
-extern "C" int vunet_conv2d_gather_variant(const vunet_conv_desc* d, int32_t has_aux, char* name, int32_t len) {
-  if (!d || !name || len < 8) return VUNET_ERR_ARG;
-  const int pro = prologue_code(d);
-  if (d->mode == 1 && d->stride > 1 && !env_no_phase()) {
-    snprintf(name, len, "conv_gather_kernel<phase x%d>", d->stride * d->stride);
-    return VUNET_OK;
-  }
-  if (const int thin = vunet_conv_thin_kind(d, pro, has_aux != 0, false)) {
-    vunet_conv_thin_name(d, thin, name, len);
-    return VUNET_OK;
-  }
-  if (use_1x1(d, pro)) {
-    vunet_conv_1x1_name(d, pro, name, len);
-    return VUNET_OK;
-  }
-  if (use_tiled(d, pro)) {
-    vunet_conv_tiled_name(d, pro, has_aux != 0, name, len);
-    return VUNET_OK;
-  }
-  const int KS = (d->KH == 3 && d->KW == 3) ? 3 : ((d->KH == 1 && d->KW == 1) ? 1 : 0);
-  const long ntiles = ((long)d->N * d->Ho * d->Wo + 31) / 32, mtiles = (d->M + 31) / 32;
-  const int kpairs = ((d->C1 + 1) >> 1) + ((d->C2 + 1) >> 1);
-  if (want_splitk(ntiles, mtiles, kpairs, d->KH * d->KW)) snprintf(name, len, "conv_gather_splitk_kernel<16, %d, %d>", pro, KS);
-  else if (d->M <= 32) snprintf(name, len, "conv_gather_kernel<1, 4, %d, %d>", pro, KS);
-  else snprintf(name, len, "conv_gather_kernel<2, 2, %d, %d>", pro, KS);
-  return VUNET_OK;
+static int launch_form(const GatherArgs& ga, int family, int MT, int pro, hipStream_t st) {
+  if (family == CONV_SPLITK) return launch_splitk<KS>(ga, pro, st);
+  return MT == 1 ? launch_gather<1, 4, KS>(ga, pro, st) : launch_gather<2, 2, KS>(ga, pro, st);
 }
 
 extern "C" int vunet_conv2d_gather(const vunet_conv_desc* d, const float* x1, const float* x2, const float* wt,
-                                   const float* shift, const float* res, const float* aux, float* y,
-                                   void* stream) {
+                                   const float* shift, const float* res, const float* aux, float* y, void* stream) {
   return vunet_conv2d_gather_amax(d, x1, x2, wt, shift, res, aux, y, nullptr, stream);
 }
 
-// kernels of this dispatcher whose epilogue publishes |y| maxima (store_tile16): the streaming 1x1 and the LDS-tiled one
-bool vunet_conv2d_gather_publishes(const vunet_conv_desc* d, bool has_aux, bool has_res) {
-  if (d->d2s || (d->mode == 1 && d->stride > 1 && !env_no_phase())) return false;
-  const int pro = prologue_code(d);
-  if (const int thin = vunet_conv_thin_kind(d, pro, has_aux, has_res)) return thin == 2;   // the 3-channel-input kernel publishes
-  return use_1x1(d, pro) || use_tiled(d, pro) || gather_uses_splitk(d);
-}
-
 int vunet_conv2d_gather_amax(const vunet_conv_desc* d, const float* x1, const float* x2, const float* wt, const float* shift,
-                             const float* res, const float* aux, float* y, float* amax_out, void* stream) {
+                             const float* res, const float* aux, float* y, float* amax_out, void* stream,
+                             const ConvRoute* route) {
   if (!d || !x1 || !wt || !y) return VUNET_ERR_ARG;
   if (d->N <= 0 || d->C1 <= 0 || d->C2 < 0 || d->M <= 0 || d->KH <= 0 || d->KW <= 0 || d->KH > 8 || d->KW > 8 ||
       d->stride <= 0 || d->Mpad % 32 != 0)
@@ -444,63 +345,43 @@ int vunet_conv2d_gather_amax(const vunet_conv_desc* d, const float* x1, const fl
   const int64_t out_elems = (int64_t)d->N * d->M * d->Ho * d->Wo;
   if (in_elems >= (1ll << 31) || out_elems >= (1ll << 31)) return VUNET_ERR_UNSUPPORTED;
 
+  const ConvRoute r = route ? *route : conv_route(d, 0, aux != nullptr, res != nullptr, false, 0, false);
   GatherArgs ga;
-  ga.wide = 0;
-  ga.amax_out = nullptr;
-  ga.res2 = nullptr;
-  ga.amax2 = nullptr;
-  ga.d = *d;
-  ga.x1 = x1; ga.x2 = x2; ga.wt = wt; ga.shift = shift; ga.res = res; ga.aux = aux; ga.y = y;
-  ga.NP = d->N * d->Ho * d->Wo;
-  ga.HoWo = d->Ho * d->Wo;
-  ga.HsWs = d->Hs * d->Ws;
-  ga.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
-  ga.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
-  ga.auxa = make_inact(d->aux_act, d->aux_slope, d->aux_drop_p, d->aux_drop_seed);
-  const int pro = prologue_code(d);
-  ga.ph = ga.pw = -1;
-  ga.subW = ga.subHW = 0;
-  ga.mask = nullptr;
+  // 16-byte epilogue (conv_common.h: store_tile_side4), the 1x1 kernel only: a 32-pixel tile is 8 aligned groups of 4
+  // consecutive pixels
+  fill_gather_args(ga, d, x1, x2, wt, shift, res, aux, nullptr, y, r.family == CONV_1X1 && (d->Ho * d->Wo) % 32 == 0);
+  if (r.publishes) ga.amax_out = amax_out;
   hipStream_t st = (hipStream_t)stream;
-  if (d->mode == 1 && d->stride > 1 && !env_no_phase()) {
-    // strided data gradient: one launch per output parity, each visiting only its own taps
-    const int s = d->stride;
-    for (int ph = 0; ph < s; ++ph)
-      for (int pw = 0; pw < s; ++pw) {
-        GatherArgs gp = ga;
-        gp.ph = ph;
-        gp.pw = pw;
-        const int subH = (d->Ho - ph + s - 1) / s;
-        gp.subW = (d->Wo - pw + s - 1) / s;
-        gp.subHW = subH * gp.subW;
-        gp.NP = d->N * gp.subHW;
-        if (gp.NP <= 0) continue;
-        const int rc = dispatch_gather<0>(gp, pro, st);
-        if (rc != VUNET_OK) return rc;
-      }
-    return VUNET_OK;
+  switch (r.family) {
+    case CONV_PHASE: {   // strided data gradient: one launch per output parity, each visiting only its own taps
+      const int s = d->stride;
+      for (int ph = 0; ph < s; ++ph)
+        for (int pw = 0; pw < s; ++pw) {
+          GatherArgs gp = ga;
+          gp.ph = ph, gp.pw = pw;
+          const int subH = (d->Ho - ph + s - 1) / s;
+          gp.subW = (d->Wo - pw + s - 1) / s;
+          gp.subHW = subH * gp.subW;
+          gp.NP = d->N * gp.subHW;
+          if (gp.NP <= 0) continue;
+          int MT, NT;
+          const int family = conv_route_gather_form(d, gp.NP, &MT, &NT);
+          const int rc = launch_form<0>(gp, family, MT, r.pro, st);
+          if (rc != VUNET_OK) return rc;
+        }
+      return VUNET_OK;
+    }
+    case CONV_THIN: return vunet_conv_thin_launch(r, ga, st);
+    case CONV_1X1: return vunet_conv_1x1_launch(r, ga, st);
+    case CONV_TILED: return vunet_conv_tiled_launch(r, ga, st);
+    case CONV_GATHER:
+    case CONV_SPLITK:
+      if (r.form == 3) return launch_form<3>(ga, r.family, r.MT, r.pro, st);
+      if (r.form == 1) return launch_form<1>(ga, r.family, r.MT, r.pro, st);
+      return launch_form<0>(ga, r.family, r.MT, r.pro, st);
+    default: return VUNET_ERR_UNSUPPORTED;
   }
-  if (const int thin = vunet_conv_thin_kind(d, pro, aux != nullptr, res != nullptr)) {
-    if (thin == 2) ga.amax_out = amax_out;
-    return vunet_conv_thin_launch(ga, thin, st);
-  }
-  if (!d->d2s) ga.amax_out = amax_out;   // read by the two kernels below only
-  if (use_1x1(d, pro)) {
-    // 16-byte epilogue (conv_common.h: store_tile_side4): a 32-pixel tile is 8 aligned groups of 4 consecutive pixels
-    const uintptr_t al = reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(aux);
-    ga.wide = (al & 15) == 0 && !d->d2s && (d->Ho * d->Wo) % 32 == 0;
-    return vunet_conv_1x1_launch(ga, pro, st);
-  }
-  if (use_tiled(d, pro)) return vunet_conv_tiled_launch(ga, pro, st);
-  float* const amax_keep = ga.amax_out;
-  ga.amax_out = nullptr;
-  ga.res2 = nullptr;
-  ga.amax2 = nullptr;
-  if (d->KH == 3 && d->KW == 3) return dispatch_gather<3>(ga, pro, st, amax_keep);
-  if (d->KH == 1 && d->KW == 1) return dispatch_gather<1>(ga, pro, st, amax_keep);
-  return dispatch_gather<0>(ga, pro, st, amax_keep);
 }
-
 
 // Data gradient through a layer whose forward epilogue was ReLU:  dx = dgrad(dy * [y > 0]) (+ res), the mask applied
 // while dy is staged -- no separate pass over dy / y.  Only the LDS-tiled kernel implements it; every other geometry
@@ -508,22 +389,13 @@ int vunet_conv2d_gather_amax(const vunet_conv_desc* d, const float* x1, const fl
 extern "C" int vunet_conv2d_dgrad_relu(const vunet_conv_desc* d, const float* dy, const float* y, const float* wt,
                                        const float* res, float* dx, void* stream) {
   if (!d || !dy || !y || !wt || !dx || d->mode != 1 || d->C2 != 0 || d->Mpad % 32 != 0) return VUNET_ERR_ARG;
-  if (d->drop_p > 0.f || d->in_act != ACT_NONE || d->aux_act != ACT_NONE || d->aux_drop_p > 0.f || !use_tiled(d, 4) ||
+  ConvRoute r;
+  if (d->drop_p > 0.f || d->in_act != ACT_NONE || d->aux_act != ACT_NONE || d->aux_drop_p > 0.f ||
+      !conv_route_tiled(d, 4, false, &r) ||
       vunet_conv_thin_kind(d, 0, false, res != nullptr) != 0)   // 3-channel side: the two-pass route ends in the VALU kernel
     return VUNET_ERR_UNSUPPORTED;
   GatherArgs ga;
-  ga.wide = 0;
-  ga.amax_out = nullptr;
-  ga.res2 = nullptr;
-  ga.amax2 = nullptr;
-  ga.d = *d;
-  ga.x1 = dy; ga.x2 = nullptr; ga.wt = wt; ga.shift = nullptr; ga.res = res; ga.aux = nullptr; ga.y = dx;
-  ga.NP = d->N * d->Ho * d->Wo;
-  ga.HoWo = d->Ho * d->Wo;
-  ga.HsWs = d->Hs * d->Ws;
+  fill_gather_args(ga, d, dy, nullptr, wt, nullptr, res, nullptr, y, dx, false);
   ga.in1 = ga.in2 = ga.auxa = make_inact(ACT_NONE, 0.f, 0.f, 0u);
-  ga.ph = ga.pw = -1;
-  ga.subW = ga.subHW = 0;
-  ga.mask = y;
-  return vunet_conv_tiled_launch(ga, 4, (hipStream_t)stream);
+  return vunet_conv_tiled_launch(r, ga, (hipStream_t)stream);
 }

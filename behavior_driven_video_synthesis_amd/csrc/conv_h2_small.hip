@@ -24,7 +24,7 @@
 // image in L2 (a wave reads 1 KiB contiguous per fragment: the image IS the fragment layout).
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_route.h"
 #include "split_h2.h"
 
 struct SmallGeo {
@@ -376,10 +376,9 @@ bool vunet_conv_h2_small_wanted(const vunet_conv_desc* d, int pro) {
 }
 
 template <int PRO>
-static int small_launch_pro(const GatherArgs& ga, const void* wx, int mtp, const float* amax, const SmallGeo& sg,
+static int small_launch_pro(const GatherArgs& ga, const void* wx, int mtp, const float* amax, const SmallGeo& sg, int NR,
                             hipStream_t st) {
-  const int nr = (2 * sg.smax + 63) / 64;
-  const int nwv = nr > 3 ? 4 : 8;
+  const int nwv = NR > 3 ? 4 : 8;
   const size_t lds_stage = (size_t)nwv * 4 * (sg.smax + 1) * 16, lds_red = (size_t)nwv * 16 * 64 * 4;
   const size_t lds = lds_stage > lds_red ? lds_stage : lds_red;
   const dim3 grid((unsigned)(sg.ntile * (ga.d.M / 32))), block(64 * nwv);
@@ -396,30 +395,30 @@ static int small_launch_pro(const GatherArgs& ga, const void* wx, int mtp, const
     }                                                                                                                \
     VUNET_LAUNCH(kern, grid, block, lds, st, ga, (const uint4*)wx, mtp, amax, sg);                                   \
   } while (0)
-  if (nr <= 1) SM_LAUNCH(1);
-  else if (nr <= 2) SM_LAUNCH(2);
-  else if (nr <= 3) SM_LAUNCH(3);
+  if (NR == 1) SM_LAUNCH(1);
+  else if (NR == 2) SM_LAUNCH(2);
+  else if (NR == 3) SM_LAUNCH(3);
   else SM_LAUNCH(5);
 #undef SM_LAUNCH
   return vunet_check_launch();
 }
 
-int vunet_conv_h2_small_launch(const GatherArgs& ga, const void* wx, int mtiles_pad, const float* amax, int pro,
+// the kernel's NR (staged slots per lane, rounded up to a built form); 0: the geometry gives no staging bound
+int vunet_conv_h2_small_nr(const vunet_conv_desc* d) {
+  SmallGeo sg;
+  if (!small_geo(d, sg)) return 0;
+  const int nr = (2 * sg.smax + 63) / 64;
+  return nr <= 1 ? 1 : nr <= 2 ? 2 : nr <= 3 ? 3 : 5;
+}
+
+int vunet_conv_h2_small_launch(const ConvRoute& r, const GatherArgs& ga, const void* wx, int mtiles_pad, const float* amax,
                                hipStream_t st) {
   SmallGeo sg;
   if (!small_geo(&ga.d, sg) || sg.smax > 160) return VUNET_ERR_UNSUPPORTED;
-  switch (pro) {
-    case 0: return small_launch_pro<0>(ga, wx, mtiles_pad, amax, sg, st);
-    case 1: return small_launch_pro<1>(ga, wx, mtiles_pad, amax, sg, st);
-    case 2: return small_launch_pro<2>(ga, wx, mtiles_pad, amax, sg, st);
+  switch (r.pro) {
+    case 0: return small_launch_pro<0>(ga, wx, mtiles_pad, amax, sg, r.form, st);
+    case 1: return small_launch_pro<1>(ga, wx, mtiles_pad, amax, sg, r.form, st);
+    case 2: return small_launch_pro<2>(ga, wx, mtiles_pad, amax, sg, r.form, st);
     default: return VUNET_ERR_UNSUPPORTED;
   }
-}
-
-int vunet_conv_h2_small_name(const vunet_conv_desc* d, int pro, char* name, int len) {
-  SmallGeo sg;
-  if (!small_geo(d, sg)) return VUNET_ERR_UNSUPPORTED;
-  const int nr = (2 * sg.smax + 63) / 64;
-  snprintf(name, len, "conv_h2_small_kernel<%d, %d>", pro, nr <= 1 ? 1 : nr <= 2 ? 2 : nr <= 3 ? 3 : 5);
-  return VUNET_OK;
 }

@@ -12,7 +12,7 @@
 // Same weight layout (K-major wt_f / wt_d), same epilogue (store_out) as the MFMA kernels.
 #include <string.h>
 
-#include "conv_common.h"
+#include "conv_route.h"
 #include "split_h2.h"
 
 // ---- M <= 4, 3x3 / stride 1 / pad 1, forward (MODE 0) or data gradient (MODE 1: mirrored taps) ----------------
@@ -388,19 +388,14 @@ int vunet_conv_thin_kind(const vunet_conv_desc* d, int pro, bool has_aux, bool h
 }
 
 VUNET_ENV_FLAG(env_no_thin_kv, "VUNET_NO_THIN_KV")   // (A/B timing: the one-pixel-per-lane form everywhere)
-static bool thin_kv(const vunet_conv_desc& d) { return d.KH == 3 && d.Hs >= 32 && !env_no_thin_kv(); }   // the column-strip form
+bool vunet_conv_thin_strips(const vunet_conv_desc* d) { return d->KH == 3 && d->Hs >= 32 && !env_no_thin_kv(); }   // the column-strip form
 
-int vunet_conv_thin_name(const vunet_conv_desc* d, int kind, char* name, int len) {
-  if (kind == 1 && thin_kv(*d)) return snprintf(name, len, "conv_thin_mv_kernel<%d, 4>", d->mode);
-  if (kind == 1) return snprintf(name, len, "conv_thin_m_kernel<%d>", d->mode);
-  if (thin_kv(*d)) return snprintf(name, len, "conv_thin_kv_kernel<3, 4>");
-  return snprintf(name, len, "conv_thin_k_kernel<%d, 3>", d->KH);
-}
-
-int vunet_conv_thin_launch(const GatherArgs& ga, int kind, hipStream_t st) {
+int vunet_conv_thin_launch(const ConvRoute& r, const GatherArgs& ga, hipStream_t st) {
   const vunet_conv_desc& d = ga.d;
+  const int kind = r.form;
+  const bool strips = r.NT == 1;
   dim3 grid((unsigned)(d.N * ((d.Hs + 7) / 8) * ((d.Ws + 31) / 32))), block(256);
-  if (kind == 1 && thin_kv(d)) {
+  if (kind == 1 && strips) {
     dim3 gv((unsigned)(d.N * ((d.Hs + 31) / 32) * ((d.Ws + 31) / 32)));
     if (d.mode == 0) VUNET_LAUNCH((conv_thin_mv_kernel<0, 4>), gv, block, 0, st, ga);
     else VUNET_LAUNCH((conv_thin_mv_kernel<1, 4>), gv, block, 0, st, ga);
@@ -408,7 +403,7 @@ int vunet_conv_thin_launch(const GatherArgs& ga, int kind, hipStream_t st) {
     if (d.mode == 0) VUNET_LAUNCH((conv_thin_m_kernel<0>), grid, block, 0, st, ga);
     else VUNET_LAUNCH((conv_thin_m_kernel<1>), grid, block, 0, st, ga);
   } else {
-    if (thin_kv(d)) {
+    if (strips) {
       dim3 gv((unsigned)(d.N * ((d.Hs + 31) / 32) * ((d.Ws + 31) / 32)));
       VUNET_LAUNCH((conv_thin_kv_kernel<3, 4>), gv, block, 0, st, ga, P2Out{});
     } else if (d.KH == 3) VUNET_LAUNCH((conv_thin_k_kernel<3, 3>), grid, block, 0, st, ga);

@@ -1,5 +1,5 @@
 // Host-side dispatch of the LDS-tiled 3x3 / stride-1 convolution (kernel: conv_tiled_kernel.h).
-#include "conv_common.h"
+#include "conv_route.h"
 
 int vunet_conv_tiled_launch_mt1(const GatherArgs& ga, int pro, int NT, int TW, hipStream_t st);
 int vunet_conv_tiled_launch_mt2(const GatherArgs& ga, int pro, int NT, int TW, hipStream_t st);
@@ -12,10 +12,10 @@ bool vunet_conv_tiled_applicable(const vunet_conv_desc* d) {
          d->Hs % (d->Ws % 32 == 0 ? 4 : 8) == 0;
 }
 
-static int tile_width(const vunet_conv_desc& d) { return d.Wo % 32 == 0 ? 32 : 16; }
+int vunet_conv_tiled_width(const vunet_conv_desc* d) { return d->Wo % 32 == 0 ? 32 : 16; }
 
 static long tiled_blocks(const vunet_conv_desc& d, int MT, int NT) {
-  const int TW = tile_width(d), TH = 4 * NT * (32 / TW);
+  const int TW = vunet_conv_tiled_width(&d), TH = 4 * NT * (32 / TW);
   if (d.Ho % TH != 0 || ((TW == 16 || d.stride == 2) && NT != 1)) return 0;
   return (long)d.N * (d.Ho / TH) * (d.Wo / TW) * ((d.M + 32 * MT - 1) / (32 * MT));
 }
@@ -67,21 +67,7 @@ int vunet_conv_tiled_pick(const vunet_conv_desc* d, int* MT, bool valu_heavy) {
   return best;
 }
 
-int vunet_conv_tiled_launch(const GatherArgs& ga, int pro, hipStream_t st) {
-  int MT;
-  const int NT = vunet_conv_tiled_pick(&ga.d, &MT, (pro != 0 && pro != 4) || (ga.d.mode == 1 && ga.aux != nullptr));
-  if (pro == 3) return VUNET_ERR_UNSUPPORTED;
-  const int TW = tile_width(ga.d);
-  return MT == 1 ? vunet_conv_tiled_launch_mt1(ga, pro, NT, TW, st) : vunet_conv_tiled_launch_mt2(ga, pro, NT, TW, st);
-}
-
-// kernel the tiled path would launch, in rocprofv3's spelling (bench.py matches it against the kernel trace)
-int vunet_conv_tiled_name(const vunet_conv_desc* d, int pro, bool has_aux, char* name, int len) {
-  int MT;
-  const int NT = vunet_conv_tiled_pick(d, &MT, (pro != 0 && pro != 4) || (d->mode == 1 && has_aux));
-  const int TW = tile_width(*d);
-  const int nt = TW == 16 ? 1 : NT;
-  const int CK = (MT == 2 && nt == 4) ? 4 : 8;
-  return snprintf(name, len, "conv_tiled_kernel<%d, %d, %d, %d, %d, %d, %d>", MT, d->stride == 2 ? 1 : nt, CK, d->mode,
-                  d->mode == 1 ? (pro == 4 ? 4 : 0) : pro, TW, d->stride);
+int vunet_conv_tiled_launch(const ConvRoute& r, const GatherArgs& ga, hipStream_t st) {
+  if (r.pro == 3) return VUNET_ERR_UNSUPPORTED;
+  return r.MT == 1 ? vunet_conv_tiled_launch_mt1(ga, r.pro, r.NT, r.TW, st) : vunet_conv_tiled_launch_mt2(ga, r.pro, r.NT, r.TW, st);
 }

@@ -132,16 +132,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a_in) {
   }
 }
 
-static void wgrad_geometry(const vunet_wgrad_desc* d, int& T, int& Ctot, int& Coutp, int& nchunks, int& WM) {
-  T = d->KH * d->KW;
-  Ctot = d->C1 + d->C2;
-  Coutp = (d->Cout + 31) / 32 * 32;
-  const int64_t NP = (int64_t)d->N * d->Ho * d->Wo;
-  nchunks = (int)((NP + 31) / 32);
-  WM = d->Cout > 64 ? 4 : (d->Cout > 32 ? 2 : 1);
-  if (T > 9 && WM == 4) WM = 2;
-}
-
 // conv_wgrad_thin.hip: 3x3 layers with <= 4 output channels at full resolution (out_conv): fp32 FMA kernel
 bool vunet_wgrad_thin_applicable(const vunet_wgrad_desc* d);
 int vunet_wgrad_thin_nslabs(const vunet_wgrad_desc* d);
@@ -176,9 +166,46 @@ int vunet_wgrad_direct_launch(const vunet_wgrad_desc* d, const float* x1, const 
 int vunet_wgrad_direct_form(const vunet_wgrad_desc* d);
 int vunet_wgrad_direct_launch_multi(const vunet_wgrad_item* items, const int* idx, int cnt, hipStream_t st);
 
+// ---- the routing decision of one weight gradient: wgrad_route() computes it, everything below reads it
+enum WgradFamily { WGRAD_X6, WGRAD_H2, WGRAD_DIRECT, WGRAD_THIN, WGRAD_TILED, WGRAD_GENERIC };
+
+struct WgradRoute {
+  int family;
+  int WM, WN, NTW;   // WGRAD_GENERIC: the instantiation of conv_wgrad_kernel
+  int nslabs;        // partial-result slabs the caller allocates (vunet_conv2d_wgrad_nsplit)
+};
+
+static WgradRoute wgrad_route(const vunet_wgrad_desc* d) {
+  WgradRoute r = {WGRAD_GENERIC, 0, 0, 0, 0};
+  if (vunet_wgrad_x6_applicable(d)) {
+    r.family = (d->flags & 2) ? WGRAD_H2 : WGRAD_X6, r.nslabs = vunet_wgrad_x6_nslabs(d);
+  } else if (vunet_wgrad_direct_applicable(d)) {
+    r.family = WGRAD_DIRECT, r.nslabs = vunet_wgrad_direct_nslabs(d);
+  } else if (vunet_wgrad_thin_applicable(d)) {
+    r.family = WGRAD_THIN, r.nslabs = vunet_wgrad_thin_nslabs(d);
+  } else if (vunet_wgrad_tiled_applicable(d)) {
+    r.family = WGRAD_TILED, r.nslabs = vunet_wgrad_tiled_nslabs(d);
+  } else {
+    const int T = d->KH * d->KW, Ctot = d->C1 + d->C2;
+    r.WM = d->Cout > 64 ? 4 : (d->Cout > 32 ? 2 : 1);
+    if (T > 9 && r.WM == 4) r.WM = 2;
+    r.WN = 4 / r.WM;
+    r.NTW = T == 1 ? 1 : (T <= 9 ? (r.WM == 4 ? 9 : (r.WM == 2 ? 5 : 3)) : (r.WM == 2 ? 8 : 4));
+    const int nchunks = (int)(((int64_t)d->N * d->Ho * d->Wo + 31) / 32);
+    const int ciblocks = (Ctot + 31) / 32, coblocks = (d->Cout + 32 * r.WM - 1) / (32 * r.WM);
+    int S = 768 / (ciblocks * coblocks);
+    if (S > nchunks) S = nchunks;  // small maps: one 32-pixel chunk per workgroup rather than a serial chunk loop
+    // (capping S to bound the slab volume was measured slower: the serial chunk loop costs more than the reduce)
+    if (S < 1) S = 1;
+    if (S > 256) S = 256;
+    r.nslabs = S;
+  }
+  return r;
+}
+
 // layers whose weight gradient runs on the direct kernel and is a short launch: batched (vunet_conv2d_wgrad_multi)
 extern "C" int vunet_conv2d_wgrad_batchable(const vunet_wgrad_desc* d) {
-  if (!d || vunet_wgrad_x6_applicable(d) || !vunet_wgrad_direct_applicable(d)) return 0;
+  if (!d || wgrad_route(d).family != WGRAD_DIRECT) return 0;
   // (A/B: VUNET_WGRAD_BATCH_PIX moves the bound between "latency" and "work")
   static const int64_t bound = [] { const char* e = getenv("VUNET_WGRAD_BATCH_PIX"); return e ? atoll(e) : 16384ll; }();
   return (int64_t)d->N * d->Ho * d->Wo <= bound ? 1 : 0;
@@ -206,53 +233,27 @@ extern "C" int vunet_conv2d_wgrad_multi(const vunet_wgrad_item* items, int32_t n
 }
 
 extern "C" int vunet_conv2d_wgrad_wants_split(const vunet_wgrad_desc* d) {
-  return d && (vunet_wgrad_x6_applicable(d) || vunet_wgrad_direct_applicable(d)) ? 1 : 0;
+  return d && wgrad_route(d).family <= WGRAD_DIRECT ? 1 : 0;
 }
 
 extern "C" int vunet_conv2d_wgrad_variant(const vunet_wgrad_desc* d, char* name, int32_t len) {
   if (!d || !name || len < 8) return VUNET_ERR_ARG;
-  if (vunet_wgrad_x6_applicable(d)) {
-    if (d->flags & 2) vunet_wgrad_h2_name(d, name, len);
-    else vunet_wgrad_x6_name(d, name, len);
-    return VUNET_OK;
+  const WgradRoute r = wgrad_route(d);
+  switch (r.family) {
+    case WGRAD_X6: vunet_wgrad_x6_name(d, name, len); break;
+    case WGRAD_H2: vunet_wgrad_h2_name(d, name, len); break;
+    case WGRAD_DIRECT: vunet_wgrad_direct_name(d, name, len); break;
+    case WGRAD_THIN: vunet_wgrad_thin_name(d, name, len); break;
+    case WGRAD_TILED:
+      if (d->stride == 2) snprintf(name, len, "conv_wgrad_tiled_kernel<2, 2, 3, 2>");
+      else snprintf(name, len, "conv_wgrad_tiled_kernel<%d, 4, %d, 1>", d->Cout >= 64 ? 2 : 1, d->KH);
+      break;
+    default: snprintf(name, len, "conv_wgrad_kernel<%d, %d, %d>", r.WM, r.WN, r.NTW);
   }
-  if (vunet_wgrad_direct_applicable(d)) {
-    vunet_wgrad_direct_name(d, name, len);
-    return VUNET_OK;
-  }
-  if (vunet_wgrad_thin_applicable(d)) {
-    vunet_wgrad_thin_name(d, name, len);
-    return VUNET_OK;
-  }
-  if (vunet_wgrad_tiled_applicable(d)) {
-    if (d->stride == 2) snprintf(name, len, "conv_wgrad_tiled_kernel<2, 2, 3, 2>");
-    else snprintf(name, len, "conv_wgrad_tiled_kernel<%d, 4, %d, 1>", d->Cout >= 64 ? 2 : 1, d->KH);
-    return VUNET_OK;
-  }
-  int T, Ctot, Coutp, nchunks, WM;
-  wgrad_geometry(d, T, Ctot, Coutp, nchunks, WM);
-  const int WN = 4 / WM;
-  const int NTW = T == 1 ? 1 : (T <= 9 ? (WM == 4 ? 9 : (WM == 2 ? 5 : 3)) : (WM == 2 ? 8 : 4));
-  snprintf(name, len, "conv_wgrad_kernel<%d, %d, %d>", WM, WN, NTW);
   return VUNET_OK;
 }
 
-extern "C" int vunet_conv2d_wgrad_nsplit(const vunet_wgrad_desc* d) {
-  if (!d) return VUNET_ERR_ARG;
-  if (vunet_wgrad_x6_applicable(d)) return vunet_wgrad_x6_nslabs(d);
-  if (vunet_wgrad_direct_applicable(d)) return vunet_wgrad_direct_nslabs(d);
-  if (vunet_wgrad_thin_applicable(d)) return vunet_wgrad_thin_nslabs(d);
-  if (vunet_wgrad_tiled_applicable(d)) return vunet_wgrad_tiled_nslabs(d);
-  int T, Ctot, Coutp, nchunks, WM;
-  wgrad_geometry(d, T, Ctot, Coutp, nchunks, WM);
-  const int ciblocks = (Ctot + 31) / 32, coblocks = (d->Cout + 32 * WM - 1) / (32 * WM);
-  int S = 768 / (ciblocks * coblocks);
-  if (S > nchunks) S = nchunks;  // small maps: one 32-pixel chunk per workgroup rather than a serial chunk loop
-  // (capping S to bound the slab volume was measured slower: the serial chunk loop costs more than the reduce)
-  if (S < 1) S = 1;
-  if (S > 256) S = 256;
-  return S;
-}
+extern "C" int vunet_conv2d_wgrad_nsplit(const vunet_wgrad_desc* d) { return d ? wgrad_route(d).nslabs : VUNET_ERR_ARG; }
 
 template <int WM, int WN, int NTW>
 static int launch_wgrad(const WgradArgs& wa, hipStream_t st) {
@@ -268,13 +269,6 @@ static int launch_wgrad(const WgradArgs& wa, hipStream_t st) {
 
 extern "C" int vunet_conv2d_wgrad_a2(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy,
                                      float* slabs, float* dshift, const float* amax_x, const float* amax_x2,
-                                     const float* amax_dy, void* stream);
-extern "C" int vunet_conv2d_wgrad(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy,
-                                  float* slabs, float* dshift, const float* amax_x, const float* amax_dy, void* stream) {
-  return vunet_conv2d_wgrad_a2(d, x1, x2, dy, slabs, dshift, amax_x, nullptr, amax_dy, stream);
-}
-extern "C" int vunet_conv2d_wgrad_a2(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy,
-                                     float* slabs, float* dshift, const float* amax_x, const float* amax_x2,
                                      const float* amax_dy, void* stream) {
   if (!d || !x1 || !dy || !slabs || !dshift) return VUNET_ERR_ARG;
   if (d->C2 > 0 && !x2) return VUNET_ERR_ARG;
@@ -282,43 +276,44 @@ extern "C" int vunet_conv2d_wgrad_a2(const vunet_wgrad_desc* d, const float* x1,
   const int64_t in_elems = (int64_t)d->N * (d->C1 > d->C2 ? d->C1 : d->C2) * d->Hs * d->Ws;
   const int64_t out_elems = (int64_t)d->N * d->Cout * d->Ho * d->Wo;
   if (in_elems >= (1ll << 31) || out_elems >= (1ll << 31)) return VUNET_ERR_UNSUPPORTED;
-  if (vunet_wgrad_x6_applicable(d)) {
-    if (d->flags & 2) {
-      if (!amax_x || !amax_dy) return VUNET_ERR_ARG;
-      return vunet_wgrad_h2_launch(d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy, (hipStream_t)stream);
-    }
-    return vunet_wgrad_x6_launch(d, x1, x2, dy, slabs, dshift, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  const WgradRoute r = wgrad_route(d);
+  if ((r.family == WGRAD_H2 || r.family == WGRAD_DIRECT) && (!amax_x || !amax_dy)) return VUNET_ERR_ARG;
+  switch (r.family) {
+    case WGRAD_X6: return vunet_wgrad_x6_launch(d, x1, x2, dy, slabs, dshift, st);
+    case WGRAD_H2: return vunet_wgrad_h2_launch(d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy, st);
+    case WGRAD_DIRECT: return vunet_wgrad_direct_launch(d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy, st);
+    case WGRAD_THIN: return vunet_wgrad_thin_launch(d, x1, dy, slabs, dshift, st);
+    case WGRAD_TILED: return vunet_wgrad_tiled_launch(d, x1, x2, dy, slabs, dshift, st);
+    default: break;
   }
-  if (vunet_wgrad_direct_applicable(d)) {
-    if (!amax_x || !amax_dy) return VUNET_ERR_ARG;
-    return vunet_wgrad_direct_launch(d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy, (hipStream_t)stream);
-  }
-  if (vunet_wgrad_thin_applicable(d)) return vunet_wgrad_thin_launch(d, x1, dy, slabs, dshift, (hipStream_t)stream);
-  if (vunet_wgrad_tiled_applicable(d)) return vunet_wgrad_tiled_launch(d, x1, x2, dy, slabs, dshift, (hipStream_t)stream);
   WgradArgs wa;
   wa.d = *d;
   wa.x1 = x1; wa.x2 = x2; wa.dy = dy; wa.slabs = slabs; wa.dshift = dshift;
-  int WM;
-  wgrad_geometry(d, wa.T, wa.Ctot, wa.Coutp, wa.nchunks, WM);
+  wa.T = d->KH * d->KW;
+  wa.Ctot = d->C1 + d->C2;
+  wa.Coutp = (d->Cout + 31) / 32 * 32;
   wa.NP = d->N * d->Ho * d->Wo;
+  wa.nchunks = (int)(((int64_t)wa.NP + 31) / 32);
   wa.HoWo = d->Ho * d->Wo;
   wa.HsWs = d->Hs * d->Ws;
   wa.cps = (wa.nchunks + d->nsplit - 1) / d->nsplit;
   wa.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
   wa.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
-  hipStream_t st = (hipStream_t)stream;
-  const int T = wa.T;
-  if (T > 16) return VUNET_ERR_UNSUPPORTED;
-  if (T == 1) {
-    if (WM == 4) return launch_wgrad<4, 1, 1>(wa, st);
-    if (WM == 2) return launch_wgrad<2, 2, 1>(wa, st);
-    return launch_wgrad<1, 4, 1>(wa, st);
+  if (wa.T > 16) return VUNET_ERR_UNSUPPORTED;
+  switch (r.WM * 16 + r.NTW) {   // <WM, WN = 4 / WM, NTW> as wgrad_route picked them
+    case 4 * 16 + 1: return launch_wgrad<4, 1, 1>(wa, st);
+    case 2 * 16 + 1: return launch_wgrad<2, 2, 1>(wa, st);
+    case 1 * 16 + 1: return launch_wgrad<1, 4, 1>(wa, st);
+    case 4 * 16 + 9: return launch_wgrad<4, 1, 9>(wa, st);
+    case 2 * 16 + 5: return launch_wgrad<2, 2, 5>(wa, st);
+    case 1 * 16 + 3: return launch_wgrad<1, 4, 3>(wa, st);
+    case 2 * 16 + 8: return launch_wgrad<2, 2, 8>(wa, st);
+    default: return launch_wgrad<1, 4, 4>(wa, st);
   }
-  if (T <= 9) {
-    if (WM == 4) return launch_wgrad<4, 1, 9>(wa, st);
-    if (WM == 2) return launch_wgrad<2, 2, 5>(wa, st);
-    return launch_wgrad<1, 4, 3>(wa, st);
-  }
-  if (WM == 2) return launch_wgrad<2, 2, 8>(wa, st);
-  return launch_wgrad<1, 4, 4>(wa, st);
+}
+
+extern "C" int vunet_conv2d_wgrad(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy,
+                                  float* slabs, float* dshift, const float* amax_x, const float* amax_dy, void* stream) {
+  return vunet_conv2d_wgrad_a2(d, x1, x2, dy, slabs, dshift, amax_x, nullptr, amax_dy, stream);
 }

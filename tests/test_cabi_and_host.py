@@ -223,6 +223,33 @@ def test_kernel_selection_of_the_gather_entry_point():
     assert variant(C1=3, M=64, Mpad=64, Hs=256, Ws=256, Ho=256, Wo=256, out_act=ops.ACT_RELU) == "conv_thin_kv_kernel<3, 4>"
 
 
+def test_routing_table_recorded_from_the_parent_replays():
+    """tests/route_table.txt: a few thousand cases of tools/route_sweep.py's grid (one row per descriptor, its flag cases
+    side by side: route_sweep.pack), every kernel family of both routers among them, with what the query entry points (the *_variant names, publishes_amax, wants_split, x6_supported; wgrad
+    variant, nsplit, wants_split, batchable; return codes) answered on the commit named in its first line.  Host logic, no
+    GPU: the built library must answer every line the same, character for character."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("route_sweep_under_test", os.path.join(root, "tools", "route_sweep.py"))
+    rs = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rs)
+    lines = open(os.path.join(root, "tests", "route_table.txt")).read().splitlines()
+    assert lines[0].startswith("# routing answers recorded from commit ")
+    cases = list(rs.unpack(lines[1:]))
+    assert len(cases) >= 2000
+    q = rs.Queries()
+    conv_seen, wgrad_seen = set(), set()
+    for line in cases:
+        assert rs.replay(q, line) == line
+        f = line.split("|")
+        if line.startswith("c "):
+            conv_seen.update(rs.conv_family(x.rsplit(" ", 2)[0].split(":", 1)[1]) for x in f[3:6])
+            if f[1] == "0": conv_seen.add("unsupported")
+        else:
+            wgrad_seen.add(rs.wgrad_family(f[1].split(":", 1)[1]))
+    assert conv_seen == set(rs.CONV_FAMILIES) and wgrad_seen == set(rs.WGRAD_FAMILIES)
+
+
 def test_p2_dispatch_and_the_vgg19_program_are_host_logic():
     """The pre-split VGG19 path (csrc/conv_p2.hip, models/imagenet_pretrained._P2Engine) without a GPU: which geometries
     vunet_p2_conv covers and which workgroup form it picks, the weight image's size, and the program the engine derives from
