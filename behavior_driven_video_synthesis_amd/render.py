@@ -222,3 +222,78 @@ def behavior_video(flow, net, vunet, app_img: torch.Tensor, start_poses: torch.T
                                  dtype=dtype, share_appearance=share_appearance)
         frames.append(rgb)
     return torch.stack(frames), poses, kps
+
+
+def _render_rows(vunet, app_img, poses: torch.Tensor, camera, joint_model, dtype, share_appearance, chunk):
+    """poses [..., L, n] -> (frames uint8 [..., L, H, W, 3] or None, keypoints [..., L, J, 2]): one projection launch over every
+    row, then ``render_sequence`` per row -- skipped without a synthesis model or an appearance image (the reference's
+    pose-only branch)."""
+    lead, length = poses.shape[:-2], poses.shape[-2]
+    kps = camera.project(poses.reshape(-1, poses.shape[-1]))
+    kps = kps.reshape(-1, length, kps.shape[-2], 2)
+    frames = None
+    if vunet is not None and app_img is not None:
+        frames = torch.stack([render_sequence(vunet, app_img, k, spatial_size=camera.spatial_size, joint_model=joint_model,
+                                              chunk=chunk, dtype=dtype, share_appearance=share_appearance)[0] for k in kps])
+        frames = frames.reshape(*lead, *frames.shape[1:])
+    return frames, kps.reshape(*lead, *kps.shape[1:])
+
+
+@torch.no_grad()
+def transfer_video(net, vunet, app_img: Optional[torch.Tensor], behavior_seq: torch.Tensor, start_poses: torch.Tensor, camera,
+                   start_frame: int = 0, length: Optional[int] = None, sample: bool = False, eps: Optional[torch.Tensor] = None,
+                   joint_model=H36M_JOINT_MODEL, dtype: str = "bf16", share_appearance: bool = True, chunk: int = 16):
+    """Behaviour transfer (``visualize_transfer3d``, lib/logging.py:207-225, :331-370): the behaviour observed in
+    ``behavior_seq`` [B, T, n] re-enacted from ``start_poses[:, start_frame]`` ([B, T', n]) and rendered with ``app_img``.
+
+    The code is the posterior mean ``mu`` of ``net.infer_b(behavior_seq)``, or with ``sample`` the posterior sample
+    ``eps * exp(logstd) + mu`` (``eps`` [B, H] given or drawn); ``length`` (default T) poses are rolled out and the start pose is
+    put in front of them, as the reference does before it plots.
+
+    Returns (frames uint8 [B, L + 1, H, W, 3], poses [B, L + 1, n], keypoints [B, L + 1, J, 2]); ``vunet`` or ``app_img`` None:
+    no synthesis, frames is None."""
+    if behavior_seq.dim() != 3 or start_poses.dim() != 3 or behavior_seq.shape[0] != start_poses.shape[0]:
+        raise ValueError(f"transfer_video: behaviour {tuple(behavior_seq.shape)} and start poses {tuple(start_poses.shape)}: one "
+                         "[B, T, n] row of each per video")
+    if not net.ib:
+        raise ValueError("transfer_video needs the behaviour net's information bottleneck (its posterior mean is the code)")
+    start_frame = start_frame % start_poses.shape[1]
+    length = behavior_seq.shape[1] if length is None else int(length)
+    if sample and eps is None:
+        eps = torch.randn(behavior_seq.shape[0], net.dim_hidden_b, device=behavior_seq.device)
+    # the encoder alone: b = eps exp(logstd) + mu, and without noise b = mu (nothing is drawn for the mean)
+    b, *_ = net.engine().infer_b(behavior_seq.contiguous(), eps.contiguous() if sample else None)
+    xs, *_ = net.generate_seq(b, start_poses, len=length, start_frame=start_frame)
+    poses = torch.cat([start_poses[:, start_frame].unsqueeze(1), xs], dim=1)
+    frames, kps = _render_rows(vunet, app_img, poses, camera, joint_model, dtype, share_appearance, chunk)
+    return frames, poses, kps
+
+
+@torch.no_grad()
+def interpolation_video(net, vunet, app_img: Optional[torch.Tensor], seq1: torch.Tensor, seq2: torch.Tensor, camera, steps=None,
+                        joint_model=H36M_JOINT_MODEL, dtype: str = "bf16", share_appearance: bool = True, chunk: int = 16):
+    """Latent interpolation (``latent_interpolate``, lib/logging.py:983-1040): a spherical walk between the behaviour codes of
+    ``seq1`` and ``seq2`` ([P, T, n] each), in both directions, every step re-enacted from its direction's own start pose.
+
+    The codes are the posterior means of both sequences; ``seq.slerp_codes`` interpolates all steps of both directions in one
+    launch (``steps``: default ``np.linspace(0, 1, 6)``) and ONE roll-out decodes the 2 P S codes -- direction 0 from
+    ``seq1[:, 0]``, direction 1 from ``seq2[:, 0]``, T poses each, the start pose in front.  The reference runs one host-side
+    slerp and one batch-1 roll-out per step and direction.
+
+    Returns (frames uint8 [2, P, S, T + 1, H, W, 3] or None, poses [2, P, S, T + 1, n], keypoints [2, P, S, T + 1, J, 2],
+    codes [2, P, S, H])."""
+    from .seq import slerp_codes
+    if seq1.dim() != 3 or seq1.shape != seq2.shape:
+        raise ValueError(f"interpolation_video: two [P, T, n] sequence tensors of one shape expected, got {tuple(seq1.shape)} and "
+                         f"{tuple(seq2.shape)}")
+    if not net.ib:
+        raise ValueError("interpolation_video needs the behaviour net's information bottleneck (its posterior mean is the code)")
+    pairs, t, n = seq1.shape
+    mu = net.engine().infer_b(torch.cat([seq1, seq2]), None)[1]      # both sequences of every pair in one pass; no noise drawn
+    codes = slerp_codes(mu[:pairs], mu[pairs:], steps)
+    s = codes.shape[2]
+    starts = torch.stack([seq1[:, :1], seq2[:, :1]]).unsqueeze(2).expand(2, pairs, s, 1, n).reshape(2 * pairs * s, 1, n)
+    xs, *_ = net.generate_seq(codes.reshape(2 * pairs * s, -1), starts, len=t, start_frame=0)
+    poses = torch.cat([starts, xs], dim=1).reshape(2, pairs, s, t + 1, n)
+    frames, kps = _render_rows(vunet, app_img, poses, camera, joint_model, dtype, share_appearance, chunk)
+    return frames, poses, kps, codes

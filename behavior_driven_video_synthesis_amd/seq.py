@@ -742,3 +742,30 @@ class BehaviorEngine:
         if len(res) == 1:
             return res[0]
         return tuple(torch.cat([r[i] for r in res]) for i in range(4))
+
+
+MAX_SLERP_STEPS = 64   # csrc/seq_interp.hip: one lane of the first wave per step
+
+
+def slerp_codes(b1: torch.Tensor, b2: torch.Tensor, steps=None) -> torch.Tensor:
+    """Spherical interpolation between two sets of behaviour codes [P, H] (lib/utils.py:920-925), every step of both
+    directions in one launch (csrc/seq_interp.hip) -- the reference walks the steps on the host, one device -> host -> device
+    round trip per step and direction (lib/logging.py:994-1012).
+
+    -> [2, P, S, H]: ``out[0, p, s] = slerp(steps[s], b1[p], b2[p])``, ``out[1, p, s] = slerp(steps[s], b2[p], b1[p])``.
+    ``steps``: a float64 sequence of at most 64 values, default ``np.linspace(0, 1, 6)``.  The sums, the angle and the
+    coefficients are float64 and a value is rounded once; a row of zeros has no direction and gives NaN rows, as numpy does."""
+    import numpy as np
+    _need_device(b1, b2)
+    if b1.dim() != 2 or b1.shape != b2.shape or b1.device != b2.device or b1.shape[0] < 1 or b1.shape[1] < 1:
+        raise ValueError(f"slerp_codes: two [P, H] code tensors of one shape on one device expected, got {tuple(b1.shape)} and "
+                         f"{tuple(b2.shape)}")
+    st = np.linspace(0, 1, 6) if steps is None else np.asarray(steps, dtype=np.float64).reshape(-1)
+    if not 1 <= st.size <= MAX_SLERP_STEPS:
+        raise ValueError(f"slerp_codes: 1..{MAX_SLERP_STEPS} steps per launch, got {st.size}")
+    b1, b2 = b1.contiguous(), b2.contiguous()
+    pairs, h = b1.shape
+    st_dev = torch.as_tensor(st, device=b1.device)
+    out = torch.empty(2, pairs, st.size, h, device=b1.device, dtype=torch.float32)
+    _call("vunet_seq_slerp", _p(b1), _p(b2), h, pairs, h, _p(st_dev), int(st.size), _p(out), _stream())
+    return out

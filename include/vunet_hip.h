@@ -669,6 +669,17 @@ int vunet_seq_actnorm_init(const float* x, int32_t ld, int32_t B, int32_t C, flo
 int vunet_seq_normlinear_rows(const float* v, const float* g, const float* bias, const float* gamma, const float* beta, int32_t M,
                               int32_t K, float* row_scale, float* bias_eff, void* stream);
 
+/* ---- spherical interpolation between behaviour codes (csrc/seq_interp.hip; lib/utils.py:920-925 as lib/logging.py:994-1012
+ * calls it, once per step and direction on the host).  b1 / b2: `pairs` rows of h floats, ld_in >= h floats apart; steps: n_steps
+ * DEVICE doubles, 1 <= n_steps <= 64; out: [2][pairs][n_steps][h].
+ *   out[0][p][s] = slerp(steps[s], b1[p], b2[p]),  out[1][p][s] = slerp(steps[s], b2[p], b1[p])   (computed, not mirrored)
+ *   slerp(v, lo, hi): omega = acos(clamp(lo.hi / (|lo| |hi|), -1, 1)), so = sin(omega);
+ *                     so == 0: (1 - v) lo + v hi;  else sin((1 - v) omega) / so * lo + sin(v omega) / so * hi.
+ * The sums, omega and the coefficients are float64 and an element is rounded once, at its store; bit-reproducible (no atomics).
+ * A row of zeros gives NaN rows, as numpy does.  One workgroup per pair. */
+int vunet_seq_slerp(const float* b1, const float* b2, int64_t ld_in, int pairs, int h, const double* steps, int n_steps, float* out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
