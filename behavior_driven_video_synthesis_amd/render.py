@@ -297,3 +297,53 @@ def interpolation_video(net, vunet, app_img: Optional[torch.Tensor], seq1: torch
     poses = torch.cat([starts, xs], dim=1).reshape(2, pairs, s, t + 1, n)
     frames, kps = _render_rows(vunet, app_img, poses, camera, joint_model, dtype, share_appearance, chunk)
     return frames, poses, kps, codes
+
+
+@torch.no_grad()
+def neighbour_video(net, vunet, app_img: Optional[torch.Tensor], behavior_seq: torch.Tensor, start_poses: torch.Tensor, bank, camera,
+                    root: int, eps: Optional[torch.Tensor] = None, pose_space: bool = True, joint_model=H36M_JOINT_MODEL,
+                    dtype: str = "bf16", share_appearance: bool = True, chunk: int = 16):
+    """The four rows of the reference's ``nearest_neighbours`` figure (lib/figures.py:207-212, :255-278, :415-422), in its
+    order: the behaviour sequence [B, T, n]; its nearest training sequence in code space (``bank.nearest_codes`` of its posterior
+    mean); the generated sequence -- the posterior sample ``eps * exp(logstd) + mu`` (``eps`` [B, H] given or drawn, as the
+    reference's ``net(poses_b, poses_in, len)`` draws it) rolled out for T poses from ``start_poses[:, 0]``, that pose in
+    front; and the generated sequence's nearest training sequence in pose space (``bank.nearest_poses``, centred on joint
+    ``root``).  ``bank``: a ``neighbours.TrainBank`` of [N, T + 1, n] sequences.
+
+    Pose space compares joint positions (n = 3 J).  A model trained on ``angle_world_expmap`` poses (an ``AnglePoseCamera``) has
+    none in its pose vectors -- the reference compares mismatched representations there -- so with ``pose_space`` that raises
+    ``ValueError``; ``pose_space=False`` keeps the first three rows and returns None for the fourth.
+
+    Returns (frames, poses, keypoints, found): three lists of four rows each (uint8 [B, L, H, W, 3], [B, L, n], [B, L, J, 2];
+    ``frames`` is None without ``vunet`` or ``app_img``), and ``found`` = {"code_index", "code_distance", "pose_index",
+    "pose_distance"}: int64 / float64 device tensors [B]."""
+    if behavior_seq.dim() != 3 or start_poses.dim() != 3 or behavior_seq.shape[0] != start_poses.shape[0]:
+        raise ValueError(f"neighbour_video: behaviour {tuple(behavior_seq.shape)} and start poses {tuple(start_poses.shape)}: one "
+                         "[B, T, n] row of each per video")
+    if not net.ib:
+        raise ValueError("neighbour_video needs the behaviour net's information bottleneck (its posterior mean is the code)")
+    if pose_space and isinstance(camera, AnglePoseCamera):
+        raise ValueError("neighbour_video: the pose-space neighbour compares joint positions, and an angle_world_expmap model's pose "
+                         "vectors are a root translation and joint rotations; pass pose_space=False to keep the code-space rows")
+    bsz, t, _ = behavior_seq.shape
+    if t + 1 != bank.sequences.shape[1]:
+        raise ValueError(f"neighbour_video: a behaviour of T={t} frames needs a bank of T + 1={t + 1} frames, got {bank.sequences.shape[1]}")
+    if eps is None:
+        eps = torch.randn(bsz, net.dim_hidden_b, device=behavior_seq.device)
+    b, mu, _, _ = net.engine().infer_b(behavior_seq.contiguous(), eps.contiguous())
+    xs, *_ = net.generate_seq(b, start_poses, len=t, start_frame=0)
+    generated = torch.cat([start_poses[:, :1], xs], dim=1)
+    code_i, code_d = bank.nearest_codes(mu)
+    rows = [behavior_seq, bank.sequences[code_i], generated, None]
+    found = {"code_index": code_i, "code_distance": code_d, "pose_index": None, "pose_distance": None}
+    if pose_space:
+        found["pose_index"], found["pose_distance"] = bank.nearest_poses(generated, root)
+        rows[3] = bank.sequences[found["pose_index"]]
+    frames, kps = [], []
+    for r in rows:
+        f, k = (None, None) if r is None else _render_rows(vunet, app_img, r, camera, joint_model, dtype, share_appearance, chunk)
+        frames.append(f)
+        kps.append(k)
+    if vunet is None or app_img is None:
+        frames = None
+    return frames, rows, kps, found
