@@ -63,24 +63,46 @@ class UnconditionalFlow2(nn.Module):
                                          for _ in range(n_flows)])
         self._engine = None
         self._train_engine = None
+        self.weight_precision = "f32"
+
+    def set_weight_precision(self, mode: str):
+        """"f32" (default) or "bf16": the precision of the coupling MLPs' weight images in the inference engine
+        (include/vunet_seq_bf16.h: bf16-rounded weights, fp32-accurate products, half the weight bytes per pass).  bf16 images
+        are for inference only: in that mode a call that autograd would record, and the training engine, raise.  Returns the
+        previous mode."""
+        from ...seq import check_weight_mode
+        check_weight_mode(mode)
+        prev = self.weight_precision
+        self.weight_precision = mode
+        if self._engine is not None:
+            self._engine.set_weights(mode)
+        return prev
 
     def engine(self):
         if self._engine is None:
             from ... import seq
             object.__setattr__(self, "_engine", seq.FlowEngine(self))
+            self._engine.set_weights(self.weight_precision)
         return self._engine
 
     def train_engine(self, **adam):
         """The training plans of this flow (``seq_train.FlowTrainEngine``); ``adam``: the hyper-parameters of its fused
         optimiser step (used by ``experiments.behavior_net``; autograd callers bring their own optimiser)."""
+        if self.weight_precision != "f32":
+            from ...seq import BF16_INFERENCE_ONLY
+            raise RuntimeError(BF16_INFERENCE_ONLY)
         if self._train_engine is None:
             from ... import seq_train
             object.__setattr__(self, "_train_engine", seq_train.FlowTrainEngine(self, **adam))
         return self._train_engine
 
     def forward(self, x, reverse=False):
-        if reverse:
+        if reverse:   # (in bf16 mode the engine refuses a call that autograd would record)
             return self.engine().reverse(x)[:, :, None, None]
+        if self.weight_precision != "f32" and torch.is_grad_enabled() and (
+                x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            from ...seq import BF16_INFERENCE_ONLY
+            raise RuntimeError(BF16_INFERENCE_ONLY)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from ... import seq_train
             out, logdet = seq_train.flow_autograd(self.train_engine(), x)

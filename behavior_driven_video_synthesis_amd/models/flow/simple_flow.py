@@ -16,6 +16,11 @@ class UnsupervisedTransformer2(nn.Module):
         self.flow = UnconditionalFlow2(in_channels=in_channels, hidden_dim=kwargs["flow_mid_channels"],
                                        hidden_depth=kwargs["flow_hidden_depth"], n_flows=kwargs["n_flows"])
 
+    def set_weight_precision(self, mode: str):
+        """"f32" (default) or "bf16" weight images for the flow's inference passes (``UnconditionalFlow2.set_weight_precision``);
+        any other string raises ``ValueError``.  Returns the previous mode."""
+        return self.flow.set_weight_precision(mode)
+
     def sample(self, shape, device="cuda"):
         """models/flow/simple_flow.py:154-158 (the reference defaults to the CPU; this path has none)."""
         z_tilde = torch.randn(shape, device=device)

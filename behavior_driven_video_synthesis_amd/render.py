@@ -202,17 +202,20 @@ class AnglePoseCamera:
 @torch.no_grad()
 def behavior_video(flow, net, vunet, app_img: torch.Tensor, start_poses: torch.Tensor, length: int, camera: PoseCamera,
                    z: Optional[torch.Tensor] = None, start_frame: int = -1, joint_model=H36M_JOINT_MODEL, dtype: str = "bf16",
-                   share_appearance: bool = True, chunk: int = 16):
+                   share_appearance: bool = True, chunk: int = 16, flow_weights: str = "f32"):
     """One synthesised sequence per row of ``start_poses`` [B, T, n_kps] (experiments/behavior_net.py:1173-1184 followed by
     data/data_conversions_3d.py:1130-1185): behaviour codes b = flow.reverse(z) with z ~ N(0, 1) (or the given ``z`` [B, C]),
     the decoder's roll-out of ``length`` poses from ``start_poses[:, start_frame]``, camera projection, stickman raster and
-    ``VunetAlter.transfer`` of ``app_img`` [1, 3, H, W] for every frame.
+    ``VunetAlter.transfer`` of ``app_img`` [1, 3, H, W] for every frame.  ``flow_weights``: "f32" or "bf16", the flow's weight
+    precision for this call (``seq.flow_weight_mode``; the flow's previous mode is restored afterwards).
 
     Returns (frames uint8 [B, length, H, W, 3], poses [B, length, n_kps], keypoints [B, length, J, 2])."""
+    from .seq import flow_weight_mode
     bsz = start_poses.shape[0]
     if z is None:
         z = torch.randn(bsz, flow.in_channels, device=start_poses.device)
-    b = flow.reverse(z)
+    with flow_weight_mode(flow, flow_weights):
+        b = flow.reverse(z)
     b = b.reshape(bsz, -1)
     poses, *_ = net.generate_seq(b, start_poses, len=length, start_frame=start_frame % start_poses.shape[1])
     kps = camera.project(poses.reshape(bsz * length, -1)).reshape(bsz, length, -1, 2)

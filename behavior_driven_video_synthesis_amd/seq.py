@@ -12,6 +12,7 @@ There is no CPU path: the engines raise without a device tensor and the HIP libr
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import gc
 import os
@@ -101,6 +102,49 @@ def linear(desc: SeqLinearDesc, w: Sequence[torch.Tensor], x: torch.Tensor, bias
           _p(bias[1] if len(bias) > 1 else None), _p(y), _stream())
 
 
+WEIGHT_MODES = ("f32", "bf16")
+BF16_INFERENCE_ONLY = ("the flow is in bf16 weight mode: bf16 images are for inference only (no backward or update reads them); "
+                       "call set_weight_precision(\"f32\") before training or differentiating through the flow")
+
+
+def check_weight_mode(mode) -> str:
+    if mode not in WEIGHT_MODES:
+        raise ValueError(f"weight precision {mode!r}: expected one of {WEIGHT_MODES}")
+    return mode
+
+
+@contextlib.contextmanager
+def flow_weight_mode(flow, mode: str):
+    """``flow`` (an ``UnsupervisedTransformer2`` / ``UnconditionalFlow2``, or None) in weight precision ``mode`` for the duration
+    of the block; the previous mode comes back afterwards.  A switch re-packs the flow's images (both ways), so a caller with
+    many calls in one mode sets it once on the module instead."""
+    check_weight_mode(mode)
+    if flow is None:
+        yield
+        return
+    prev = flow.set_weight_precision(mode)
+    try:
+        yield
+    finally:
+        flow.set_weight_precision(prev)
+
+
+def linear_bf16w(desc: SeqLinearDesc, w: Sequence[torch.Tensor], x: torch.Tensor, bias: Sequence[Optional[torch.Tensor]], y: torch.Tensor,
+                 layout: int):
+    """``linear`` on bf16 weight images (include/vunet_seq_bf16.h): ``layout`` always has bit 1."""
+    _call("vunet_seq_linear_bf16w", ctypes.byref(desc), layout, _p(w[0]), _p(w[1] if len(w) > 1 else None), _p(x), _p(bias[0]),
+          _p(bias[1] if len(bias) > 1 else None), _p(y), _stream())
+
+
+def tile_image_bf16(w_img: torch.Tensor) -> torch.Tensor:
+    """A row-major fp32 [M, K] weight image -> its tile-major bf16 image (``vunet_seq_pack_tiles_bf16``), M K bfloat16 values in
+    the order of include/vunet_seq_bf16.h: half the bytes of the weights."""
+    m, k = w_img.shape
+    out = torch.empty(m * k, device=w_img.device, dtype=torch.bfloat16)
+    _call("vunet_seq_pack_tiles_bf16", _p(w_img), w_img.stride(0), m, k, _p(out), _stream())
+    return out
+
+
 def tile_image(w_img: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A row-major [M, K] weight image -> its tile-major copy (``vunet_seq_pack_tiles``): every wave load of the layer's kernel
     then covers 1 KB contiguous."""
@@ -119,11 +163,14 @@ class MlpGroup:
     are single."""
 
     def __init__(self, layers: Sequence[Sequence[Tuple[torch.Tensor, torch.Tensor]]], k_in_pad: int, tanh_head: Sequence[bool],
-                 split_head: bool = False, pad_hidden: int = 32, pad_out: int = 16, tiled: bool = False):
+                 split_head: bool = False, pad_hidden: int = 32, pad_out: int = 16, tiled: bool = False, weights: str = "f32"):
         """``pad_hidden`` / ``pad_out``: the multiples the hidden / head widths are padded to (training pads both to 64: the
         tiles of ``vunet_seq_dx`` / ``vunet_seq_dw``).  ``tiled``: the kernels read TILE-MAJOR copies of the weight images and
         hand the hidden activations to each other tile-major (include/vunet_seq_tiled.h) -- a second copy of the weights (the
-        row-major parameters stay what ``state_dict`` / an optimiser see), bit-identical results."""
+        row-major parameters stay what ``state_dict`` / an optimiser see), bit-identical results.  ``weights``: "bf16" -- the
+        kernels read bf16 tile images instead (include/vunet_seq_bf16.h; inference only, any number of layers) and those are the
+        only images held: neither the fp32 tile copies nor padded fp32 images are kept."""
+        self.weights = check_weight_mode(weights)
         self.nets = len(layers)
         n_layers = len(layers[0])
         self.dims = []     # per layer: (m_pad, k_pad)
@@ -139,8 +186,12 @@ class MlpGroup:
             self.dims.append((m_pad, k_pad))
             k_pad = m_pad
         self.out_pad = self.dims[-1][0]
-        self.tiled = tiled and n_layers >= 2
+        self.tiled = tiled and n_layers >= 2 and self.weights == "f32"
         self.wt = [[tile_image(weight_image(net[li][0], m, k)) for net in layers] for li, (m, k) in enumerate(self.dims)] if self.tiled else None
+        self.wt16 = None
+        if self.weights == "bf16":
+            self.wt16 = [[tile_image_bf16(img) for img in lay] for lay in self.w]
+            self.w = []
         # the head layer as raw partial slabs for seq_coupling_kernel to add (``split_head``: the consumer is that kernel): a
         # 512-row head would otherwise run on 32 workgroups per net; K is split until the launch has 256
         self.head_split = 1
@@ -160,6 +211,17 @@ class MlpGroup:
         row-major weights): two more buffers through which the hidden activations ALSO go tile-major from layer to layer."""
         src, shared = xin, 1
         last = len(self.dims) - 1
+        if self.wt16 is not None:
+            if tile_bufs is not None:   # (the training plans' second set of buffers)
+                raise RuntimeError(BF16_INFERENCE_ONLY)
+            for li, (m_pad, k_pad) in enumerate(self.dims):
+                dst = bufs[li % len(bufs)]
+                act = self.head_act if li == last else [ACT_LRELU, ACT_LRELU]
+                d = SeqLinearDesc(rows, m_pad, k_pad, ldx if li == 0 else k_pad, act[0], act[1], self.nets, shared,
+                                  self.head_split if li == last else 1)
+                linear_bf16w(d, self.wt16[li], src, self.b[li], dst, 1 | (2 if li > 0 else 0) | (4 if li < last else 0))
+                src, shared = dst, 0
+            return src
         if tile_bufs is not None and last >= 1:
             for li, (m_pad, k_pad) in enumerate(self.dims):
                 dst = bufs[li % len(bufs)]
@@ -353,15 +415,29 @@ class FlowEngine:
         self._packed_for = None
         self._plans: Dict[int, dict] = {}
         self.graph = _GraphCache()
+        self.weights = "f32"               # "bf16": the MLPs read bf16 weight images (include/vunet_seq_bf16.h), inference only
 
     @property
     def flow(self):
         return self._flow()
 
+    def set_weights(self, mode: str):
+        """The weight precision of the MLP kernels.  A switch drops the other mode's images, the plans and the recorded graphs;
+        the next call packs the active mode's images."""
+        if check_weight_mode(mode) == self.weights:
+            return
+        self.weights = mode
+        self._packed_for = None
+        self._image_sig = None
+        self.blocks = []
+        self._plans.clear()
+        self.graph.graphs.clear()
+        self.graph.__dict__.pop("_warmed", None)
+
     # ---- weights
     def _pack(self, dev=None):
         params = list(self.flow.parameters()) + list(self.flow.buffers())
-        key = _versions(params)
+        key = (self.weights,) + _versions(params)
         if key == self._packed_for:
             return
         if dev is not None:
@@ -379,7 +455,7 @@ class FlowEngine:
             cp = blk.coupling
             halves = [MlpGroup([[(l.weight, l.bias) for l in cp.s[i].linears()], [(l.weight, l.bias) for l in cp.t[i].linears()]],
                                _up(c1, self.PAD), [True, False], split_head=True, pad_hidden=self.PAD, pad_out=self.PAD_OUT,
-                               tiled=self.TILED)
+                               tiled=self.TILED, weights=self.weights)
                       for i in range(2)]
             self.blocks.append(dict(
                 halves=halves, scale=blk.norm_layer.scale.detach().reshape(-1), loc=blk.norm_layer.loc.detach().reshape(-1),
@@ -388,7 +464,8 @@ class FlowEngine:
         self._all_init = False
         # a re-pack that finds every image where it was (parameters used in place, updated by an optimiser: their version
         # counters moved, their storage did not) keeps the buffers and the recordings, which hold nothing but pointers
-        sig = tuple(t.data_ptr() for blk in self.blocks for h in blk["halves"] for lay in (h.w + h.b + (h.wt or [])) for t in lay) + tuple(
+        sig = (self.weights,) + tuple(t.data_ptr() for blk in self.blocks for h in blk["halves"]
+                                      for lay in (h.w + h.b + (h.wt or []) + (h.wt16 or [])) for t in lay) + tuple(
             blk[k].data_ptr() for blk in self.blocks for k in ("scale", "loc", "fwd", "bwd"))
         if sig != getattr(self, "_image_sig", None):
             self._image_sig = sig
@@ -483,6 +560,8 @@ class FlowEngine:
 
     def _run(self, x: torch.Tensor, reverse: bool):
         _need_device(x)
+        if self.weights != "f32" and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.flow.parameters())):
+            raise RuntimeError(BF16_INFERENCE_ONLY)
         _inference_only(self.flow.parameters())
         _lib.lib()
         self._pack(x.device)

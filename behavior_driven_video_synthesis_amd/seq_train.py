@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from .ops import _call, _p, _stream
-from .seq import ACT_LRELU, FlowEngine, SeqCouplingDesc, _need_device, _up, padded_vector, weight_image  # noqa: F401
+from .seq import ACT_LRELU, BF16_INFERENCE_ONLY, FlowEngine, SeqCouplingDesc, _need_device, _up, padded_vector, weight_image  # noqa: F401
 
 LRELU_SLOPE = 0.01   # nn.LeakyReLU() default (lib/modules.py:244)
 
@@ -147,6 +147,8 @@ class FlowTrainEngine(FlowEngine):
 
     # ---- weights
     def _pack(self, dev=None):
+        if getattr(self.flow, "weight_precision", "f32") != "f32":   # (the inference engine's bf16 images: nothing here reads them)
+            raise RuntimeError(BF16_INFERENCE_ONLY)
         before = self._packed_for
         super()._pack(dev)
         if self._packed_for == before and getattr(self, "layers", None) is not None:
@@ -606,6 +608,8 @@ class _FlowFn(torch.autograd.Function):
 
 def flow_autograd(engine: FlowTrainEngine, x: torch.Tensor):
     """(z [B, C], logdet [B]) with a graph: the forward of the flow for a loop that calls ``backward()`` itself."""
+    if getattr(engine.flow, "weight_precision", "f32") != "f32":
+        raise RuntimeError(BF16_INFERENCE_ONLY)
     named = list(engine.flow.named_parameters())
     return _FlowFn.apply(engine, [n for n, _ in named], x, *[p for _, p in named])
 

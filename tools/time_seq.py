@@ -4,6 +4,12 @@ pass (1024 channels, 2048 hidden, depth 2, 15 blocks: 2.5 GB of fp32 weights) on
 (dim_hidden_b 1024, 51 pose dimensions).  HIP events around replayed graphs; weights are random (no checkpoint here).
 
     python tools/time_seq.py [--rows 16] [--flows 15] [--reps 20] [--eager]
+    python tools/time_seq.py --weights f32|bf16|both [--flows 15] [--reps 200] [--rounds 3]
+
+``--weights``: the flow's reverse and forward passes only, at 1, 16 and 64 rows, in the given weight mode(s) of the inference
+engine (``set_weight_precision``; include/vunet_seq_bf16.h) in ONE process: the modes alternate ``--rounds`` times, every round's
+time is kept (the spread) and the median reported, with the weight bytes the mode streams per pass and bytes/s.  One JSON line per
+mode and row count.
 """
 import argparse
 import json
@@ -28,6 +34,31 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def time_weight_modes(flow, modes, reps, rounds):
+    w_elems = sum(p.numel() for n, p in flow.named_parameters() if ".main." in n and n.endswith("weight"))
+    rows_list = (1, 16, 64)
+    eng = flow.flow.engine()
+    zs = {r: torch.randn(r, flow.in_channels, device="cuda") for r in rows_list}
+    times = {}
+    for _ in range(rounds):
+        for mode in modes:
+            flow.set_weight_precision(mode)
+            for r in rows_list:
+                for name, rev in (("reverse", True), ("forward", False)):
+                    times.setdefault((mode, r, name), []).append(timed(lambda: eng._run(zs[r], rev), reps))
+    for mode in modes:
+        w_bytes = w_elems * (2 if mode == "bf16" else 4)
+        for r in rows_list:
+            res = {"weights": mode, "rows": r, "flows": len(flow.flow.sub_layers), "reps": reps, "flow_weight_GB": round(w_bytes / 1e9, 3)}
+            for name in ("reverse", "forward"):
+                ts = sorted(times[(mode, r, name)])
+                med = ts[len(ts) // 2]
+                res[f"flow_{name}_ms"] = round(med, 4)
+                res[f"flow_{name}_ms_rounds"] = [round(t, 4) for t in times[(mode, r, name)]]
+                res[f"flow_{name}_weight_GBps"] = round(w_bytes / med / 1e6, 1)
+            print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=16)
@@ -35,6 +66,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--eager", action="store_true")
     ap.add_argument("--only", default=None, choices=[None, "reverse"], help="time the flow's reverse pass only (counter runs)")
+    ap.add_argument("--weights", default=None, choices=["f32", "bf16", "both"],
+                    help="time the flow's passes at 1, 16 and 64 rows in these weight modes (nothing else)")
+    ap.add_argument("--rounds", type=int, default=3, help="with --weights: how often the modes alternate")
     args = ap.parse_args()
     from behavior_driven_video_synthesis_amd.models.flow.simple_flow import UnsupervisedTransformer2
     from behavior_driven_video_synthesis_amd.models.pose_behavior_rnn import ResidualBehaviorNet
@@ -45,6 +79,11 @@ def main():
         for net in blk.coupling.s:
             net.linears()[-1].weight.data.mul_(0.1)
     flow = flow.cuda()
+    if args.weights is not None:
+        if args.eager:
+            flow.flow.engine().graph.enabled = False
+        time_weight_modes(flow, ["f32", "bf16"] if args.weights == "both" else [args.weights], args.reps, args.rounds)
+        return
     net = ResidualBehaviorNet(51, information_bottleneck=True, decoder_arch="lstm", linear_in_decoder=False, dim_hidden_b=1024).cuda()
     if args.eager:
         flow.flow.engine().graph.enabled = False
