@@ -87,6 +87,10 @@ class ShapePoseNet:
                              for i in range(arch["n_latent_scales"], 0, -1)]
             self.regressor = Regressor(n_keypoints * 2, latent_widths=latent_widths, **arch).to(self.device)
             self.optimizer_regressor = FusedAdam(list(self.regressor.parameters()), lr=0.001)
+        # opt-in: the side loop's inner steps on the probe's fused engine (reg_probe.RegProbeEngine) instead of the module's
+        # forward + autograd + FusedAdam.  Issued OUTSIDE a hipGraph capture of the outer step only (enable_hip_graph refuses).
+        self.fused_regressor = self.train_regressor and bool(tr.get("fused_regressor", False))
+        self._reg_engine = None
         # ---- adversarial term (models/synth_discriminator.py:115-242), optional
         gan = tr.get("gan") or {}
         self.gan = None
@@ -180,6 +184,9 @@ class ShapePoseNet:
             raise RuntimeError("hipGraph mode with data parallelism needs the gradient all-reduce on the C-ABI RCCL "
                                "communicator (vunet_dp_allreduce_bucket: an ordinary stream operation, capturable); this "
                                "averager runs on torch.distributed collectives -- run eagerly")
+        if self.fused_regressor:
+            raise RuntimeError("training.fused_regressor runs outside a hipGraph capture of the outer step only (its engine "
+                               "records its own step); switch one of the two off")
         if not self._dev_sched:
             self._lr_dev = torch.full((1,), self.lr, dtype=torch.float64, device=self.device)
             self._imax_dev = torch.full((), self.imax, dtype=torch.float32, device=self.device)
@@ -443,6 +450,12 @@ class ShapePoseNet:
             eps_all = None if reg_eps is None else [torch.cat([e[s_] for e in reg_eps], dim=0)
                                                      for s_ in range(len(reg_eps[0]))]
             _, means_all, _, _ = self.vunet.ed(self.vunet.eu(flat), eps_all)
+        if self.fused_regressor:
+            eng = self._regressor_engine()
+            for i in range(steps):
+                eng.step([m[i * b:(i + 1) * b] for m in means_all], reg_targets[:, i].reshape(b, -1))
+            eng.write_back()
+            return eng.last[0].clone()
         loss_regressor = None
         for i in range(steps):
             means = [m[i * b:(i + 1) * b] for m in means_all]
@@ -456,6 +469,31 @@ class ShapePoseNet:
             loss_regressor.backward()
             self.optimizer_regressor.step()
         return loss_regressor
+
+    def _regressor_engine(self):
+        if self._reg_engine is None:
+            self._reg_engine = self.regressor.probe_engine(lr=0.001)
+        return self._reg_engine
+
+    # ---- run_inference's post-hoc probe (:921-995)
+    def regressor_probe(self, batches, n_epochs: int = 20, lr: float = 1e-3, eps=None) -> dict:
+        """The disentanglement check at the end of ``run_inference``: a FRESH ``Regressor`` (:921-930) trained for ``n_epochs``
+        passes over ``batches`` to predict ``keypoints`` from the frozen VUnet's appearance ``means``, with ``Adam(lr)`` on
+        ``mean_b ||pred_b - kps_b||_2`` (:971-977) -- one recorded step per batch (reg_probe.RegProbeEngine).  Only ``eu`` / ``ed``
+        run per batch: the decoder pass, whose image the reference throws away, is not issued.  ``eps``: recorded latent noise
+        as on ``train_fn``.  -> {"loss": [n_steps] floats (what the reference plots), "regressor", "running_mean_100"}."""
+        from ..reg_probe import run_probe
+        arch, data = self.config["architecture"], self.config["data"]
+        latent_widths = [data["spatial_size"] // (2 ** (self.vunet.n_scales - i)) for i in range(arch["n_latent_scales"], 0, -1)]
+        first = next(iter(batches))
+        regressor = Regressor(first["keypoints"][0].numel(), latent_widths=latent_widths, **arch).to(self.device)
+        self.vunet.eval()                                                               # :936
+        key = "pose_img" if data.get("dataset", "Human3.6m") == "Human3.6m" else "pose_img_inplane"   # :960-963
+
+        def encode(batch, noise):
+            _, means, _, _ = self.vunet.ed(self.vunet.eu(batch[key].to(self.device)), noise)
+            return means
+        return run_probe(regressor, encode, batches, n_epochs, lr, eps)
 
     @torch.no_grad()
     def transfer(self, app_img, stickman, dtype: str = "f32"):
@@ -473,7 +511,8 @@ class ShapePoseNet:
             g["gamma"] = gamma
         sd = {"model": self.vunet.state_dict(), "optimizer": opt}
         if self.train_regressor:
-            sd["regressor"] = {"model": self.regressor.state_dict(), "optimizer": self.optimizer_regressor.state_dict()}
+            reg_opt = self._regressor_engine().optimizer_state_dict() if self.fused_regressor else self.optimizer_regressor.state_dict()
+            sd["regressor"] = {"model": self.regressor.state_dict(), "optimizer": reg_opt}
         if self.gan is not None:   # DiscTrainer's own save dict (models/synth_discriminator.py:228-231) rides along
             sd["discriminator"] = self.gan.checkpoint()
         return sd
@@ -497,8 +536,13 @@ class ShapePoseNet:
             self.adjust_params(self.iteration)
         if self.train_regressor and ckpt.get("regressor") is not None:
             self.regressor.load_state_dict(ckpt["regressor"]["model"])
+            if self.fused_regressor:
+                self._regressor_engine().load_module()
             if ckpt["regressor"].get("optimizer") is not None:
-                self.optimizer_regressor.load_state_dict(ckpt["regressor"]["optimizer"])
+                if self.fused_regressor:
+                    self._regressor_engine().load_optimizer_state_dict(ckpt["regressor"]["optimizer"])
+                else:
+                    self.optimizer_regressor.load_state_dict(ckpt["regressor"]["optimizer"])
         if self.gan is not None and "discriminator" in ckpt:
             self.gan.disc.load_state_dict(ckpt["discriminator"]["disc"])
             self.gan.opt.load_state_dict(ckpt["discriminator"]["opt"])

@@ -107,6 +107,25 @@ class Vunet:
         out.update({k: v.detach() for k, v in ld.items()})
         return out
 
+    # ---- run_inference's post-hoc probe (:745-805)
+    def regressor_probe(self, batches, n_epochs: int = 20, lr: float = 1e-3, eps=None) -> dict:
+        """As ``ShapePoseNet.regressor_probe``, over ``VunetOrg``: a fresh ``Regressor`` (:747-753) trained on the posterior
+        means of the model's own encoder (:779-787: ``vunet(pose_img_inplane, stickman)[1]``); the decoder pass is not issued.
+        ``linear_width_factor`` / ``n_linear`` default to 1 / 2 where the architecture section does not name them."""
+        from ..models.vunets import Regressor
+        from ..reg_probe import run_probe
+        arch, data = dict(linear_width_factor=1, n_linear=2), self.config["data"]
+        arch.update(self.config["architecture"])
+        latent_widths = [data["spatial_size"] // (2 ** (self.vunet.n_scales - i)) for i in range(arch["n_latent_scales"], 0, -1)]
+        first = next(iter(batches))
+        regressor = Regressor(first["keypoints"][0].numel(), latent_widths=latent_widths, **arch).to(self.device)
+        self.vunet.eval()                                                               # :757
+
+        def encode(batch, noise):
+            _, qs, _ = self.vunet.ed(self.vunet.eu(batch.get("pose_img_inplane", batch["pose_img"]).to(self.device)), noise)
+            return qs
+        return run_probe(regressor, encode, batches, n_epochs, lr, eps)
+
     def state_dict(self):
         return {"model": self.vunet.state_dict(), "optimizer": self.optimizer.state_dict()}
 

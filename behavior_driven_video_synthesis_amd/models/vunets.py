@@ -480,3 +480,10 @@ class Regressor(nn.Module):
         for i, lin in enumerate(self.linears):
             h = lin.fused(h, out_act=ops.ACT_NONE if i == last else ops.ACT_RELU)
         return h.reshape(h.shape[0], -1)
+
+    def probe_engine(self, lr: float = 1e-3, n_steps: int = 0):
+        """The fused training step over this module's own parameters (reg_probe.RegProbeEngine): forward, the probe's loss,
+        backward and Adam as one recorded launch sequence.  The engine updates the parameters in place and owns Adam's moments;
+        ``forward``, the state-dict keys and shapes are untouched."""
+        from ..reg_probe import RegProbeEngine
+        return RegProbeEngine(self, lr=lr, n_steps=n_steps)
