@@ -10,7 +10,13 @@
 and friends resolve to the HIP-backed classes without a single edited line.  ``UnsupervisedTransformer2`` and
 ``ResidualBehaviorNet`` train under autograd on this path (``experiments/behavior_net.py:591-714``: csrc/seq_train.hip,
 csrc/seq_bptt.hip), so an unchanged ``main.py --config config/behavior_net.yaml`` runs both of its stages -- with
-``use_regressor: False``.  The shipped YAML's ``use_regressor: True`` does not run through the drop-in: the reference's own
+``use_regressor: False``.  The cVAE stage's ``train_fn`` keeps three passes of the net alive per iteration (:616, :627 -- never
+used --, :681 after the optimiser's step, back-propagated through ``classifier_beta``): the net's training engine keeps up to
+``max_passes`` (4) passes of one shape in flight, each in buffers of its own until its autograd node dies, allows
+``backward(retain_graph=True)``, and refuses a backward whose parameters were modified since its forward (``seq_train``,
+``seq_passes``); the flow's engine, whose stage runs one pass per iteration, does the same with
+``max_passes`` 1 by default (a second forward replaces the first pass).  The action classifiers stay the checkout's torch
+modules.  The shipped YAML's ``use_regressor: True`` does not run through the drop-in: the reference's own
 regressor code raises on torch >= 1.5 before any of this package's kernels are reached (it steps the regressor in place between
 the loss's forward and backward); that configuration trains through ``experiments.behavior_net.BehaviorNet``.  Each alias is a
 HYBRID module: names this package defines come from here -- except ``HIDDEN`` ones, the flat-input building blocks of

@@ -23,9 +23,15 @@ import torch
 
 from . import _lib
 from .ops import _call, _p, _stream
-from .seq import ACT_LRELU, BF16_INFERENCE_ONLY, FlowEngine, SeqCouplingDesc, _need_device, _up, padded_vector, weight_image  # noqa: F401
+from .seq import (ACT_LRELU, BF16_INFERENCE_ONLY, FlowEngine, SeqCouplingDesc, _need_device, _up, _versions, padded_vector,  # noqa: F401
+                  weight_image)
+from .seq_passes import PassPool
 
 LRELU_SLOPE = 0.01   # nn.LeakyReLU() default (lib/modules.py:244)
+
+STALE_WEIGHTS = ("the {}'s parameters were modified between this pass's forward and its backward (an optimiser step, a "
+                 "load_state_dict, an in-place operation): its saved activations belong to the weights before.  Run the backward "
+                 "before the step, or run the forward again")
 
 
 class SeqAdamHp(ctypes.Structure):
@@ -124,7 +130,9 @@ class FlowTrainEngine(FlowEngine):
         self._adam_args = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.adam: Optional[AdamState] = None
         self._moments: Dict[str, tuple] = {}
-        self._generation = 0
+        # autograd's passes in flight (seq_passes).  The flow stage runs one pass per iteration (experiments/behavior_net.py:707-710):
+        # by default one pass at a time, a second forward REPLACES the first one's activations; ``max_passes`` > 1 keeps several
+        self._passes = PassPool(1, "the flow")
         # the update sweep beside the next half's chain on a second stream: measured slower (8.1 vs 7.75 ms per step: the sweep's
         # 5120 workgroups hold every CU, the chain's 1024-thread workgroups wait for room) -- off unless asked for
         self.two_streams = os.environ.get("VUNET_SEQ_TRAIN_STREAMS", "1") == "2"
@@ -186,9 +194,22 @@ class FlowTrainEngine(FlowEngine):
             lay.moments()
             self._moments[lay.name] = (lay.m, lay.v, lay.bm, lay.bv)
 
+    @property
+    def max_passes(self) -> int:
+        """How many forward passes of one batch size may be alive (under autograd) at the same time, each in a plan of its own.
+        1, the default: a forward takes the one plan whether or not an earlier pass is alive, and that pass's backward raises."""
+        return self._passes.max_passes
+
+    @max_passes.setter
+    def max_passes(self, n: int):
+        self._passes.max_passes = int(n)
+
     # ---- buffers
-    def _plan(self, rows: int) -> dict:
-        p = self._plans.get(("train", rows))
+    def _plan(self, rows: int, slot: int = 0) -> dict:
+        """Slot 0 is the fused step's plan (``train_step``: its recorded graph points into it) and the first autograd pass's;
+        slot k > 0 is allocated when k + 1 autograd passes of ``rows`` rows are alive."""
+        key = ("train", rows) if slot == 0 else ("train", rows, slot)
+        p = self._plans.get(key)
         if p is not None:
             return p
         dev = self.blocks[0]["scale"].device
@@ -215,7 +236,7 @@ class FlowTrainEngine(FlowEngine):
         p["raw"] = z(max(h0.nets * s * b_pad * k for s, (_, k) in zip(p["S"], h0.dims)))
         p["dx_cnt"] = torch.zeros(h0.nets * max(k for (_, k) in h0.dims) // 64, dtype=torch.int32, device=dev)   # vunet_seq_dx_finish
         p["raw_in"] = [z(h0.nets * p["S"][0] * b_pad * h0.dims[0][1]) for _ in range(2)]
-        self._plans[("train", rows)] = p
+        self._plans[key] = p
         return p
 
     @staticmethod
@@ -485,23 +506,38 @@ class FlowTrainEngine(FlowEngine):
         return p["scalars"]
 
     # ---- autograd's view of the same kernels
+    def _param_versions(self) -> tuple:
+        return _versions(list(self.flow.parameters()) + list(self.flow.buffers()))
+
     def train_forward(self, x: torch.Tensor):
+        """-> (z, logdet, token).  With ``max_passes`` > 1 the pass takes the lowest free slot of its batch size and keeps that
+        plan until ``token`` (held by the autograd node) is collected, as the behaviour net's passes do.  With ``max_passes`` 1
+        (the default) there is one plan and no waiting for it: a forward takes it whether or not an earlier pass is alive, and
+        that pass's backward then raises.  Either way ``train_backward(token, ...)`` may run any number of times, and the token
+        carries the plan itself: its buffers stay valid when a re-pack clears ``_plans``."""
         x2 = self._check_input(x.detach())
         rows = x2.shape[0]
         self._initialise_actnorm(x2)
-        p = self._plan(rows)
+        lease = self._passes.lease(rows) if self._passes.max_passes > 1 else None
+        p = self._plan(rows, lease.slot if lease is not None else 0)
         p["x_in"].copy_(x2)
         self._issue_train_forward(rows, p)
-        self._generation += 1
-        return p["x_out"].clone(), p["logdet"][:rows].clone(), (rows, self._generation)
+        p["pass"] = p.get("pass", 0) + 1      # which forward the plan's activations belong to
+        return p["x_out"].clone(), p["logdet"][:rows].clone(), (p, lease, rows, p["pass"], self._param_versions())
 
     def train_backward(self, token, gz: Optional[torch.Tensor], gld: Optional[torch.Tensor]):
-        """-> (dx [B, C], {parameter name: gradient}) for the forward pass ``token`` came from."""
-        rows, gen = token
-        if gen != self._generation:
-            raise RuntimeError("the flow was run again before this pass's backward: its saved activations are gone "
-                               "(one forward / backward pair at a time)")
-        p = self._plan(rows)
+        """-> (dx [B, C], {parameter name: gradient}) for the forward pass ``token`` came from.  The pass is not spent: every
+        buffer the chain writes is written anew by each run, so a second call returns the same bits.  Parameters that were
+        modified since the forward are refused, as torch refuses them (the kernels read the weights in place: the gradients would
+        be those of another function).  ``train_step``'s fused Adam writes through a kernel and moves no version counter: mixing it
+        with passes under autograd goes undetected."""
+        p, _, rows, pass_id, versions = token
+        if pass_id != p["pass"]:
+            raise RuntimeError("the flow was run again before this pass's backward: its saved activations are gone (with max_passes "
+                               "= 1, the default, the engine keeps one forward pass at a time: raise its max_passes attribute to keep "
+                               "several in flight)")
+        if versions != self._param_versions():
+            raise RuntimeError(STALE_WEIGHTS.format("flow"))
         dev = p["x_in"].device
         p["dzl"].zero_()
         if gz is not None:
@@ -525,7 +561,6 @@ class FlowTrainEngine(FlowEngine):
             gs, gl = grads[f"sub_layers.{bi}.norm_layer"]
             out[f"sub_layers.{bi}.norm_layer.scale"] = gs.reshape(1, self.C, 1, 1)
             out[f"sub_layers.{bi}.norm_layer.loc"] = gl.reshape(1, self.C, 1, 1)
-        self._generation += 1      # the activations are spent
         return p["dx"].clone(), out
 
     # ---- torch.optim.Adam's state layout (checkpoints: experiments/behavior_net.py:392-393, :1003-1011)
@@ -629,13 +664,24 @@ class BehaviorTrainEngine(BehaviorEngine):
     state and gate activations kept, and its backward pass: back-propagation through time over the decoder's roll-out and the
     encoder's LSTM (csrc/seq_bptt.hip + the matrix kernels of csrc/seq_train.hip).  One batch of <= 64 rows
     (config/behavior_net.yaml: 64).  Gradients are written in torch's parameter layout -- into the ``.grad`` views of the fused
-    optimiser (``experiments.behavior_net``) or into fresh tensors for autograd (``behavior_autograd``)."""
+    optimiser (``experiments.behavior_net``) or into fresh tensors for autograd (``behavior_autograd``).
+
+    Under autograd several passes may be alive at once, as in the reference's ``train_fn`` (experiments/behavior_net.py:616, :627,
+    :681: three calls of one shape per iteration): every pass keeps a plan of its own -- the lowest free slot of its shape,
+    ``seq_passes.PassPool``; slot k is allocated when k + 1 passes of that shape are alive, at most ``max_passes`` (4) -- until its
+    autograd node dies, and its backward may run more than once (``retain_graph=True``).  A backward after the parameters were
+    modified raises, as torch's does.  ``optim.FusedAdam`` writes through a raw kernel and moves no version counter: mixing the
+    fused optimiser (or ``experiments.behavior_net.BehaviorNet``'s fused step, which works in slot 0 without taking it) with
+    passes under autograd goes undetected, and so does a write through ``p.data``.  The weight images are re-packed when a
+    counter moved, not on every pass: after such an uncounted write the next forward under autograd would run on the OLD
+    images -- whoever writes that way sets ``_packed_for = None`` on this engine afterwards, as ``BehaviorNet``'s fused step
+    does (experiments/behavior_net.py, ``_cvae_step``)."""
 
     HOFF_PAD = 64
 
     def __init__(self, net):
         super().__init__(net)
-        self._generation = 0
+        self._passes = PassPool(4, "the behaviour net")
         # h handed from LSTM step to LSTM step as tiles too (vunet_seq_lstm_gates_tiled_h; batches of more than 32 rows);
         # "0": the step reads its whole operand from the row-major rows (bit-identical)
         self.tile_h = os.environ.get("VUNET_SEQ_LSTM_TILED_H", "1") != "0"
@@ -652,8 +698,18 @@ class BehaviorTrainEngine(BehaviorEngine):
         if self.H % 64:
             raise ValueError("dim_hidden_b must be a multiple of 64 for training on the HIP path")
 
-    def _tplan(self, rows: int, t_in: int, t2: int, length: int) -> dict:
-        key = ("train", rows, t_in, t2, length)
+    @property
+    def max_passes(self) -> int:
+        """How many forward passes of one shape may be alive (under autograd) at the same time: each keeps a plan."""
+        return self._passes.max_passes
+
+    @max_passes.setter
+    def max_passes(self, n: int):
+        self._passes.max_passes = int(n)
+
+    def _tplan(self, rows: int, t_in: int, t2: int, length: int, slot: int = 0) -> dict:
+        """Slot 0 is the fused step's plan (its recorded graph points into it) and the first autograd pass's."""
+        key = ("train", rows, t_in, t2, length) + ((slot,) if slot else ())
         p = self._plans.get(key)
         if p is not None:
             return p
@@ -733,14 +789,21 @@ class BehaviorTrainEngine(BehaviorEngine):
                   _p(p["xraw"]), ctypes.c_void_p(xs.data_ptr() + t * n * esz), ctypes.c_void_p(cs.data_ptr() + t * n * esz), _stream())
 
     # ---- backward
-    def _issue_train_backward(self, rows, p, t_in, length, sample_prior: bool, gpre: Optional[torch.Tensor] = None):
+    def _issue_train_backward(self, rows, p, t_in, length, sample_prior: bool, gpre: Optional[torch.Tensor] = None,
+                              decoder: bool = True):
         """``p['gxs']`` = d loss / d xs, ``p['gmu']`` / ``p['glogstd']`` = the loss's direct gradients wrt the heads.  Leaves the
-        weight gradients as images in ``p`` (``_unpack_grads`` turns them into torch's layout)."""
+        weight gradients as images in ``p`` (``_unpack_grads`` turns them into torch's layout).  Every buffer the chain reads is
+        written by the chain first (``gc`` starts from zero by the ``first`` flags, the slabs and dgates are stored, not added
+        to): the pass can be run again.  ``decoder`` False: nothing reaches the roll-out (the loss sees mu / logstd / pre only) --
+        its 2 x length launches are skipped and what they would have left, all zeros, is filled in."""
         dec = self.net.decoder
         n, H, esz = self.n, self.H, 4
         s_d, s_e, s_h = p["S"]
         w_out = dec.n_out.weight.detach()
-        for t in reversed(range(length)):
+        if not decoder:
+            for k in ("raw_d", "gc", "dgates_d", "gx"):
+                p[k].zero_()
+        for t in reversed(range(length if decoder else 0)):
             first = t == length - 1
             d = SeqCellBwdDesc(rows, H, n, s_d, self.ldx, self.hoff, 3 if first else 0, 0, length * n)
             _call("vunet_seq_cell_bwd", ctypes.byref(d), None if first else _p(p["raw_d"]), _p(w_out),
@@ -800,21 +863,20 @@ class BehaviorTrainEngine(BehaviorEngine):
         if x1.shape[2] != self.n or x2.shape[2] != self.n or x2.shape[0] != rows:
             raise ValueError(f"forward: sequences {tuple(x1.shape)}, {tuple(x2.shape)} for {self.n} pose dimensions")
         start_frame = start_frame % t2
-        p = self._tplan(rows, t_in, t2, length)
+        lease = self._passes.lease((rows, t_in, t2, length))
+        p = self._tplan(rows, t_in, t2, length, lease.slot)
         p["x1"].copy_(x1)
         p["x2"].copy_(x2)
         p["eps"].copy_(eps)
-        self._fill_images()
+        # (the weight images are those of the parameters as they are: ``_check`` -> ``_pack`` re-filled them if a version moved)
         self._issue_train_forward(rows, p, t_in, t2, length, start_frame, sample_prior)
-        self._generation += 1
-        return p, (rows, t_in, t2, length, sample_prior, self._generation)
+        return p, (p, lease, rows, t_in, length, sample_prior, _versions(list(self.net.parameters())))
 
     def train_backward(self, token, gxs, gcs, gb, gmu, glogstd, gpre):
-        rows, t_in, t2, length, sample_prior, gen = token
-        if gen != self._generation:
-            raise RuntimeError("the net was run again before this pass's backward: its saved activations are gone "
-                               "(one forward / backward pair at a time)")
-        p = self._tplan(rows, t_in, t2, length)
+        """{parameter name: gradient} of the pass ``token`` came from; the pass is not spent (``retain_graph=True``)."""
+        p, _, rows, t_in, length, sample_prior, versions = token
+        if versions != _versions(list(self.net.parameters())):
+            raise RuntimeError(STALE_WEIGHTS.format("behaviour net"))
         p["gxs"].zero_()
         if gxs is not None:
             p["gxs"].copy_(gxs)
@@ -829,10 +891,10 @@ class BehaviorTrainEngine(BehaviorEngine):
         if gb is not None and not sample_prior:   # b = eps exp(logstd) + mu
             p["gmu"].add_(gb)
             p["glogstd"].add_(gb * p["eps"] * torch.exp(p["logstd"]))
-        self._issue_train_backward(rows, p, t_in, length, sample_prior, gpre)
+        self._issue_train_backward(rows, p, t_in, length, sample_prior, gpre,
+                                   decoder=not (gxs is None and gcs is None and gb is None))
         out = {n: torch.empty_like(q) for n, q in self.net.named_parameters()}
         self._unpack_grads(p, out)
-        self._generation += 1
         return out
 
 
