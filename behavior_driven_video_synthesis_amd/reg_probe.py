@@ -21,14 +21,15 @@ There is no CPU path.
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Sequence
 
 import torch
 
 from . import _lib
 from .ops import _call, _p, _stream
 from .seq import ACT_NONE, SeqLinearDesc, _GraphCache, _need_device, _need_module_on, _up, linear
-from .seq_train import ACT_RELU_SEQ, AdamState, FlowTrainEngine, SeqDwLayer, SeqDxDesc, _table
+from .seq_train import (ACT_RELU_SEQ, AdamState, SeqDxDesc, TrainLayer, _table, adam_state_dict, dx_chain, dx_split,
+                        load_adam_state)
 
 MAX_SCALES = 2
 TOO_MANY_SCALES = "the fused regressor engine covers at most two latent scales; the module route still serves more"
@@ -40,65 +41,6 @@ def split_k(m: int, k: int) -> int:
     chunks = k // 64
     want = max(1, min(chunks, 256 // max(1, m // 16)))
     return max(s for s in range(1, want + 1) if chunks % s == 0)
-
-
-class _Layer:
-    """One layer's operand images (the parameter itself where its shape fits) and Adam's moments."""
-
-    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor, pieces: Sequence[tuple], kp: int):
-        """``pieces``: (first column of the parameter's matrix, columns, first column in the image) per column block."""
-        w2 = weight.data.reshape(weight.shape[0], -1)
-        self.name, self.weight, self.bias_p, self.pieces = name, weight, bias, list(pieces)
-        self.m, self.k = w2.shape
-        self.mp, self.kp = _up(self.m, 64), kp
-        self.inplace = (self.mp, self.kp) == (self.m, self.k) and w2.is_contiguous() and bias.data.is_contiguous()
-        if self.inplace:
-            self.w, self.b = w2, bias.data
-        else:
-            self.w = torch.zeros(self.mp, self.kp, device=weight.device)
-            self.b = torch.zeros(self.mp, device=weight.device)
-            self.load()
-        self.mw, self.vw = torch.zeros_like(self.w), torch.zeros_like(self.w)
-        self.mb, self.vb = torch.zeros_like(self.b), torch.zeros_like(self.b)
-
-    def load(self):
-        if self.inplace:
-            return
-        w2 = self.weight.data.reshape(self.m, -1)
-        for src, n, dst in self.pieces:
-            self.w[:self.m, dst:dst + n].copy_(w2[:, src:src + n])
-        self.b[:self.m].copy_(self.bias_p.data)
-
-    def write_back(self):
-        if self.inplace:
-            return
-        w2 = self.weight.data.reshape(self.m, -1)
-        for src, n, dst in self.pieces:
-            w2[:, src:src + n].copy_(self.w[:self.m, dst:dst + n])
-        self.bias_p.data.copy_(self.b[:self.m])
-
-    def _gather(self, img: torch.Tensor) -> torch.Tensor:
-        out = torch.empty(self.m, self.k, device=img.device)
-        for src, n, dst in self.pieces:
-            out[:, src:src + n].copy_(img[:self.m, dst:dst + n])
-        return out.reshape(self.weight.shape)
-
-    def _scatter(self, img: torch.Tensor, val: torch.Tensor):
-        v2 = val.to(img.device, torch.float32).reshape(self.m, self.k)
-        for src, n, dst in self.pieces:
-            img[:self.m, dst:dst + n].copy_(v2[:, src:src + n])
-
-    def moments(self):
-        """-> [(exp_avg, exp_avg_sq) of the weight, of the bias] in the parameters' own shapes."""
-        return [(self._gather(self.mw), self._gather(self.vw)), (self.mb[:self.m].clone(), self.vb[:self.m].clone())]
-
-    def set_moments(self, w_state: Optional[dict], b_state: Optional[dict]):
-        if w_state is not None:
-            self._scatter(self.mw, w_state["exp_avg"])
-            self._scatter(self.vw, w_state["exp_avg_sq"])
-        if b_state is not None:
-            self.mb[:self.m].copy_(b_state["exp_avg"].reshape(-1))
-            self.vb[:self.m].copy_(b_state["exp_avg_sq"].reshape(-1))
 
 
 class RegProbeEngine:
@@ -130,29 +72,29 @@ class RegProbeEngine:
     def load_module(self):
         """(Re)build the training state from the module's parameters; Adam's moments and step count are reset."""
         r = self.reg
-        self.emb: List[_Layer] = []
+        self.emb: List[TrainLayer] = []
         pieces, off = [], 0
         for i, e in enumerate(r.embedders):
             m, k = e.weight.shape[0], e.weight[0].numel()
             if k % 64:
                 raise ValueError(f"embedder {i} reads {k} values per sample: the split-K kernel takes multiples of 64")
-            self.emb.append(_Layer(f"embedders.{i}", e.weight, e.bias, [(0, k, 0)], k))
+            self.emb.append(TrainLayer(f"embedders.{i}", e.weight, e.bias))
             pieces.append((i * m, m, off))
             off += _up(m, 64)
         self.ldc = off                                                   # the concat operand: one 64-padded block per embedder
-        self.lin: List[_Layer] = []
+        self.lin: List[TrainLayer] = []
         kp = self.ldc
         for i, lin_ in enumerate(r.linears):
-            pc = pieces if i == 0 else [(0, lin_.weight.shape[1], 0)]
+            pc = pieces if i == 0 else None
             if i == 0 and sum(n for _, n, _ in pc) != lin_.weight.shape[1]:
                 raise ValueError("the first linear layer does not read the concatenated embeddings")
-            self.lin.append(_Layer(f"linears.{i}", lin_.weight, lin_.bias, pc, kp))
+            self.lin.append(TrainLayer(f"linears.{i}", lin_.weight, lin_.bias, pc, kp))
             kp = self.lin[-1].mp
         self.n_out = r.linears[-1].weight.shape[0]
         self.adam.step_dev.zero_()
         self._reset_recordings()
 
-    def layers(self) -> List[_Layer]:
+    def layers(self) -> List[TrainLayer]:
         return self.emb + self.lin
 
     def write_back(self):
@@ -161,8 +103,7 @@ class RegProbeEngine:
 
     def _reset_recordings(self):
         self._plans.clear()
-        self.graph.graphs.clear()
-        self.graph.__dict__.pop("_warmed", None)
+        self.graph.clear()
 
     def reserve(self, n_steps: int):
         """A fresh loss course of ``n_steps`` entries (the recorded steps hold the old buffer's address: they are dropped)."""
@@ -182,35 +123,29 @@ class RegProbeEngine:
         z = lambda *s: torch.zeros(*s, device=self.dev)   # noqa: E731
         p = dict(b_pad=bp, x=[z(bp, e.k) for e in self.emb], cat=z(bp, self.ldc), dcat=z(bp, self.ldc),
                  y=[z(bp, lay.mp) for lay in self.lin], dz=[z(bp, lay.mp) for lay in self.lin], tgt=z(rows, self.n_out),
-                 S_emb=[split_k(_up(e.m, 16), e.k) for e in self.emb],
-                 S_dx=[FlowTrainEngine._dx_split(lay.mp, lay.kp, 1) for lay in self.lin])
-        p["part"] = z(max(s * bp * _up(e.m, 16) for s, e in zip(p["S_emb"], self.emb)))
+                 S_emb=[split_k(_up(e.rows, 16), e.k) for e in self.emb],
+                 S_dx=[dx_split(lay.mp, lay.kp, 1) for lay in self.lin])
+        p["part"] = z(max(s * bp * _up(e.rows, 16) for s, e in zip(p["S_emb"], self.emb)))
         p["raw"] = z(max(s * bp * lay.kp for s, lay in zip(p["S_dx"], self.lin)))
         # the update sweep: every layer in one launch.  An embedder's dZ is its column block of the concat operand's gradient.
         entries, tile, off = [], 0, 0
         for e, x in zip(self.emb, p["x"]):
-            entries.append(self._dw_entry(e, p["dcat"].data_ptr() + 4 * off, self.ldc, x, e.k, tile))
-            tile += (e.mp // 64) * (e.kp // 64)
+            entries.append(e.dw_entry(p["dcat"].data_ptr() + 4 * off, self.ldc, x.data_ptr(), e.k, tile))
+            tile += e.tiles()
             off += e.mp
         for i, lay in enumerate(self.lin):
             x = p["cat"] if i == 0 else p["y"][i - 1]
-            entries.append(self._dw_entry(lay, p["dz"][i].data_ptr(), lay.mp, x, lay.kp, tile))
-            tile += (lay.mp // 64) * (lay.kp // 64)
+            entries.append(lay.dw_entry(p["dz"][i].data_ptr(), lay.mp, x.data_ptr(), lay.kp, tile))
+            tile += lay.tiles()
         p["dw"] = dict(table=_table(entries, self.dev), n=len(entries), tiles=tile)
         self._plans[rows] = p
         return p
-
-    @staticmethod
-    def _dw_entry(lay: _Layer, dz_ptr: int, ldz: int, x: torch.Tensor, ldx: int, tile: int) -> SeqDwLayer:
-        return SeqDwLayer(lay.w.data_ptr(), lay.mw.data_ptr(), lay.vw.data_ptr(), None, lay.b.data_ptr(), lay.mb.data_ptr(),
-                          lay.vb.data_ptr(), None, dz_ptr, x.data_ptr(), lay.mp, lay.kp, ldz, ldx, tile, lay.kp // 64, lay.kp, 1, 0, 0,
-                          None)
 
     # ---- the launch sequence
     def _issue_forward(self, rows: int, p: dict):
         off = 0
         for e, x, s in zip(self.emb, p["x"], p["S_emb"]):
-            m16 = _up(e.m, 16)
+            m16 = _up(e.rows, 16)
             _call("vunet_reg_probe_embed", _p(x), _p(e.w), rows, m16, e.k, s, _p(p["part"]), _stream())
             _call("vunet_reg_probe_embed_finish", _p(p["part"]), s, _p(e.b), rows, m16, _p(p["cat"]), self.ldc, off, _stream())
             off += e.mp
@@ -221,16 +156,14 @@ class RegProbeEngine:
                    [lay.b], p["y"][i])
 
     def _issue_step(self, rows: int, p: dict):
-        bp, last = p["b_pad"], len(self.lin) - 1
+        last = len(self.lin) - 1
         self._issue_forward(rows, p)
         _call("vunet_reg_probe_loss", _p(p["y"][last]), self.lin[last].mp, _p(p["tgt"]), self.n_out, rows, self.n_out, _p(p["dz"][last]),
               _p(self.last), _p(self.losses_dev) if self.cap else None, self.cap, _p(self.cursor), _stream())
         for i in range(last, -1, -1):          # input gradients on the weights before this step's update
-            lay, s = self.lin[i], p["S_dx"][i]
-            d = SeqDxDesc(rows, lay.mp, lay.kp, 1, s, 0)
-            _call("vunet_seq_dx", ctypes.byref(d), _p(lay.w), None, _p(p["dz"][i]), _p(p["raw"]), _stream())
-            y_prev, dz_prev = (p["cat"], p["dcat"]) if i == 0 else (p["y"][i - 1], p["dz"][i - 1])
-            _call("vunet_seq_dz_finish", _p(p["raw"]), _p(y_prev), _p(dz_prev), 1, s, bp, lay.kp, 0.0, _stream())
+            lay = self.lin[i]
+            dx_chain(SeqDxDesc(rows, lay.mp, lay.kp, 1, p["S_dx"][i], 0), [lay.w], p["dz"][i], p["raw"],
+                     (p["cat"], p["dcat"]) if i == 0 else (p["y"][i - 1], p["dz"][i - 1]))
         self.adam.tick()
         _call("vunet_seq_dw", _p(p["dw"]["table"]), p["dw"]["n"], 0, p["dw"]["tiles"], rows, ctypes.byref(self.adam.hp), _stream())
 
@@ -270,30 +203,14 @@ class RegProbeEngine:
 
     # ---- torch.optim.Adam's state layout over ``reg.parameters()`` (embedders, then linears: weight, bias each)
     def optimizer_state_dict(self) -> dict:
-        step = self.adam.step
-        moments = [mv for lay in self.layers() for mv in lay.moments()]
-        state = {i: {"step": torch.tensor(float(step)), "exp_avg": m, "exp_avg_sq": v} for i, (m, v) in enumerate(moments)} if step else {}
-        a = self.adam
-        group = {"lr": a.lr, "betas": a.betas, "eps": a.eps, "weight_decay": 0.0, "amsgrad": False, "maximize": False, "foreach": None,
-                 "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(moments)))}
-        return {"state": state, "param_groups": [group]}
+        return adam_state_dict(self.adam, self.adam.step, [mv for lay in self.layers() for mv in lay.moments()])
 
     def load_optimizer_state_dict(self, sd: dict):
-        group = sd["param_groups"][0]
-        a = self.adam
-        a.set_lr(group["lr"])
-        a.betas, a.eps = tuple(float(b) for b in group["betas"]), float(group["eps"])
-        a.hp.beta1, a.hp.beta2, a.hp.eps = a.betas[0], a.betas[1], a.eps
-        step = 0
+        states, step = load_adam_state(self.adam, sd)
         for i, lay in enumerate(self.layers()):
-            ws, bs = sd["state"].get(2 * i), sd["state"].get(2 * i + 1)
-            lay.set_moments(ws, bs)
-            for st in (ws, bs):
-                if st is not None:
-                    step = int(st["step"])
-        a.step_dev.fill_(step)
-        self.graph.graphs.clear()      # the hyper-parameters are launch arguments of the recorded step
-        self.graph.__dict__.pop("_warmed", None)
+            lay.set_moments(states[2 * i], states[2 * i + 1])
+        self.adam.step_dev.fill_(step)
+        self.graph.clear()      # the hyper-parameters are launch arguments of the recorded step
 
 
 # ================================================================================================

@@ -325,6 +325,7 @@ class _GraphCache:
         self.enabled = os.environ.get("VUNET_SEQ_GRAPH", "1") != "0"
         self._stream = None
         self.on_evict = None    # weakref.WeakMethod called with the key of a recording that is dropped (its buffers go too)
+        self._warmed: set = set()   # run_step's keys that were issued eagerly once: the next call records
 
     def run(self, key, issue):
         if not self.enabled or torch.cuda.is_current_stream_capturing():   # (inside someone else's capture: become part of it)
@@ -360,9 +361,8 @@ class _GraphCache:
         if key in self.graphs and self.enabled and not torch.cuda.is_current_stream_capturing():
             self.graphs[key].replay()
             return "replayed"
-        warmed = self.__dict__.setdefault("_warmed", set())
-        if not self.enabled or torch.cuda.is_current_stream_capturing() or key not in warmed:
-            warmed.add(key)
+        if not self.enabled or torch.cuda.is_current_stream_capturing() or key not in self._warmed:
+            self._warmed.add(key)
             issue()
             return "eager"
         torch.cuda.synchronize()
@@ -382,6 +382,12 @@ class _GraphCache:
         self.graphs[key] = g
         g.replay()
         return "captured"
+
+    def clear(self):
+        """Forget every recording and which keys ``run_step`` has warmed up (the next call of each key is issued eagerly again).
+        ``on_evict`` is not called: the callers drop their plans themselves."""
+        self.graphs.clear()
+        self._warmed.clear()
 
     def drop(self, key):
         if self.graphs.pop(key, None) is not None and self.on_evict is not None:
@@ -431,8 +437,7 @@ class FlowEngine:
         self._image_sig = None
         self.blocks = []
         self._plans.clear()
-        self.graph.graphs.clear()
-        self.graph.__dict__.pop("_warmed", None)
+        self.graph.clear()
 
     # ---- weights
     def _pack(self, dev=None):
@@ -470,8 +475,7 @@ class FlowEngine:
         if sig != getattr(self, "_image_sig", None):
             self._image_sig = sig
             self._plans.clear()
-            self.graph.graphs.clear()
-            self.graph.__dict__.pop("_warmed", None)
+            self.graph.clear()
 
     def _plan(self, rows: int) -> dict:
         p = self._plans.get(rows)
@@ -666,8 +670,7 @@ class BehaviorEngine:
             self.heads = ([z(self.H, self.H) for _ in range(2)], [z(self.H) for _ in range(2)]) if enc.ib else None
             self.head_rs = [z(self.H) for _ in range(2)] if enc.ib else None
             self._plans.clear()
-            self.graph.graphs.clear()
-            self.graph.__dict__.pop("_warmed", None)
+            self.graph.clear()
         self._fill_images()
         self._packed_for = key
 

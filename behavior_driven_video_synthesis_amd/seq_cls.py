@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .ops import _call, _p, _stream
+from .seq_train import SeqAdamHp
 
 NIN, KP, HID, G3 = 51, 64, 256, 768
 OFF_WHH = G3 * KP
@@ -34,12 +35,6 @@ class GemmDesc(ctypes.Structure):
                 ("mask", ctypes.c_void_p)] + [(f, ctypes.c_int64) for f in (
                     "a_net", "a_m", "a_k", "b_net", "b_k", "b_n", "c_net", "c_m", "c_n", "c_split", "bias_net", "mask_net", "mask_m")] + [
                 (f, ctypes.c_int32) for f in ("M", "N", "K", "nets", "split", "relu", "accumulate", "pad")]
-
-
-class AdamHp(ctypes.Structure):
-    """vunet_seq_adam_hp (include/vunet_seq_train.h)."""
-    _fields_ = [("lr_dev", ctypes.c_void_p), ("step_dev", ctypes.c_void_p), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
-                ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float), ("resolved_dev", ctypes.c_void_p)]
 
 
 def _ptr(t: torch.Tensor, off: int = 0) -> int:
@@ -157,7 +152,7 @@ class StudyEngine:
         self.de = torch.zeros(nt, self.L, **f32)
         self.adam_step = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr = torch.full((1,), 1e-3, dtype=torch.float64, device=dev)
-        self.hp = AdamHp(self.lr.data_ptr(), self.adam_step.data_ptr(), 0.9, 0.999, 1e-8, 0.0, None)
+        self.hp = SeqAdamHp(self.lr.data_ptr(), self.adam_step.data_ptr(), 0.9, 0.999, 1e-8, 0.0, None)
         self.graphs = {}
 
     def _group(self, nets, R):

@@ -84,6 +84,11 @@ class AdamState:
             self.lr = float(lr)
             self.lr_dev.fill_(self.lr)
 
+    def set_hyper(self, betas, eps: float, weight_decay: float):
+        """The launch arguments among the hyper-parameters: a recorded step holds the old ones (the caller forgets it)."""
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.hp.beta1, self.hp.beta2, self.hp.eps, self.hp.weight_decay = self.betas[0], self.betas[1], self.eps, self.weight_decay
+
     def tick(self):
         _call("vunet_seq_adam_tick", _p(self.step_dev), _p(self.lr_dev), self.hp.beta1, self.hp.beta2, _p(self.resolved_dev), _stream())
 
@@ -92,28 +97,158 @@ class AdamState:
         return int(self.step_dev.item())
 
 
-class _TrainLayer:
-    """One Linear layer of one MLP: the (possibly padded) weight / bias images the kernels read, and Adam's moments."""
+def adam_state_dict(adam, step: int, moments, **group_extra) -> dict:
+    """``torch.optim.Adam(...).state_dict()`` as the installed torch writes it, for the parameters whose (exp_avg, exp_avg_sq)
+    ``moments`` lists in order: one float ``step`` tensor per entry, the group's full key set (+ ``group_extra``), and -- as
+    torch's -- no state at all before the first step.  ``adam``: lr, betas, eps, weight_decay as plain attributes."""
+    group = torch.optim.Adam([torch.zeros(1)], lr=adam.lr, betas=adam.betas, eps=adam.eps,
+                             weight_decay=adam.weight_decay).state_dict()["param_groups"][0]
+    group.update(group_extra, params=list(range(len(moments))))
+    state = {i: {"step": torch.tensor(float(step)), "exp_avg": m, "exp_avg_sq": v} for i, (m, v) in enumerate(moments)} if step else {}
+    return {"state": state, "param_groups": [group]}
 
-    def __init__(self, name: str, lin, w_img: torch.Tensor, b_img: torch.Tensor):
-        self.name, self.lin, self.w, self.b = name, lin, w_img, b_img
-        self.w_inplace = w_img.data_ptr() == lin.weight.data_ptr()
-        self.b_inplace = b_img.data_ptr() == lin.bias.data_ptr()
+
+def load_adam_state(adam, sd: dict):
+    """The inverse: ``adam`` takes the group's hyper-parameters; -> ([(exp_avg, exp_avg_sq) or None per parameter], step)."""
+    group = sd["param_groups"][0]
+    adam.set_lr(group["lr"])
+    adam.set_hyper(group["betas"], group["eps"], group["weight_decay"])
+    states = [sd["state"].get(i) for i in range(len(group["params"]))]
+    step = 0
+    for st in states:
+        if st is not None:
+            step = int(st["step"])
+    return [None if st is None else (st["exp_avg"], st["exp_avg_sq"]) for st in states], step
+
+
+def dx_split(m: int, k: int, nets: int) -> int:
+    """Row ranges (slabs) of W per input-gradient launch: as many as keep the launch within ONE round of workgroups on the
+    chip's 256 CUs and a slab at >= 64 rows, at most 16 -- 4 for the flow's 2048 x 2048 layers (64 stripes), 16 for its first
+    layers, 15 for the LSTM's gate matrix over [x | h] (17 stripes: 255 workgroups; slabs of 17 or 18 row groups)."""
+    wgs = (k // 64) * nets
+    if os.environ.get("VUNET_SEQ_DX_TAIL", "0") == "1":    # the rule before: doubled until >= 256 workgroups (17 stripes: 272)
+        s = 1
+        while wgs * s < 256 and m % (32 * s) == 0 and m // (2 * s) >= 64 and s < 16:
+            s *= 2
+        return s
+    return max(1, min(16, 256 // wgs, m // 64))
+
+
+def dx_chain(d: SeqDxDesc, w, dz: torch.Tensor, raw: torch.Tensor, below=None, slope: float = 0.0):
+    """One layer of an input-gradient chain: ``vunet_seq_dx`` of the layer's dZ through ``w`` (one image per net) into the raw
+    slabs and, with a layer ``below`` = (its output, its dZ), ``vunet_seq_dz_finish``: the slab sum times the derivative of the
+    activation between them (LeakyReLU of ``slope``; 0: ReLU)."""
+    _call("vunet_seq_dx", ctypes.byref(d), _p(w[0]), _p(w[1] if d.nets > 1 else None), _p(dz), _p(raw), _stream())
+    if below is not None:
+        _call("vunet_seq_dz_finish", _p(raw), _p(below[0]), _p(below[1]), d.nets, d.S, _up(d.B, 16), d.K, slope, _stream())
+
+
+class TrainLayer:
+    """One trainable (weight, bias) pair of the seq kernels: the operand images they read, Adam's moments beside them and the
+    layer's entry of the update sweep's table.
+
+    The images are [mp, kp] / [mp], multiples of 64.  A parameter whose 2-D view [out, in k k] fits and is contiguous IS its image
+    and is updated in place; any other trains as a zero-padded image (padded rows produce zeros and receive no update) that
+    ``write_back`` copies into the parameter.  ``pieces``: (first column of the parameter's matrix, columns, first column in the
+    image) per column block of a padded image.  ``images``: a (weight, bias) image pair the caller already holds -- nothing is
+    allocated or loaded here.  The moments ``m, v, bm, bv`` are shaped like the images and allocated on first use."""
+
+    def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor, pieces=None, kp: Optional[int] = None, images=None):
+        w2 = weight.data.reshape(weight.shape[0], -1)
+        self.name, self.weight, self.bias = name, weight, bias
+        self.rows, self.k = w2.shape                       # (``m`` is Adam's first moment)
+        self.pieces = [(0, self.k, 0)] if pieces is None else list(pieces)
+        own = images is None
+        if own:
+            mp, kp = _up(self.rows, 64), _up(self.k, 64) if kp is None else kp
+            fits = (mp, kp) == (self.rows, self.k) and w2.is_contiguous() and bias.data.is_contiguous()
+            images = (w2, bias.data) if fits else (torch.zeros(mp, kp, device=weight.device), torch.zeros(mp, device=weight.device))
+        self.w, self.b = images
+        self.mp, self.kp = self.w.shape
+        self.w_inplace, self.b_inplace = self.w.data_ptr() == weight.data_ptr(), self.b.data_ptr() == bias.data_ptr()
         self.m = self.v = self.bm = self.bv = None
+        if own:
+            self.load()
 
-    def moments(self):
-        if self.m is None:
-            self.m, self.v = torch.zeros_like(self.w), torch.zeros_like(self.w)
-            self.bm, self.bv = torch.zeros_like(self.b), torch.zeros_like(self.b)
+    @property
+    def inplace(self) -> bool:
+        return self.w_inplace and self.b_inplace
+
+    def load(self):
+        """The parameter's values -> the padded images."""
+        if not self.w_inplace:
+            self._scatter(self.w, self.weight.data)
+        if not self.b_inplace:
+            self.b[:self.rows].copy_(self.bias.data)
 
     def write_back(self):
         """A padded image is the training master: copy its valid part into the module's parameter."""
         if not self.w_inplace:
-            m, k = self.lin.weight.shape
-            _call("vunet_seq_unpack_rows", _p(self.w), self.w.shape[1], 0, 0, 1, _p(self.lin.weight.data), m, k, 0, _stream())
+            if self.pieces == [(0, self.k, 0)] and self.weight.data.is_contiguous():
+                _call("vunet_seq_unpack_rows", _p(self.w), self.kp, 0, 0, 1, _p(self.weight.data), self.rows, self.k, 0, _stream())
+            else:
+                self.weight.data.copy_(self._gather(self.w))
         if not self.b_inplace:
-            n = self.lin.bias.numel()
-            _call("vunet_seq_unpack_rows", _p(self.b), self.b.numel(), 0, 0, 1, _p(self.lin.bias.data), 1, n, 0, _stream())
+            _call("vunet_seq_unpack_rows", _p(self.b), self.mp, 0, 0, 1, _p(self.bias.data), 1, self.rows, 0, _stream())
+
+    def _gather(self, img: Optional[torch.Tensor]) -> torch.Tensor:
+        """An image's valid part in the weight's own shape, as a copy (no image: zeros)."""
+        out = torch.zeros(self.rows, self.k, device=self.w.device)
+        if img is not None:
+            for src, n, dst in self.pieces:
+                out[:, src:src + n].copy_(img[:self.rows, dst:dst + n])
+        return out.reshape(self.weight.shape)
+
+    def _scatter(self, img: torch.Tensor, val: torch.Tensor):
+        v2 = val.to(img.device, torch.float32).reshape(self.rows, self.k)
+        for src, n, dst in self.pieces:
+            img[:self.rows, dst:dst + n].copy_(v2[:, src:src + n])
+
+    def ensure_moments(self):
+        if self.m is None:
+            self.m, self.v = torch.zeros_like(self.w), torch.zeros_like(self.w)
+            self.bm, self.bv = torch.zeros_like(self.b), torch.zeros_like(self.b)
+
+    def adopt_moments(self, other: "TrainLayer"):
+        """Adam's moments survive a re-pack (a load_state_dict between two steps) as long as the image's shape does."""
+        if other.m is not None and other.m.shape == self.w.shape:
+            self.m, self.v, self.bm, self.bv = other.m, other.v, other.bm, other.bv
+
+    def moments(self):
+        """-> [(exp_avg, exp_avg_sq) of the weight, of the bias] in the parameters' own shapes, as copies (zeros before the
+        first step: nothing is allocated for them)."""
+        bias = [torch.zeros(self.rows, device=self.w.device) if t is None else t[:self.rows].clone() for t in (self.bm, self.bv)]
+        return [(self._gather(self.m), self._gather(self.v)), tuple(bias)]
+
+    def set_moments(self, w_state, b_state):
+        """The inverse of ``moments``: (exp_avg, exp_avg_sq) of the weight and of the bias; None (a parameter without state, as
+        in torch's dictionary before the first step): zeros."""
+        if w_state is None and b_state is None and self.m is None:
+            return
+        self.ensure_moments()
+        for img in (self.m, self.v, self.bm, self.bv):
+            img.zero_()
+        for img, val in zip((self.m, self.v), w_state or ()):
+            self._scatter(img, val)
+        for img, val in zip((self.bm, self.bv), b_state or ()):
+            img[:self.rows].copy_(val.reshape(-1))
+
+    def tiles(self, nchunk: int = 1) -> int:
+        """64 x 64 tiles of the layer's entry in the sweep's table; ``nchunk`` > 1 (``vunet_seq_dwx``): tiles of 64 nchunk rows."""
+        return -(-self.mp // (64 * nchunk)) * (self.kp // 64)
+
+    def dw_entry(self, dz_ptr: int, ldz: int, x_ptr: int, ldx: int, tile0: int, *, grads=None, kv: Optional[int] = None,
+                 nchunk: int = 1, dx_raw: Optional[int] = None) -> SeqDwLayer:
+        """The layer's entry of a ``vunet_seq_dw`` / ``vunet_seq_dwx`` table (include/vunet_seq_train.h).  ``grads`` = (g, bg):
+        write mode, the gradients go there and nothing is updated; None: the update fused into Adam, on the layer's moments
+        (allocated here if they are not yet).  ``kv``: valid columns (default: all of the image's); ``nchunk``, ``dx_raw``:
+        ``vunet_seq_dwx``'s rows per tile (in 64s) and its slabs."""
+        if grads is None:
+            self.ensure_moments()
+        g, bg = grads if grads is not None else (None, None)
+        return SeqDwLayer(w=_ptr(self.w), m=_ptr(self.m), v=_ptr(self.v), g=_ptr(g), bias=_ptr(self.b), bm=_ptr(self.bm),
+                          bv=_ptr(self.bv), bg=_ptr(bg), dz=dz_ptr, x=x_ptr, M=self.mp, K=self.kp, ldz=ldz, ldx=ldx, tile0=tile0,
+                          tiles_k=self.kp // 64, kv=self.kp if kv is None else kv, nchunk=nchunk, chunk_z=0, chunk_x=0, dx_raw=dx_raw)
 
 
 class FlowTrainEngine(FlowEngine):
@@ -129,7 +264,6 @@ class FlowTrainEngine(FlowEngine):
         super().__init__(flow)
         self._adam_args = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.adam: Optional[AdamState] = None
-        self._moments: Dict[str, tuple] = {}
         # autograd's passes in flight (seq_passes).  The flow stage runs one pass per iteration (experiments/behavior_net.py:707-710):
         # by default one pass at a time, a second forward REPLACES the first one's activations; ``max_passes`` > 1 keeps several
         self._passes = PassPool(1, "the flow")
@@ -164,23 +298,22 @@ class FlowTrainEngine(FlowEngine):
         dev = self.blocks[0]["scale"].device
         if self.adam is None:
             self.adam = AdamState(dev, **self._adam_args)
-        self.layers: List[List[List[List[_TrainLayer]]]] = []    # [block][half][net][layer]
+        old = {lay.name: lay for lay in self._all_layers()} if getattr(self, "layers", None) else {}
+        self.layers: List[List[List[List[TrainLayer]]]] = []    # [block][half][net][layer]
         for bi, (blk, mod) in enumerate(zip(self.blocks, self.flow.sub_layers)):
             per_half = []
             for hi, half in enumerate(blk["halves"]):
                 nets = []
                 for ni, kind in enumerate(("s", "t")):
                     lins = getattr(mod.coupling, kind)[hi].linears()
-                    nets.append([_TrainLayer(f"sub_layers.{bi}.coupling.{kind}.{hi}.main.{2 * li}", lin, half.w[li][ni], half.b[li][ni])
-                                 for li, lin in enumerate(lins)])
+                    nets.append([TrainLayer(f"sub_layers.{bi}.coupling.{kind}.{hi}.main.{2 * li}", lin.weight, lin.bias,
+                                            images=(half.w[li][ni], half.b[li][ni])) for li, lin in enumerate(lins)])
                 per_half.append(nets)
             self.layers.append(per_half)
         self.inv_swap = torch.argsort(self.swap.long()).to(torch.int32)
-        # Adam's moments survive a re-pack (a load_state_dict between two steps) as long as the shapes do
         for lay in self._all_layers():
-            old = self._moments.get(lay.name)
-            if old is not None and old[0].shape == lay.w.shape:
-                lay.m, lay.v, lay.bm, lay.bv = old
+            if lay.name in old:
+                lay.adopt_moments(old[lay.name])
         self.norm_moments = getattr(self, "norm_moments", None)
         if self.norm_moments is None or self.norm_moments[0].device != dev:
             n = len(self.blocks)
@@ -188,11 +321,6 @@ class FlowTrainEngine(FlowEngine):
 
     def _all_layers(self):
         return [lay for blk in self.layers for half in blk for net in half for lay in net]
-
-    def _ensure_moments(self):
-        for lay in self._all_layers():
-            lay.moments()
-            self._moments[lay.name] = (lay.m, lay.v, lay.bm, lay.bv)
 
     @property
     def max_passes(self) -> int:
@@ -232,7 +360,7 @@ class FlowTrainEngine(FlowEngine):
         # fused form (vunet_seq_dwx): one slab per 256-row tile of W; separate form: S row ranges chosen for >= 256 workgroups
         p["tsub"] = [self._dwx_rows(m, k, h0.nets) for (m, k) in h0.dims]      # 64-row sub-tiles per tile of the fused form
         p["S"] = ([(m + 64 * t - 1) // (64 * t) for (m, _), t in zip(h0.dims, p["tsub"])] if self.fused_dx
-                  else [self._dx_split(m, k, h0.nets) for (m, k) in h0.dims])
+                  else [dx_split(m, k, h0.nets) for (m, k) in h0.dims])
         p["raw"] = z(max(h0.nets * s * b_pad * k for s, (_, k) in zip(p["S"], h0.dims)))
         p["dx_cnt"] = torch.zeros(h0.nets * max(k for (_, k) in h0.dims) // 64, dtype=torch.int32, device=dev)   # vunet_seq_dx_finish
         p["raw_in"] = [z(h0.nets * p["S"][0] * b_pad * h0.dims[0][1]) for _ in range(2)]
@@ -248,19 +376,6 @@ class FlowTrainEngine(FlowEngine):
         while t > 1 and ((m + 64 * t - 1) // (64 * t)) * (k // 64) * nets < want:
             t //= 2
         return t
-
-    @staticmethod
-    def _dx_split(m: int, k: int, nets: int) -> int:
-        """Row ranges (slabs) of W per input-gradient launch: as many as keep the launch within ONE round of workgroups on the
-        chip's 256 CUs and a slab at >= 64 rows, at most 16 -- 4 for the flow's 2048 x 2048 layers (64 stripes), 16 for its first
-        layers, 15 for the LSTM's gate matrix over [x | h] (17 stripes: 255 workgroups; slabs of 17 or 18 row groups)."""
-        wgs = (k // 64) * nets
-        if os.environ.get("VUNET_SEQ_DX_TAIL", "0") == "1":    # the rule before: doubled until >= 256 workgroups (17 stripes: 272)
-            s = 1
-            while wgs * s < 256 and m % (32 * s) == 0 and m // (2 * s) >= 64 and s < 16:
-                s *= 2
-            return s
-        return max(1, min(16, 256 // wgs, m // 64))
 
     # ---- forward, everything kept
     def _issue_train_forward(self, rows: int, p: dict):
@@ -292,20 +407,15 @@ class FlowTrainEngine(FlowEngine):
 
     def _mlp_bwd(self, rows, p, half, ys, dzs, raw_in):
         """The input-gradient chain of one coupling half: head -> first layer.  ``dzs[-1]`` holds the heads' dZ."""
-        b_pad = p["b_pad"]
         for li in range(len(half.dims) - 1, -1, -1):
             m_pad, k_pad = half.dims[li]
-            s = p["S"][li]
             raw = raw_in if li == 0 else p["raw"]
-            d = SeqDxDesc(rows, m_pad, k_pad, half.nets, s, 0)
-            w1 = _p(half.w[li][1] if half.nets > 1 else None)
+            d = SeqDxDesc(rows, m_pad, k_pad, half.nets, p["S"][li], 0)
             if li > 0 and self.fused_finish:   # the stripe's last workgroup finishes dZ of the layer below: one launch, not two
-                _call("vunet_seq_dx_finish", ctypes.byref(d), _p(half.w[li][0]), w1, _p(dzs[li]), _p(raw), _p(ys[li - 1]),
-                      _p(dzs[li - 1]), _p(p["dx_cnt"]), LRELU_SLOPE, _stream())
+                _call("vunet_seq_dx_finish", ctypes.byref(d), _p(half.w[li][0]), _p(half.w[li][1] if half.nets > 1 else None),
+                      _p(dzs[li]), _p(raw), _p(ys[li - 1]), _p(dzs[li - 1]), _p(p["dx_cnt"]), LRELU_SLOPE, _stream())
                 continue
-            _call("vunet_seq_dx", ctypes.byref(d), _p(half.w[li][0]), w1, _p(dzs[li]), _p(raw), _stream())
-            if li > 0:
-                _call("vunet_seq_dz_finish", _p(raw), _p(ys[li - 1]), _p(dzs[li - 1]), half.nets, s, b_pad, k_pad, LRELU_SLOPE, _stream())
+            dx_chain(d, half.w[li], dzs[li], raw, (ys[li - 1], dzs[li - 1]) if li > 0 else None, LRELU_SLOPE)
 
     def _dw_table(self, p: dict, grads: Optional[dict]) -> dict:
         """The update sweep's descriptor table: per block (last first) and half (1, then 0) the eight layers of its two nets.
@@ -321,11 +431,9 @@ class FlowTrainEngine(FlowEngine):
                         lay = self.layers[bi][hi][ni][li]
                         x = (p["s0"][bi] if hi == 0 else p["s1"][bi]) if li == 0 else p["y"][bi][hi][li - 1][ni * b_pad * k_pad:]
                         dz = p["dz"][bi][hi][li][ni * b_pad * m_pad:]
-                        g, bg = grads[lay.name] if grads is not None else (None, None)
-                        entries.append(SeqDwLayer(_ptr(lay.w), _ptr(lay.m), _ptr(lay.v), _ptr(g), _ptr(lay.b), _ptr(lay.bm), _ptr(lay.bv),
-                                                  _ptr(bg), dz.data_ptr(), x.data_ptr(), m_pad, k_pad, m_pad,
-                                                  self.ld if li == 0 else k_pad, tile, k_pad // 64, lay.lin.weight.shape[1], 1, 0, 0, None))
-                        tile += (m_pad // 64) * (k_pad // 64)
+                        entries.append(lay.dw_entry(dz.data_ptr(), m_pad, x.data_ptr(), self.ld if li == 0 else k_pad, tile,
+                                                    grads=None if grads is None else grads[lay.name], kv=lay.k))
+                        tile += lay.tiles()
                 ranges.append((first, tile - first))
         return dict(table=_table(entries, self.blocks[0]["scale"].device), n=len(entries), ranges=ranges, tiles=tile)
 
@@ -340,19 +448,17 @@ class FlowTrainEngine(FlowEngine):
                 for li in reversed(range(len(half.dims))):
                     m_pad, k_pad = half.dims[li]
                     first = tile
-                    s_li = p["S"][li]
+                    s_li, tsub = p["S"][li], p["tsub"][li]
                     raw = p["raw_in"][hi] if li == 0 else p["raw"]
                     for ni in range(half.nets):
                         lay = self.layers[bi][hi][ni][li]
                         x = (p["s0"][bi] if hi == 0 else p["s1"][bi]) if li == 0 else p["y"][bi][hi][li - 1][ni * b_pad * k_pad:]
                         dz = p["dz"][bi][hi][li][ni * b_pad * m_pad:]
-                        g, bg = grads[lay.name] if grads is not None else (None, None)
                         dx = raw[ni * s_li * b_pad * k_pad:]
-                        entries.append(SeqDwLayer(_ptr(lay.w), _ptr(lay.m), _ptr(lay.v), _ptr(g), _ptr(lay.b), _ptr(lay.bm), _ptr(lay.bv),
-                                                  _ptr(bg), dz.data_ptr(), x.data_ptr(), m_pad, k_pad, m_pad,
-                                                  self.ld if li == 0 else k_pad, tile, k_pad // 64, lay.lin.weight.shape[1], p["tsub"][li], 0, 0,
-                                                  dx.data_ptr()))
-                        tile += s_li * (k_pad // 64)
+                        entries.append(lay.dw_entry(dz.data_ptr(), m_pad, x.data_ptr(), self.ld if li == 0 else k_pad, tile,
+                                                    grads=None if grads is None else grads[lay.name], kv=lay.k, nchunk=tsub,
+                                                    dx_raw=dx.data_ptr()))
+                        tile += lay.tiles(tsub)
                     ranges[(bi, hi, li)] = (first, tile - first)
         return dict(table=_table(entries, self.blocks[0]["scale"].device), n=len(entries), ranges=ranges, tiles=tile)
 
@@ -481,7 +587,6 @@ class FlowTrainEngine(FlowEngine):
         x2 = self._check_input(x.detach())
         rows = x2.shape[0]
         self._initialise_actnorm(x2)
-        self._ensure_moments()
         p = self._plan(rows)
         p["x_in"].copy_(x2)
         if noise is None:
@@ -554,7 +659,7 @@ class FlowTrainEngine(FlowEngine):
         out = {}
         for lay in self._all_layers():
             g, bg = grads[lay.name]
-            m, k = lay.lin.weight.shape
+            m, k = lay.weight.shape
             out[lay.name + ".weight"] = g if g.shape == (m, k) else g[:m, :k].contiguous()
             out[lay.name + ".bias"] = bg if bg.numel() == m else bg[:m].contiguous()
         for bi in range(len(self.blocks)):
@@ -564,62 +669,35 @@ class FlowTrainEngine(FlowEngine):
         return p["dx"].clone(), out
 
     # ---- torch.optim.Adam's state layout (checkpoints: experiments/behavior_net.py:392-393, :1003-1011)
+    def _norm_moment_views(self):
+        """name -> (exp_avg, exp_avg_sq) views of the ActNorm moments, in the parameters' shapes."""
+        out = {}
+        for bi in range(len(self.blocks)):
+            mom = self.norm_moments[0][bi].reshape(4, 1, self.C, 1, 1)
+            out[f"sub_layers.{bi}.norm_layer.scale"], out[f"sub_layers.{bi}.norm_layer.loc"] = (mom[0], mom[1]), (mom[2], mom[3])
+        return out
+
     def optimizer_state_dict(self) -> dict:
         self._pack()
-        self._ensure_moments()
-        step = torch.tensor(float(self.adam.step))
-        state, names = {}, [n for n, _ in self.flow.named_parameters()]
-        by_name = {}
+        by_name = {n: (m.clone(), v.clone()) for n, (m, v) in self._norm_moment_views().items()}
         for lay in self._all_layers():
-            m, k = lay.lin.weight.shape
-            by_name[lay.name + ".weight"] = (lay.m[:m, :k], lay.v[:m, :k])
-            by_name[lay.name + ".bias"] = (lay.bm[:m], lay.bv[:m])
-        for bi in range(len(self.blocks)):
-            mom = self.norm_moments[0][bi]
-            by_name[f"sub_layers.{bi}.norm_layer.scale"] = (mom[0].reshape(1, -1, 1, 1), mom[1].reshape(1, -1, 1, 1))
-            by_name[f"sub_layers.{bi}.norm_layer.loc"] = (mom[2].reshape(1, -1, 1, 1), mom[3].reshape(1, -1, 1, 1))
-        for idx, n in enumerate(names):
-            m, v = by_name[n]
-            state[idx] = {"step": step.clone(), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
-        a = self.adam
-        group = {"lr": a.lr, "betas": a.betas, "eps": a.eps, "weight_decay": a.weight_decay, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "name": "latent_flow",
-                 "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group]}
+            by_name[lay.name + ".weight"], by_name[lay.name + ".bias"] = lay.moments()
+        return adam_state_dict(self.adam, self.adam.step, [by_name[n] for n, _ in self.flow.named_parameters()], name="latent_flow")
 
     def load_optimizer_state_dict(self, sd: dict):
         self._pack()
-        self._ensure_moments()
-        names = [n for n, _ in self.flow.named_parameters()]
-        group = sd["param_groups"][0]
-        a = self.adam
-        a.set_lr(group["lr"])
-        a.betas, a.eps, a.weight_decay = tuple(float(b) for b in group["betas"]), float(group["eps"]), float(group["weight_decay"])
-        a.hp.beta1, a.hp.beta2, a.hp.eps, a.hp.weight_decay = a.betas[0], a.betas[1], a.eps, a.weight_decay
-        lay_by = {lay.name: lay for lay in self._all_layers()}
-        step = 0
-        for idx, n in enumerate(names):
-            st = sd["state"].get(idx)
-            if st is None:
-                continue
-            step = int(st["step"])
-            m, v = st["exp_avg"].to(a.lr_dev.device), st["exp_avg_sq"].to(a.lr_dev.device)
-            base, leaf = n.rsplit(".", 1)
-            if base in lay_by:
-                lay = lay_by[base]
-                if leaf == "weight":
-                    lay.m[:m.shape[0], :m.shape[1]].copy_(m)
-                    lay.v[:v.shape[0], :v.shape[1]].copy_(v)
+        states, step = load_adam_state(self.adam, sd)
+        by_name = dict(zip((n for n, _ in self.flow.named_parameters()), states))
+        for lay in self._all_layers():
+            lay.set_moments(by_name[lay.name + ".weight"], by_name[lay.name + ".bias"])
+        for n, views in self._norm_moment_views().items():
+            for i, view in enumerate(views):
+                if by_name[n] is None:
+                    view.zero_()
                 else:
-                    lay.bm[:m.numel()].copy_(m)
-                    lay.bv[:v.numel()].copy_(v)
-            else:
-                bi = int(n.split(".")[1])
-                o = 0 if leaf == "scale" else 2
-                self.norm_moments[0][bi][o].copy_(m.reshape(-1))
-                self.norm_moments[0][bi][o + 1].copy_(v.reshape(-1))
-        a.step_dev.fill_(step)
-        self.graph.graphs.clear()   # the hyper-parameters are launch arguments of the recorded step
+                    view.copy_(by_name[n][i])
+        self.adam.step_dev.fill_(step)
+        self.graph.clear()   # the hyper-parameters are launch arguments of the recorded step
 
 
 class _FlowFn(torch.autograd.Function):
@@ -716,9 +794,7 @@ class BehaviorTrainEngine(BehaviorEngine):
         dev = self.dec_w.device
         bp, H, n, ldx = _up(rows, 16), self.H, self.n, self.ldx
         z = lambda *s: torch.zeros(*s, device=dev)   # noqa: E731
-        s_d = FlowTrainEngine._dx_split(4 * H, ldx, 1)
-        s_e = FlowTrainEngine._dx_split(4 * H, H, 1)
-        s_h = FlowTrainEngine._dx_split(H, H, 2)
+        s_d, s_e, s_h = dx_split(4 * H, ldx, 1), dx_split(4 * H, H, 1), dx_split(H, H, 2)
         p = dict(b_pad=bp, x1=z(rows, t_in, n), x2=z(rows, t2, n), eps=z(rows, H), target=z(rows, length, n),
                  xh_e=z(t_in + 1, bp, ldx), c_e=z(t_in + 1, bp, H), gates_e=z(t_in, bp, 4 * H),
                  xh_d=z(length + 1, bp, ldx), c_d=z(length + 1, bp, H), gates_d=z(length, bp, 4 * H),
@@ -938,8 +1014,9 @@ class RegressorTrainEngine:
     through the UPDATED weights with the fifth forward's ReLU masks -- what the reference's torch 1.3.1 computes, whose Adam
     writes through ``p.data`` -- scaled by ``-w ([L_5 <= 0.45] + [L_5 <= 0.7])``.
 
-    The module's fc1 .. fc4 parameters are the kernels' operands and are updated in place; fc5 (51 rows) trains as a zero-padded
-    64-row image, written back into the module by ``write_back``."""
+    The module's fc1 .. fc4 parameters are the kernels' operands and are updated in place (fc4, one column per inner step, by a
+    kernel of its own on moments in the parameter's shape); fc5 (51 rows) trains as a zero-padded 64-row image, written back into
+    the module by ``write_back``."""
 
     def __init__(self, reg, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8):
         H, n = reg.n_dim, reg.n_key
@@ -958,17 +1035,13 @@ class RegressorTrainEngine:
     def load_module(self):
         """(Re)build the training state from the module's parameters: the fc5 image; Adam's moments and step count are reset."""
         r = self.reg
-        self.w5 = weight_image(r.fc5.weight.detach(), 64, self.K5)
-        self.b5 = padded_vector(r.fc5.bias.detach(), 64)
-        self.layers = [_TrainLayer("fc1", r.fc1, r.fc1.weight.data, r.fc1.bias.data),
-                       _TrainLayer("fc2", r.fc2, r.fc2.weight.data, r.fc2.bias.data),
-                       _TrainLayer("fc3", r.fc3, r.fc3.weight.data, r.fc3.bias.data),
-                       _TrainLayer("fc5", r.fc5, self.w5, self.b5)]
+        self.fc1, self.fc2, self.fc3, self.fc5 = (TrainLayer(n, lin.weight, lin.bias)
+                                                  for n, lin in (("fc1", r.fc1), ("fc2", r.fc2), ("fc3", r.fc3), ("fc5", r.fc5)))
+        self.fc4 = TrainLayer("fc4", r.fc4.weight, r.fc4.bias, images=(r.fc4.weight.data, r.fc4.bias.data))
+        self.layers = [self.fc1, self.fc2, self.fc3, self.fc4, self.fc5]          # the order of ``reg.parameters()``
         for layer in self.layers:
-            layer.moments()
-        w4 = r.fc4.weight.data
-        self.m4, self.v4 = torch.zeros_like(w4), torch.zeros_like(w4)
-        self.bm4, self.bv4 = torch.zeros_like(r.fc4.bias.data), torch.zeros_like(r.fc4.bias.data)
+            layer.ensure_moments()
+        self.w5, self.b5 = self.fc5.w, self.fc5.b
         self.adam.step_dev.zero_()
         self._plans.clear()
 
@@ -979,36 +1052,28 @@ class RegressorTrainEngine:
         dev = self.w5.device
         bp, H, H2, H4, K5 = _up(rows, 16), self.H, self.H // 2, self.H4, self.K5
         z = lambda *s: torch.zeros(*s, device=dev)   # noqa: E731
-        S = {"fc5": FlowTrainEngine._dx_split(64, K5, 1), "fc3": FlowTrainEngine._dx_split(H4, H2, 1),
-             "fc2": FlowTrainEngine._dx_split(H2, H, 1), "fc1": FlowTrainEngine._dx_split(H, H, 1)}
+        S = {"fc5": dx_split(64, K5, 1), "fc3": dx_split(H4, H2, 1), "fc2": dx_split(H2, H, 1), "fc1": dx_split(H, H, 1)}
         p = dict(b_pad=bp, S=S, idx=torch.zeros(REG_STEPS, dtype=torch.int32, device=dev), mu=z(bp, H), h1=z(bp, H), h2=z(bp, H2),
                  h3=z(bp, H4), cat=z(bp, K5), pred=z(bp, 64), tgt=z(bp, self.n), dpred=z(bp, 64), dz1=z(bp, H), dz2=z(bp, H2),
                  dz3=z(bp, H4), dzc=z(bp, 128), reg=z(6), adv=z(rows, H),
                  raw=z(max(S["fc5"] * bp * K5, S["fc3"] * bp * H2, S["fc2"] * bp * H, S["fc1"] * bp * H)))
         # the update sweep: fc1, fc2, fc3, fc5 in one launch (fc4 has its own kernel)
         entries, tile = [], 0
-        for layer, dz, x, ldz in zip(self.layers, (p["dz1"], p["dz2"], p["dz3"], p["dpred"]), (p["mu"], p["h1"], p["h2"], p["cat"]),
-                                     (H, H2, H4, 64)):
-            m, k = layer.w.shape
-            entries.append(SeqDwLayer(layer.w.data_ptr(), layer.m.data_ptr(), layer.v.data_ptr(), None, layer.b.data_ptr(),
-                                      layer.bm.data_ptr(), layer.bv.data_ptr(), None, dz.data_ptr(), x.data_ptr(), m, k, ldz, k, tile,
-                                      k // 64, k, 1, 0, 0, None))
-            tile += (m // 64) * (k // 64)
+        for layer, dz, x in zip((self.fc1, self.fc2, self.fc3, self.fc5), (p["dz1"], p["dz2"], p["dz3"], p["dpred"]),
+                                (p["mu"], p["h1"], p["h2"], p["cat"])):
+            entries.append(layer.dw_entry(dz.data_ptr(), layer.mp, x.data_ptr(), layer.kp, tile))
+            tile += layer.tiles()
         p["dw"] = dict(table=_table(entries, dev), n=len(entries), tiles=tile)
         self._plans[rows] = p
         return p
 
     def _dx_chain(self, rows: int, p: dict, dzc: Optional[torch.Tensor]):
         """d L / d pred (p['dpred']) back to the dZ of fc1 (p['dz1']) on the weights as they are now; ``dzc``: fc4's dZ too."""
-        r, bp, S = self.reg, p["b_pad"], p["S"]
-        d = SeqDxDesc(rows, 64, self.K5, 1, S["fc5"], 0)
-        _call("vunet_seq_dx", ctypes.byref(d), _p(self.w5), None, _p(p["dpred"]), _p(p["raw"]), _stream())
-        _call("vunet_seq_reg_cat_bwd", _p(p["raw"]), S["fc5"], bp, self.H4, _p(p["cat"]), _p(p["dz3"]), _p(dzc), _stream())
-        for lin, s, dz_in, y_prev, dz_out in ((r.fc3, S["fc3"], p["dz3"], p["h2"], p["dz2"]), (r.fc2, S["fc2"], p["dz2"], p["h1"], p["dz1"])):
-            m, k = lin.weight.shape
-            d = SeqDxDesc(rows, m, k, 1, s, 0)
-            _call("vunet_seq_dx", ctypes.byref(d), _p(lin.weight.data), None, _p(dz_in), _p(p["raw"]), _stream())
-            _call("vunet_seq_dz_finish", _p(p["raw"]), _p(y_prev), _p(dz_out), 1, s, bp, k, 0.0, _stream())
+        S = p["S"]
+        dx_chain(SeqDxDesc(rows, 64, self.K5, 1, S["fc5"], 0), [self.w5], p["dpred"], p["raw"])
+        _call("vunet_seq_reg_cat_bwd", _p(p["raw"]), S["fc5"], p["b_pad"], self.H4, _p(p["cat"]), _p(p["dz3"]), _p(dzc), _stream())
+        for lay, dz_in, y_prev, dz_out in ((self.fc3, p["dz3"], p["h2"], p["dz2"]), (self.fc2, p["dz2"], p["h1"], p["dz1"])):
+            dx_chain(SeqDxDesc(rows, lay.mp, lay.kp, 1, S[lay.name], 0), [lay.w], dz_in, p["raw"], (y_prev, dz_out))
 
     def issue_step(self, rows: int, p: dict, mu: torch.Tensor, seq: torch.Tensor, t_len: int, weight: float, scalars: torch.Tensor,
                    gmu: Optional[torch.Tensor]):
@@ -1030,7 +1095,7 @@ class RegressorTrainEngine:
             self.adam.tick()
             _call("vunet_seq_dw", _p(p["dw"]["table"]), p["dw"]["n"], 0, p["dw"]["tiles"], rows, hpp, _stream())
             _call("vunet_seq_reg_fc4_adam", _p(p["dzc"]), p["b_pad"], _p(p["idx"]), k, _p(r.fc4.weight.data), _p(r.fc4.bias.data),
-                  _p(self.m4), _p(self.v4), _p(self.bm4), _p(self.bv4), hpp, _stream())
+                  _p(self.fc4.m), _p(self.fc4.v), _p(self.fc4.bm), _p(self.fc4.bv), hpp, _stream())
         if gmu is None:
             return
         # the adversarial term: L_5's input gradient through the updated weights, the fifth forward's masks (torch 1.3.1)
@@ -1042,7 +1107,7 @@ class RegressorTrainEngine:
 
     # ---- checkpoints: the reference's layout (``Regressor_fly`` keys; torch.optim.Adam's state)
     def write_back(self):
-        self.layers[3].write_back()
+        self.fc5.write_back()
 
     def _params(self):
         r = self.reg
@@ -1054,14 +1119,4 @@ class RegressorTrainEngine:
         return self.reg.state_dict()
 
     def optimizer_state_dict(self) -> dict:
-        step = self.adam.step
-        n5, k5 = self.reg.fc5.weight.shape
-        moments = []
-        for layer in self.layers[:3]:
-            moments += [(layer.m, layer.v), (layer.bm, layer.bv)]
-        moments += [(self.m4, self.v4), (self.bm4, self.bv4)]
-        f5 = self.layers[3]
-        moments += [(f5.m[:n5, :k5], f5.v[:n5, :k5]), (f5.bm[:n5], f5.bv[:n5])]
-        state = {i: {"step": step, "exp_avg": m.clone(), "exp_avg_sq": v.clone()} for i, (m, v) in enumerate(moments)} if step else {}
-        return {"state": state, "param_groups": [{"lr": self.adam.lr, "betas": self.adam.betas, "eps": self.adam.eps, "weight_decay": 0.0,
-                                                  "amsgrad": False, "params": list(range(10))}]}
+        return adam_state_dict(self.adam, self.adam.step, [mv for layer in self.layers for mv in layer.moments()])
