@@ -29,7 +29,7 @@ import torch.distributed as dist
 from .. import ops
 from ..lib.losses import compute_kl_with_prior, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
-from ..models.imagenet_pretrained import PerceptualVGG, vgg19
+from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, p2_precision, vgg19
 from ..models.synth_discriminator import DiscTrainer
 from ..models.vunets import Regressor, VunetAlter
 from ..optim import FusedAdam
@@ -47,6 +47,8 @@ DEFAULT_CONFIG = {
                  "gamma_step": 0.00001, "n_init_batches": 4, "adam_betas": (0.5, 0.9), "end_iteration": 150000,
                  "imax_scaling": "none", "information_max": 1000, "ll_weight": 1.0, "train_regressor": True,
                  "weight_regressor": 4.0, "reg_steps": 5,
+                 # optional "vgg_precision": "split" (the default where the key is absent) | "f16" -- the arithmetic of the frozen
+                 # VGG19's p2 convolutions (models/imagenet_pretrained.py: set_p2_precision); read at construction
                  # adversarial term: not part of the reference loop, off by default
                  "gan": {"enabled": False, "weight": 1.0, "pd_scales": 3, "grad_pen": False, "lambda_gp": 10,
                          "grad_weighting": False, "lr": 0.0002, "save_intervall": 10000}},
@@ -77,6 +79,8 @@ class ShapePoseNet:
                          synthetic=vgg_synthetic).to(self.device)
         self.vgg.eval()
         self.custom_vgg = PerceptualVGG(self.vgg, tr["vgg_weights"]).to(self.device)
+        # arithmetic of the frozen VGG19's p2 convolutions: "split" (fp32-accurate, default) | "f16" (one product per tap)
+        self.vgg_precision = apply_config_precision(tr)
         # ---- optimiser (:237-246)
         self.optimizer = FusedAdam(
             [{"params": list(get_member(self.vunet, n).parameters()), "name": n} for n in ("eu", "ed", "du", "dd")],
@@ -210,7 +214,9 @@ class ShapePoseNet:
         # companion streams) exists before anything is recorded
         if it <= tr["n_init_batches"] or self._eager_dev_steps < 2:
             return None
-        return tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in batch.items() if torch.is_tensor(v)))
+        # (the p2 kernel choice is baked into a recording: the mode in force is part of the key, a switch records again)
+        return (("vgg_precision", p2_precision()),) + tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in batch.items()
+                                                                   if torch.is_tensor(v)))
 
     def _train_fn_graph(self, batch, it, eps, reg_eps):
         # Every device-schedule step -- the eager ones before the capture, the capture itself and the replays -- runs on

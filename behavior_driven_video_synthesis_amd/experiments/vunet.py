@@ -18,7 +18,7 @@ import torch.distributed as dist
 from .. import ops
 from ..lib.losses import compute_kl_loss, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
-from ..models.imagenet_pretrained import PerceptualVGG, vgg19
+from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, vgg19
 from ..models.vunets import VunetOrg
 from ..optim import FusedAdam
 from ..parallel import BucketedGradAverager, broadcast_parameters
@@ -33,6 +33,8 @@ DEFAULT_CONFIG = {
     "training": {"batch_size": 8, "vgg_weights": [1.0] * 6, "dropout_prob": 0.05, "lr": 0.0008, "kl_init": 1e-6,
                  "kl_max": 1.0, "n_init_batches": 4, "adam_betas": (0.5, 0.9), "end_iteration": 300000,
                  "ll_weight": 5.0},
+    # optional training.vgg_precision: "split" (the default where the key is absent) | "f16" -- the arithmetic of the frozen
+    # VGG19's p2 convolutions (models/imagenet_pretrained.py: set_p2_precision); read at construction
 }
 
 
@@ -55,6 +57,8 @@ class Vunet:
                          synthetic=vgg_synthetic).to(self.device)
         self.vgg.eval()
         self.custom_vgg = PerceptualVGG(self.vgg, tr["vgg_weights"]).to(self.device)
+        # arithmetic of the frozen VGG19's p2 convolutions: "split" (fp32-accurate, default) | "f16" (one product per tap)
+        self.vgg_precision = apply_config_precision(tr)
         self.optimizer = FusedAdam(
             [{"params": list(get_member(self.vunet, n).parameters()), "name": n} for n in ("eu", "ed", "du", "dd")],
             lr=tr["lr"], betas=tuple(tr["adam_betas"]))

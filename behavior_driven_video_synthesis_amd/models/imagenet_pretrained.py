@@ -118,6 +118,48 @@ def enable_p2(on: bool = True):
     _p2_switch["on"] = bool(on)
 
 
+# Precision of the p2 convolutions.  "split" (default): two scaled fp16 terms per operand, three products per tap -- fp32
+# accuracy.  "f16": ONE product per tap on the hi planes of activations and weights (csrc/conv_p2_kernel.h, P2_TERMS = 1):
+# operands rounded to fp16's 11 bits, fp32 accumulation; half the operand bytes, a third of the matrix instructions.  The
+# planes layout, conv1_1 (fp32 FMA), the L1 tap / pool kernels and the masks are the same in both modes, and a stack /
+# geometry the p2 kernels do not cover runs the per-layer three-product path in both.  The mode is the process-wide tuning
+# key "p2_terms" (VUNET_TUNING=p2_terms=1 selects "f16" for a whole program); a captured training step bakes the kernel
+# choice in, so ShapePoseNet keys its recorded graphs by the mode (a switch after capture records the step again).
+P2_PRECISIONS = ("split", "f16")
+
+
+def p2_precision() -> str:
+    return "f16" if ops.tuning("p2_terms") == 1 else "split"
+
+
+def set_p2_precision(mode: str) -> str:
+    """Select the arithmetic of the perceptual loss's p2 convolutions, "split" | "f16"; returns the previous mode."""
+    if mode not in P2_PRECISIONS:
+        raise ValueError(f"unknown p2 precision {mode!r} (split | f16)")
+    prev = p2_precision()
+    if mode != prev:
+        ops.set_tuning("p2_terms", 1 if mode == "f16" else 0)
+    return prev
+
+
+def vgg_precision_from_config(training: dict) -> str:
+    """``training.vgg_precision`` of a trainer's config (default "split"), checked."""
+    mode = training.get("vgg_precision", "split")
+    if mode not in P2_PRECISIONS:
+        raise ValueError(f"training.vgg_precision: unknown mode {mode!r} (split | f16)")
+    return mode
+
+
+def apply_config_precision(training: dict) -> str:
+    """What the trainers do with ``training.vgg_precision`` at construction: a config that NAMES a mode selects it for the
+    process; one that does not leaves the process's mode alone (so that VUNET_TUNING=p2_terms=1 A/B-runs a program whose
+    config is silent) and reports the default."""
+    mode = vgg_precision_from_config(training)
+    if "vgg_precision" in training:
+        set_p2_precision(mode)
+    return mode
+
+
 class _P2Target(dict):
     """``PerceptualVGG.features_for_loss(target)`` on the p2 path: tap name -> the tap's planes BUFFER (a tensor, so that
     callers can ``record_stream`` the values), "input" -> the preprocessed image (fp32); ``planes``: name -> ops.Planes.

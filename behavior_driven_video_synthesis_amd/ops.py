@@ -205,13 +205,22 @@ def _scheme() -> int:
 
 
 _wants_split_cache = {}
-_TUNING_KEYS = {"split_force_nt": 0, "tiled_force_nt": 1, "force_small": 2, "blk_force_nt": 3, "parity_launches": 4, "blk_ws": 5, "wgrad_rowsplit": 6, "s2_fwd_f32": 7, "p2_form": 8}
+_TUNING_KEYS = {"split_force_nt": 0, "tiled_force_nt": 1, "force_small": 2, "blk_force_nt": 3, "parity_launches": 4, "blk_ws": 5, "wgrad_rowsplit": 6, "s2_fwd_f32": 7, "p2_form": 8,
+                "p2_terms": 9}
+_tuning_values = {}
 
 
 def set_tuning(key: str, value: int):
     """vunet_set_tuning: process-wide dispatcher overrides for tests / kernel tuning (0 = the dispatcher's own choice)."""
     _call("vunet_set_tuning", _TUNING_KEYS[key], int(value))
+    _tuning_values[key] = int(value)
     _wants_split_cache.clear()
+
+
+def tuning(key: str) -> int:
+    """The value ``set_tuning`` / ``apply_env_tuning`` last gave ``key`` in this process (0: never set)."""
+    _TUNING_KEYS[key]   # (an unknown key is an error here as in set_tuning)
+    return _tuning_values.get(key, 0)
 
 
 def apply_env_tuning():

@@ -419,6 +419,11 @@ int vunet_set_dropout_step(const uint32_t* step_dev);
  *   VUNET_TUNE_P2_FORM         vunet_p2_conv: 1 = always the four-wave / 64-channel workgroup, 2 = the eight-wave / 128-channel
  *                              one (wave groups in antiphase) wherever the channel count allows, 3 = that one with all waves in
  *                              lockstep (A/B); 0 = by how many workgroups the problem has
+ *   VUNET_TUNE_P2_TERMS        vunet_p2_conv: 1 = ONE product per tap on the hi planes of activations and weights (operands
+ *                              rounded to fp16's 11 bits; the "f16" mode of the perceptual loss), forward and data gradient;
+ *                              0 / 2 = two terms per operand, three products (fp32 accuracy).  The one-term kernels read the
+ *                              same planes and the same weight image and write both output planes; there is no lockstep
+ *                              one-term kernel (P2_FORM = 3 then runs the antiphase one)
  * Returns VUNET_ERR_ARG for an unknown key. */
 #define VUNET_TUNE_SPLIT_FORCE_NT 0
 #define VUNET_TUNE_TILED_FORCE_NT 1
@@ -429,7 +434,8 @@ int vunet_set_dropout_step(const uint32_t* step_dev);
 #define VUNET_TUNE_WGRAD_ROWSPLIT 6
 #define VUNET_TUNE_S2_FWD_F32 7
 #define VUNET_TUNE_P2_FORM 8
-#define VUNET_TUNE_COUNT 9
+#define VUNET_TUNE_P2_TERMS 9
+#define VUNET_TUNE_COUNT 10
 int vunet_set_tuning(int32_t key, int32_t value);
 
 /* Dropout keep-mask of the conv prologue, materialised (parity tests / debugging only) */
@@ -543,7 +549,9 @@ typedef struct vunet_p2_desc {
   int32_t relu;         /* 1: ReLU on the output (the forward layers of the stack) */
 } vunet_p2_desc;
 int vunet_p2_conv_supported(const vunet_p2_desc* d);   /* 1 / 0 */
-int vunet_p2_conv_variant(const vunet_p2_desc* d, char* name, int32_t len);   /* kernel instantiation, rocprofv3 spelling */
+int vunet_p2_conv_variant(const vunet_p2_desc* d, char* name, int32_t len);   /* kernel instantiation, rocprofv3 spelling; the
+                                                                                 one-term kernels (VUNET_TUNE_P2_TERMS = 1) are
+                                                                                 conv_p2a_kernel<CT, 1> / conv_p2_kernel<4, CT, 1, 1> */
 /* y = [relu]( conv3x3_pad1(x; image) + shift ), or with `mask` (planes shaped like y: the forward activation that feeds the
  * layer below) the data-gradient form  y = conv3x3(x; dgrad image) * [mask != 0].  image / wk from vunet_p2_pack_weights. */
 int vunet_p2_conv(const vunet_p2_desc* d, const void* x, const int32_t* xmeta, const void* w_image, const float* wk,

@@ -2,10 +2,12 @@
 """Time vunet_p2_conv (pre-split planes, csrc/conv_p2.hip) beside the h2 kernel of vunet_conv2d on the VGG19 layer shapes of
 the bs-16 256x256 step (needs an MI355X).
 
-    python tools/time_p2.py [--form 0|1|2] [--reps 20]
+    python tools/time_p2.py [--form 0|1|2] [--terms 2|1] [--reps 20]
+    python tools/time_p2.py --ab [--windows 6]          one term against two, alternating windows in ONE process
 
 Per shape: average launch time over --reps back-to-back launches (HIP events; sustained, clock-limited regime), algorithmic
-TFLOP/s and fraction of the 833 TFLOP/s three-product roof -- forward (ReLU epilogue) and data gradient (masked)."""
+TFLOP/s and fraction of the 833 TFLOP/s three-product roof (also printed for --terms 1, whose own roof is three times that) --
+forward (ReLU epilogue) and data gradient (masked)."""
 import argparse
 import ctypes
 import os
@@ -21,8 +23,13 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--form", type=int, default=0)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--batch", type=int, default=16)
+ap.add_argument("--terms", type=int, default=2, choices=(1, 2),
+                help="products per operand of the p2 kernels: 2 = split (three products per tap), 1 = the f16 mode (one)")
+ap.add_argument("--ab", action="store_true", help="time --terms 1 against --terms 2 in alternating windows (no h2 column)")
+ap.add_argument("--windows", type=int, default=6, help="--ab: windows per term count and figure (the median is reported)")
 args = ap.parse_args()
 ops.set_tuning("p2_form", args.form)
+ops.set_tuning("p2_terms", args.terms)
 
 SHAPES = [("conv1_2", 64, 64, 256), ("conv2_1", 64, 128, 128), ("conv2_2", 128, 128, 128), ("conv3_1", 128, 256, 64),
           ("conv3_x", 256, 256, 64), ("conv4_1", 256, 512, 32), ("conv4_x", 512, 512, 32), ("conv5_x", 512, 512, 16)]
@@ -40,8 +47,56 @@ def timed(fn):
     return e0.elapsed_time(e1) / args.reps * 1e3
 
 
+def variant(n, c, s, m):
+    d = ops.P2Desc(n, c, s, s, m, 0)
+    buf = ctypes.create_string_buffer(96)
+    ops._call("vunet_p2_conv_variant", ctypes.byref(d), buf, 96)
+    return buf.value.decode()
+
+
+def ab(n):
+    """One term against two on the same buffers: per figure --windows windows of --reps launches per term count, the term
+    counts ALTERNATING window by window (clock and temperature drift hit both alike); medians."""
+    import statistics
+    print(f"batch {n}, p2 form {args.form} (0 = dispatcher): terms 2 vs terms 1, {args.windows} alternating windows of {args.reps} "
+          "launches each, median window (us per launch)")
+    tot = {"f2": 0.0, "f1": 0.0, "d2": 0.0, "d1": 0.0}
+    for name, cin, cout, s in SHAPES:
+        g = torch.Generator().manual_seed(1)
+        x = torch.randn(n, cin, s, s, generator=g).clamp_min(0).cuda()
+        wt = (torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5).cuda()
+        bias = (torch.randn(cout, generator=g) * 0.1).cuda()
+        dy = (torch.randn(n, cout, s, s, generator=g) * 1e-3).cuda()
+        W = ops.P2Weights(wt, bias)
+        px, pdy = ops.p2_from_nchw(x), ops.p2_from_nchw(dy)
+        out, gout = ops.Planes((n, cout, s, s), "cuda"), ops.Planes((n, cin, s, s), "cuda")
+        W.image(False), W.image(True)
+        fns = {"f": lambda: ops.p2_conv(px, W, out), "d": lambda: ops.p2_conv(pdy, W, gout, dgrad=True, mask=px)}
+        res, names = {}, {}
+        for kind, fn in fns.items():
+            t = {1: [], 2: []}
+            for _ in range(args.windows):
+                for terms in (2, 1):
+                    ops.set_tuning("p2_terms", terms)
+                    t[terms].append(timed(fn))
+            for terms in (2, 1):
+                res[kind + str(terms)] = statistics.median(t[terms])
+                ops.set_tuning("p2_terms", terms)
+                names[kind + str(terms)] = variant(n, cin, s, cout) if kind == "f" else variant(n, cout, s, cin)
+        for k in tot:
+            tot[k] += res[k]
+        print(f"{name:8s} {cin:3d}->{cout:3d} @{s:3d}^2 | fwd  2: {res['f2']:7.1f}  1: {res['f1']:7.1f}  x{res['f2'] / res['f1']:4.2f} "
+              f"[{names['f1']}] | dgrad 2: {res['d2']:7.1f}  1: {res['d1']:7.1f}  x{res['d2'] / res['d1']:4.2f} [{names['d1']}]")
+    print("sum over the listed shapes (us): " + ", ".join(f"{k} {v:.0f}" for k, v in tot.items())
+          + f" | fwd x{tot['f2'] / tot['f1']:.2f}, dgrad x{tot['d2'] / tot['d1']:.2f}")
+    ops.set_tuning("p2_terms", 0)
+
+
 n = args.batch
-print(f"batch {n}, p2 form {args.form} (0 = dispatcher), {args.reps} back-to-back launches per figure")
+if args.ab:
+    ab(n)
+    sys.exit(0)
+print(f"batch {n}, p2 terms {args.terms}, p2 form {args.form} (0 = dispatcher), {args.reps} back-to-back launches per figure")
 tot = {"p2f": 0.0, "h2f": 0.0, "p2d": 0.0, "h2d": 0.0}
 for name, cin, cout, s in SHAPES:
     g = torch.Generator().manual_seed(1)
