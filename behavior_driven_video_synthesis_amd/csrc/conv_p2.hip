@@ -32,7 +32,8 @@
 //             m-tiles), rows 2 (w & 3), 2 (w & 3) + 1 (2 CT / 16 pixel tiles): 4 x 4 accumulator tiles of 4 registers,
 //             two sets (leading term / cross terms) = 128 VGPRs
 //   xL        [XBUF][2 planes][4 k-quarters][10 x (CT + 2)] units, filled by LDS-DMA one chunk ahead (XBUF = 2: eight waves,
-//             one workgroup per CU) or between chunks (XBUF = 1: four waves, two workgroups per CU cover each other)
+//             one workgroup per CU; also four waves with ONE term on small grids, see p2_route) or between chunks (XBUF = 1:
+//             four waves, two workgroups per CU cover each other)
 //   wL        [2][16 NW / 16 m-tiles][2 planes][64] the weight slab of ONE tap, by LDS-DMA one tap ahead; one barrier per tap
 //   epilogue  combine, de-scale, + shift, ReLU (forward) -- scale by the OUTPUT's 2^e, split, pack; two lane rows exchange
 //             halves (v_permlane16_swap) so that a lane holds the 8 channels of one 16-byte unit; data gradient: the unit is
@@ -168,8 +169,33 @@ static int p2_form(const vunet_p2_desc* d) {
   return wide ? 8 : 4;
 }
 
-// VUNET_TUNE_P2_TERMS: 1 = one product per tap on the hi planes ("f16" mode); 0 / 2 = the three-product arithmetic
-static bool p2_one_term() { return g_vunet_tune[VUNET_TUNE_P2_TERMS] == 1; }
+// Which kernel runs a problem: the ONE decision behind vunet_p2_conv and vunet_p2_conv_variant.
+// VUNET_TUNE_P2_TERMS: 0 / 2 = two terms per operand, three products per tap; 1 = one product per tap on the hi planes ("f16"
+// mode), every launch, on the form the two-term rule picks; 3 = one product per tap for DATA-GRADIENT launches only
+// ("f16grad" mode): a forward launch takes exactly the path of 0, a data gradient the four-wave one-term kernel -- measured
+// faster than the eight-wave antiphase one on every VGG19 shape where the two-term rule picks eight waves
+// (profiles/p2_f16grad_time.txt) -- unless VUNET_TUNE_P2_FORM = 2 / 3 asks for the antiphase one.  A one-term x tile is half
+// the size, so the four-wave kernel can hold two of them and fetch the next chunk's tile one chunk ahead (XBUF = 2, 52 KiB,
+// still two workgroups per CU) instead of between chunks: that wins where the launch has at most one workgroup per CU, so
+// that no second resident workgroup covers the refill (conv4_1, conv5_x at batch 16: x1.08), and loses x0.93 - x0.97 on the
+// large grids (same file).  VUNET_TUNE_P2_FORM = 1 keeps the single buffer (A/B, tests).
+struct P2Route {
+  int terms;       // 2 | 1
+  int form;        // waves per workgroup: 4 | 8
+  bool lockstep;   // two terms, eight waves: conv_p2_kernel<8, CT, 2> instead of the antiphase kernel (VUNET_TUNE_P2_FORM = 3)
+  int xbuf;        // x tiles in LDS of conv_p2_kernel: four waves 1 (one term in "f16grad" mode: 1 | 2), eight waves 2
+};
+static P2Route p2_route(const vunet_p2_desc* d, bool dgrad) {
+  const int mode = g_vunet_tune[VUNET_TUNE_P2_TERMS], force = g_vunet_tune[VUNET_TUNE_P2_FORM];
+  if (mode == 3 && dgrad) {
+    if (d->M % 128 == 0 && (force == 2 || force == 3)) return {1, 8, false, 2};
+    const long wgs = (long)d->N * (d->H / 8) * (d->W / (d->W == 16 ? 16 : 32)) * (d->M / 64);
+    return {1, 4, false, force != 1 && wgs <= 256 ? 2 : 1};
+  }
+  const int terms = mode == 1 ? 1 : 2, form = p2_form(d);
+  // one term: no lockstep eight-wave variant (VUNET_TUNE_P2_FORM = 3 runs the antiphase kernel)
+  return {terms, form, terms == 2 && force == 3, form == 8 ? 2 : 1};
+}
 
 extern "C" int vunet_p2_conv(const vunet_p2_desc* d, const void* x, const int32_t* xmeta, const void* w_image, const float* wk,
                              const float* shift, const void* mask, void* y, int32_t* ymeta, void* stream) {
@@ -181,29 +207,34 @@ extern "C" int vunet_p2_conv(const vunet_p2_desc* d, const void* x, const int32_
   a.y = (uint4*)y; a.ymeta = ymeta;
   a.N = d->N; a.C = d->C; a.H = d->H; a.W = d->W; a.M = d->M; a.relu = d->relu;
   hipStream_t st = (hipStream_t)stream;
-  const int form = p2_form(d);
-  if (!p2_one_term()) {
-    const bool lockstep = g_vunet_tune[VUNET_TUNE_P2_FORM] == 3;   // (A/B: the eight-wave form without the antiphase)
-    if (d->W == 16) return form == 8 ? (lockstep ? p2_launch<8, 16, 2, 2>(a, st) : p2a_launch<16, 2>(a, st)) : p2_launch<4, 16, 1, 2>(a, st);
-    return form == 8 ? (lockstep ? p2_launch<8, 32, 2, 2>(a, st) : p2a_launch<32, 2>(a, st)) : p2_launch<4, 32, 1, 2>(a, st);
+  // a data-gradient launch: no ReLU and no shift (a data gradient has neither; the descriptor does not say which image w is)
+  const P2Route r = p2_route(d, d->relu == 0 && shift == nullptr);
+  if (r.terms == 2) {
+    if (d->W == 16) return r.form == 8 ? (r.lockstep ? p2_launch<8, 16, 2, 2>(a, st) : p2a_launch<16, 2>(a, st)) : p2_launch<4, 16, 1, 2>(a, st);
+    return r.form == 8 ? (r.lockstep ? p2_launch<8, 32, 2, 2>(a, st) : p2a_launch<32, 2>(a, st)) : p2_launch<4, 32, 1, 2>(a, st);
   }
-  // one term: no lockstep eight-wave variant (VUNET_TUNE_P2_FORM = 3 runs the antiphase kernel)
-  if (d->W == 16) return form == 8 ? p2a_launch<16, 1>(a, st) : p2_launch<4, 16, 1, 1>(a, st);
-  return form == 8 ? p2a_launch<32, 1>(a, st) : p2_launch<4, 32, 1, 1>(a, st);
+  if (r.form == 8 || r.xbuf == 1) {
+    if (d->W == 16) return r.form == 8 ? p2a_launch<16, 1>(a, st) : p2_launch<4, 16, 1, 1>(a, st);
+    return r.form == 8 ? p2a_launch<32, 1>(a, st) : p2_launch<4, 32, 1, 1>(a, st);
+  }
+  // (named last: the compiler emits kernels in the order of their first use, and a kernel's local labels carry its index)
+  return d->W == 16 ? p2_launch<4, 16, 2, 1>(a, st) : p2_launch<4, 32, 2, 1>(a, st);
 }
 
-// the kernel instantiation vunet_p2_conv launches for this problem, in rocprofv3's spelling (bench.py's roofline keys)
+// the kernel instantiation vunet_p2_conv launches for this problem, in rocprofv3's spelling (bench.py's roofline keys).  The
+// descriptor is all it has: relu == 0 stands for the data gradient
 extern "C" int vunet_p2_conv_variant(const vunet_p2_desc* d, char* name, int32_t len) {
   if (!d || !name || len < 32) return VUNET_ERR_ARG;
   if (!p2_shape_ok(d)) return VUNET_ERR_UNSUPPORTED;
-  const int form = p2_form(d);
-  if (p2_one_term()) {
-    if (form == 8) snprintf(name, (size_t)len, "conv_p2a_kernel<%d, 1>", d->W == 16 ? 16 : 32);
-    else snprintf(name, (size_t)len, "conv_p2_kernel<4, %d, 1, 1>", d->W == 16 ? 16 : 32);
+  const P2Route r = p2_route(d, d->relu == 0);
+  const int ct = d->W == 16 ? 16 : 32;
+  if (r.terms == 1) {
+    if (r.form == 8) snprintf(name, (size_t)len, "conv_p2a_kernel<%d, 1>", ct);
+    else snprintf(name, (size_t)len, "conv_p2_kernel<4, %d, %d, 1>", ct, r.xbuf);
     return VUNET_OK;
   }
-  if (form == 8 && g_vunet_tune[VUNET_TUNE_P2_FORM] != 3) snprintf(name, (size_t)len, "conv_p2a_kernel<%d>", d->W == 16 ? 16 : 32);
-  else snprintf(name, (size_t)len, "conv_p2_kernel<%d, %d, %d>", form, d->W == 16 ? 16 : 32, form == 8 ? 2 : 1);
+  if (r.form == 8 && !r.lockstep) snprintf(name, (size_t)len, "conv_p2a_kernel<%d>", ct);
+  else snprintf(name, (size_t)len, "conv_p2_kernel<%d, %d, %d>", r.form, ct, r.xbuf);
   return VUNET_OK;
 }
 

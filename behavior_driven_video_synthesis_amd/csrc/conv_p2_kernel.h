@@ -3,7 +3,7 @@
 // keep their names (conv_p2_kernel<NW, CT, XBUF>, conv_p2a_kernel<CT> -- profiles, bench.py's roofline keys and
 // vunet_p2_conv_variant spell them so) AND their exact device code (tools/device_asm_diff.sh); routing both term counts through
 // one inlined body changed the register allocation of the existing instantiations.  The one-term kernels are overloads with
-// one more template parameter (always 1): conv_p2_kernel<4, CT, 1, 1>, conv_p2a_kernel<CT, 1>.
+// one more template parameter (always 1): conv_p2_kernel<4, CT, 1, 1>, conv_p2_kernel<4, CT, 2, 1>, conv_p2a_kernel<CT, 1>.
 //
 // TERMS = 2: the arithmetic described above.  TERMS = 1 ("f16" mode of the perceptual loss, VUNET_TUNE_P2_TERMS): the hi
 // plane of a planes tensor is by itself a complete scaled-fp16 image of it, so a one-term instantiation copies only the hi

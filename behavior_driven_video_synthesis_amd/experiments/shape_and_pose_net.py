@@ -47,7 +47,7 @@ DEFAULT_CONFIG = {
                  "gamma_step": 0.00001, "n_init_batches": 4, "adam_betas": (0.5, 0.9), "end_iteration": 150000,
                  "imax_scaling": "none", "information_max": 1000, "ll_weight": 1.0, "train_regressor": True,
                  "weight_regressor": 4.0, "reg_steps": 5,
-                 # optional "vgg_precision": "split" (the default where the key is absent) | "f16" -- the arithmetic of the frozen
+                 # optional "vgg_precision": "split" (the default where the key is absent) | "f16" | "f16grad" -- arithmetic of the frozen
                  # VGG19's p2 convolutions (models/imagenet_pretrained.py: set_p2_precision); read at construction
                  # adversarial term: not part of the reference loop, off by default
                  "gan": {"enabled": False, "weight": 1.0, "pd_scales": 3, "grad_pen": False, "lambda_gp": 10,

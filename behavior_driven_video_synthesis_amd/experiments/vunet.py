@@ -33,7 +33,7 @@ DEFAULT_CONFIG = {
     "training": {"batch_size": 8, "vgg_weights": [1.0] * 6, "dropout_prob": 0.05, "lr": 0.0008, "kl_init": 1e-6,
                  "kl_max": 1.0, "n_init_batches": 4, "adam_betas": (0.5, 0.9), "end_iteration": 300000,
                  "ll_weight": 5.0},
-    # optional training.vgg_precision: "split" (the default where the key is absent) | "f16" -- the arithmetic of the frozen
+    # optional training.vgg_precision: "split" (the default where the key is absent) | "f16" | "f16grad" -- arithmetic of the frozen
     # VGG19's p2 convolutions (models/imagenet_pretrained.py: set_p2_precision); read at construction
 }
 

@@ -120,25 +120,31 @@ def enable_p2(on: bool = True):
 
 # Precision of the p2 convolutions.  "split" (default): two scaled fp16 terms per operand, three products per tap -- fp32
 # accuracy.  "f16": ONE product per tap on the hi planes of activations and weights (csrc/conv_p2_kernel.h, P2_TERMS = 1):
-# operands rounded to fp16's 11 bits, fp32 accumulation; half the operand bytes, a third of the matrix instructions.  The
-# planes layout, conv1_1 (fp32 FMA), the L1 tap / pool kernels and the masks are the same in both modes, and a stack /
-# geometry the p2 kernels do not cover runs the per-layer three-product path in both.  The mode is the process-wide tuning
-# key "p2_terms" (VUNET_TUNING=p2_terms=1 selects "f16" for a whole program); a captured training step bakes the kernel
-# choice in, so ShapePoseNet keys its recorded graphs by the mode (a switch after capture records the step again).
-P2_PRECISIONS = ("split", "f16")
+# operands rounded to fp16's 11 bits, fp32 accumulation; half the operand bytes, a third of the matrix instructions -- in both
+# forward passes and the data-gradient chain; measured NOT usable for training (the rounded features flip ReLU masks,
+# sign(p - t) and pool argmaxima: DESIGN.md 4c).  "f16grad": the forward passes exactly as in "split" (same kernels, same loss
+# terms, same masks), one product per tap in the 13 data-gradient launches only -- the gradient stays within the 5e-3 the two
+# fp32-accurate paths are allowed to differ by.  The planes layout, conv1_1 (fp32 FMA), the L1 tap / pool kernels and the
+# masks are the same in every mode, and a stack / geometry the p2 kernels do not cover runs the per-layer three-product path
+# in every mode.  The mode is the process-wide tuning key "p2_terms" (0 / 2 = "split", 1 = "f16", 3 = "f16grad";
+# VUNET_TUNING=p2_terms=3 selects "f16grad" for a whole program); a captured training step bakes the kernel choice in, so
+# ShapePoseNet keys its recorded graphs by the mode (a switch after capture records the step again).
+P2_PRECISIONS = ("split", "f16", "f16grad")
+_P2_TERMS_OF = {"split": 0, "f16": 1, "f16grad": 3}
+_P2_MODES = " | ".join(P2_PRECISIONS)
 
 
 def p2_precision() -> str:
-    return "f16" if ops.tuning("p2_terms") == 1 else "split"
+    return {1: "f16", 3: "f16grad"}.get(ops.tuning("p2_terms"), "split")
 
 
 def set_p2_precision(mode: str) -> str:
-    """Select the arithmetic of the perceptual loss's p2 convolutions, "split" | "f16"; returns the previous mode."""
+    """Select the arithmetic of the perceptual loss's p2 convolutions, "split" | "f16" | "f16grad"; returns the previous mode."""
     if mode not in P2_PRECISIONS:
-        raise ValueError(f"unknown p2 precision {mode!r} (split | f16)")
+        raise ValueError(f"unknown p2 precision {mode!r} ({_P2_MODES})")
     prev = p2_precision()
     if mode != prev:
-        ops.set_tuning("p2_terms", 1 if mode == "f16" else 0)
+        ops.set_tuning("p2_terms", _P2_TERMS_OF[mode])
     return prev
 
 
@@ -146,7 +152,7 @@ def vgg_precision_from_config(training: dict) -> str:
     """``training.vgg_precision`` of a trainer's config (default "split"), checked."""
     mode = training.get("vgg_precision", "split")
     if mode not in P2_PRECISIONS:
-        raise ValueError(f"training.vgg_precision: unknown mode {mode!r} (split | f16)")
+        raise ValueError(f"training.vgg_precision: unknown mode {mode!r} ({_P2_MODES})")
     return mode
 
 

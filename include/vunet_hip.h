@@ -423,7 +423,15 @@ int vunet_set_dropout_step(const uint32_t* step_dev);
  *                              rounded to fp16's 11 bits; the "f16" mode of the perceptual loss), forward and data gradient;
  *                              0 / 2 = two terms per operand, three products (fp32 accuracy).  The one-term kernels read the
  *                              same planes and the same weight image and write both output planes; there is no lockstep
- *                              one-term kernel (P2_FORM = 3 then runs the antiphase one)
+ *                              one-term kernel (P2_FORM = 3 then runs the antiphase one).
+ *                              3 = one product per tap in DATA-GRADIENT launches only (the "f16grad" mode: same loss terms as the
+ *                              default, gradient 7.6e-4 off in relative L2).  What counts as a data gradient: in vunet_p2_conv
+ *                              d->relu == 0 && shift == NULL; in vunet_p2_conv_variant, which has the descriptor only,
+ *                              d->relu == 0.  Every other launch takes exactly the path of 0.  A data gradient runs the
+ *                              four-wave one-term kernel -- conv_p2_kernel<4, CT, 2, 1> (two x tiles in LDS, the next chunk
+ *                              fetched one chunk ahead) where the launch has at most 256 workgroups, conv_p2_kernel<4, CT, 1, 1>
+ *                              beyond -- unless P2_FORM = 2 / 3 asks for conv_p2a_kernel<CT, 1>; P2_FORM = 1 keeps
+ *                              conv_p2_kernel<4, CT, 1, 1> (profiles/p2_f16grad_time.txt)
  * Returns VUNET_ERR_ARG for an unknown key. */
 #define VUNET_TUNE_SPLIT_FORCE_NT 0
 #define VUNET_TUNE_TILED_FORCE_NT 1
@@ -550,8 +558,9 @@ typedef struct vunet_p2_desc {
 } vunet_p2_desc;
 int vunet_p2_conv_supported(const vunet_p2_desc* d);   /* 1 / 0 */
 int vunet_p2_conv_variant(const vunet_p2_desc* d, char* name, int32_t len);   /* kernel instantiation, rocprofv3 spelling; the
-                                                                                 one-term kernels (VUNET_TUNE_P2_TERMS = 1) are
-                                                                                 conv_p2a_kernel<CT, 1> / conv_p2_kernel<4, CT, 1, 1> */
+                                                                                 one-term kernels (VUNET_TUNE_P2_TERMS = 1, or 3
+                                                                                 and d->relu == 0) are conv_p2a_kernel<CT, 1> /
+                                                                                 conv_p2_kernel<4, CT, 1 | 2, 1> */
 /* y = [relu]( conv3x3_pad1(x; image) + shift ), or with `mask` (planes shaped like y: the forward activation that feeds the
  * layer below) the data-gradient form  y = conv3x3(x; dgrad image) * [mask != 0].  image / wk from vunet_p2_pack_weights. */
 int vunet_p2_conv(const vunet_p2_desc* d, const void* x, const int32_t* xmeta, const void* w_image, const float* wk,

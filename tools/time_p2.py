@@ -2,8 +2,9 @@
 """Time vunet_p2_conv (pre-split planes, csrc/conv_p2.hip) beside the h2 kernel of vunet_conv2d on the VGG19 layer shapes of
 the bs-16 256x256 step (needs an MI355X).
 
-    python tools/time_p2.py [--form 0|1|2] [--terms 2|1] [--reps 20]
-    python tools/time_p2.py --ab [--windows 6]          one term against two, alternating windows in ONE process
+    python tools/time_p2.py [--form 0|1|2] [--terms 2|1|3] [--reps 20]
+    python tools/time_p2.py --ab [--form 0|1|2] [--windows 6]     one term against two, alternating windows in ONE process; the
+                                                        data gradient also under --terms 3 ("f16grad": one term there only)
 
 Per shape: average launch time over --reps back-to-back launches (HIP events; sustained, clock-limited regime), algorithmic
 TFLOP/s and fraction of the 833 TFLOP/s three-product roof (also printed for --terms 1, whose own roof is three times that) --
@@ -23,9 +24,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--form", type=int, default=0)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--batch", type=int, default=16)
-ap.add_argument("--terms", type=int, default=2, choices=(1, 2),
-                help="products per operand of the p2 kernels: 2 = split (three products per tap), 1 = the f16 mode (one)")
-ap.add_argument("--ab", action="store_true", help="time --terms 1 against --terms 2 in alternating windows (no h2 column)")
+ap.add_argument("--terms", type=int, default=2, choices=(1, 2, 3),
+                help="products per operand of the p2 kernels: 2 = split (three products per tap), 1 = the f16 mode (one), "
+                     "3 = the f16grad mode (forward as 2, data gradient one term on its own form rule)")
+ap.add_argument("--ab", action="store_true",
+                help="time --terms 1 (and, for the data gradient, 3) against --terms 2 in alternating windows (no h2 column)")
 ap.add_argument("--windows", type=int, default=6, help="--ab: windows per term count and figure (the median is reported)")
 args = ap.parse_args()
 ops.set_tuning("p2_form", args.form)
@@ -47,20 +50,22 @@ def timed(fn):
     return e0.elapsed_time(e1) / args.reps * 1e3
 
 
-def variant(n, c, s, m):
-    d = ops.P2Desc(n, c, s, s, m, 0)
+def variant(n, c, s, m, relu):
+    """The kernel of a forward (relu = 1) or data-gradient (relu = 0) launch under the tuning values in force."""
+    d = ops.P2Desc(n, c, s, s, m, relu)
     buf = ctypes.create_string_buffer(96)
     ops._call("vunet_p2_conv_variant", ctypes.byref(d), buf, 96)
     return buf.value.decode()
 
 
 def ab(n):
-    """One term against two on the same buffers: per figure --windows windows of --reps launches per term count, the term
-    counts ALTERNATING window by window (clock and temperature drift hit both alike); medians."""
+    """One term against two on the same buffers: per figure --windows windows of --reps launches per value of p2_terms, the
+    values ALTERNATING window by window (clock and temperature drift hit all alike); medians.  Forward: 2, 1 (3 launches the
+    kernel of 2).  Data gradient: 2, 1 and 3 -- 1 and 3 differ in the form they pick, the kernel of each is printed."""
     import statistics
-    print(f"batch {n}, p2 form {args.form} (0 = dispatcher): terms 2 vs terms 1, {args.windows} alternating windows of {args.reps} "
-          "launches each, median window (us per launch)")
-    tot = {"f2": 0.0, "f1": 0.0, "d2": 0.0, "d1": 0.0}
+    print(f"batch {n}, p2 form {args.form} (0 = dispatcher): terms 2 vs terms 1 (data gradient: and terms 3), {args.windows} "
+          f"alternating windows of {args.reps} launches each, median window (us per launch)")
+    tot = {"f2": 0.0, "f1": 0.0, "d2": 0.0, "d1": 0.0, "d3": 0.0}
     for name, cin, cout, s in SHAPES:
         g = torch.Generator().manual_seed(1)
         x = torch.randn(n, cin, s, s, generator=g).clamp_min(0).cuda()
@@ -71,24 +76,25 @@ def ab(n):
         px, pdy = ops.p2_from_nchw(x), ops.p2_from_nchw(dy)
         out, gout = ops.Planes((n, cout, s, s), "cuda"), ops.Planes((n, cin, s, s), "cuda")
         W.image(False), W.image(True)
-        fns = {"f": lambda: ops.p2_conv(px, W, out), "d": lambda: ops.p2_conv(pdy, W, gout, dgrad=True, mask=px)}
+        fns = {"f": (lambda: ops.p2_conv(px, W, out), (2, 1)), "d": (lambda: ops.p2_conv(pdy, W, gout, dgrad=True, mask=px), (2, 1, 3))}
         res, names = {}, {}
-        for kind, fn in fns.items():
-            t = {1: [], 2: []}
+        for kind, (fn, values) in fns.items():
+            t = {v: [] for v in values}
             for _ in range(args.windows):
-                for terms in (2, 1):
+                for terms in values:
                     ops.set_tuning("p2_terms", terms)
                     t[terms].append(timed(fn))
-            for terms in (2, 1):
+            for terms in values:
                 res[kind + str(terms)] = statistics.median(t[terms])
                 ops.set_tuning("p2_terms", terms)
-                names[kind + str(terms)] = variant(n, cin, s, cout) if kind == "f" else variant(n, cout, s, cin)
+                names[kind + str(terms)] = variant(n, cin, s, cout, 1) if kind == "f" else variant(n, cout, s, cin, 0)
         for k in tot:
             tot[k] += res[k]
         print(f"{name:8s} {cin:3d}->{cout:3d} @{s:3d}^2 | fwd  2: {res['f2']:7.1f}  1: {res['f1']:7.1f}  x{res['f2'] / res['f1']:4.2f} "
-              f"[{names['f1']}] | dgrad 2: {res['d2']:7.1f}  1: {res['d1']:7.1f}  x{res['d2'] / res['d1']:4.2f} [{names['d1']}]")
+              f"[{names['f1']}] | dgrad 2: {res['d2']:7.1f} [{names['d2']}]  1: {res['d1']:7.1f}  x{res['d2'] / res['d1']:4.2f} "
+              f"[{names['d1']}]  3: {res['d3']:7.1f}  x{res['d2'] / res['d3']:4.2f} [{names['d3']}]")
     print("sum over the listed shapes (us): " + ", ".join(f"{k} {v:.0f}" for k, v in tot.items())
-          + f" | fwd x{tot['f2'] / tot['f1']:.2f}, dgrad x{tot['d2'] / tot['d1']:.2f}")
+          + f" | fwd x{tot['f2'] / tot['f1']:.2f}, dgrad 1: x{tot['d2'] / tot['d1']:.2f}, dgrad 3: x{tot['d2'] / tot['d3']:.2f}")
     ops.set_tuning("p2_terms", 0)
 
 
@@ -128,5 +134,6 @@ for name, cin, cout, s in SHAPES:
                                     None, ops._p(x), ops._p(dx), ops._p(ady), None, ops._p(am), ops._stream()))
     tot["p2f"] += us_f; tot["h2f"] += us_hf; tot["p2d"] += us_d; tot["h2d"] += us_hd
     f = lambda us: f"{us:7.1f} us {flop / us / 1e6:6.1f} TF/s {flop / us / 1e6 / 833.3:5.3f}"
-    print(f"{name:8s} {cin:3d}->{cout:3d} @{s:3d}^2 | fwd  p2 {f(us_f)} | h2 {f(us_hf)} | dgrad p2 {f(us_d)} | h2 {f(us_hd)}")
+    print(f"{name:8s} {cin:3d}->{cout:3d} @{s:3d}^2 | fwd  p2 {f(us_f)} | h2 {f(us_hf)} | dgrad p2 {f(us_d)} | h2 {f(us_hd)} "
+          f"| {variant(n, cin, s, cout, 1)} / {variant(n, cout, s, cin, 0)}")
 print("sum over the listed shapes (us): " + ", ".join(f"{k} {v:.0f}" for k, v in tot.items()))
