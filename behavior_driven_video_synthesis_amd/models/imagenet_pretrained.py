@@ -378,9 +378,7 @@ class _P2Engine:
         c0 = st["shp"][0][0]
         dconv = D.to_nchw()
         dx = torch.empty(n, 3, h, w, device=self.device, dtype=torch.float32)
-        d = ops.ConvDesc(N=n, C1=c0, C2=0, Hs=h, Ws=w, M=3, m_off=0, Mpad=wt_d.shape[1], Ho=h, Wo=w, KH=3, KW=3, stride=1, pad=1,
-                         mode=1, in_act=ops.ACT_NONE, in_slope=0.0, drop_p=0.0, drop_seed=0, out_act=ops.ACT_NONE, d2s=0)
-        ops._conv_gather(d, dconv, None, wt_d, None, None, None, dx, wx_d)
+        ops._conv_gather(ops._dgrad_desc(n, c0, h, w, 3, h, w, 3, 1, 1, wt_d.shape[1]), dconv, None, wt_d, None, None, None, dx, wx_d)
         return dx
 
 

@@ -14,6 +14,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -472,11 +473,45 @@ class _Timed:
             _prof["recs"].append((self.name, self.flop, self.e0, self.e1))
 
 
+def _timed(key_fn, *args):
+    """The timer of one launch; ``key_fn(*args) -> (record key, FLOPs)`` runs only while profiling."""
+    return _Timed(*key_fn(*args)) if _prof["on"] else _NO_TIMER
+
+
+def _kernel_name(query, *args):
+    """What a ``vunet_*_variant`` entry point calls the kernel a launch with these arguments would run."""
+    buf = ctypes.create_string_buffer(96)
+    _call(query, *args, buf, 96)
+    return buf.value.decode()
+
+
+def _gather_key(desc, has_aux, scheme, mask):
+    t = desc.KH * desc.KW
+    if desc.mode == 0:
+        name, flop = "conv_gather_fwd", 2.0 * desc.N * desc.Ho * desc.Wo * desc.M * (desc.C1 + desc.C2) * t
+    else:  # transposed gather: MACs of the forward conv restricted to this source
+        name, flop = "conv_gather_dgrad", 2.0 * desc.N * desc.Hs * desc.Ws * desc.C1 * desc.M * t
+    kname = _kernel_name("vunet_conv2d_variant", ctypes.byref(desc), has_aux, scheme, mask)
+    if mask and kname.startswith("conv_tiled"):   # (the fused-ReLU form of the tiled kernel)
+        kname = kname.replace(", 1, 0, ", ", 1, 4, ")
+    return (name, desc.N, desc.C1, desc.C2, desc.Hs, desc.Ws, desc.M, desc.KH, desc.stride, desc.in_act, kname), flop
+
+
+def _bf16_key(d):
+    return (("conv_bf16_fwd", d.N, d.C1, d.C2, d.Hs, d.Ws, d.M, d.KH, d.stride, d.in_act, "conv_bf16_kernel"),
+            2.0 * d.N * d.Ho * d.Wo * d.M * (d.C1 + d.C2) * d.KH * d.KW)
+
+
+def _wgrad_key(wd):
+    return (("conv_wgrad", wd.N, wd.C1, wd.C2, wd.Hs, wd.Ws, wd.Cout, wd.KH, wd.stride, wd.in_act,
+             _kernel_name("vunet_conv2d_wgrad_variant", ctypes.byref(wd))),
+            2.0 * wd.N * wd.Ho * wd.Wo * wd.Cout * (wd.C1 + wd.C2) * wd.KH * wd.KW)
+
+
 def _conv_gather(desc: ConvDesc, x1, x2, wt, shift, res, aux, y, wx=None, amax=None, res2=None):
     """``amax``: the |x| partial maxima if the caller already has them (h2 scheme), else taken from the producer's tag or
     computed here when needed.  Returns the maxima the launch used (None if it did not need any).  When the fp16 kernel
     runs (and does not store through depth-to-space) y is tagged with the maxima of what it wrote."""
-    t = desc.KH * desc.KW
     scheme = _scheme() if wx is not None else 0
     amax_out = None
     if scheme == 2:
@@ -489,17 +524,7 @@ def _conv_gather(desc: ConvDesc, x1, x2, wt, shift, res, aux, y, wx=None, amax=N
         amax = None
     if _scheme() == 2 and _publishes_amax(desc, aux is not None, res is not None, wx is not None):
         amax_out = _new_amax_out(y.device)   # the h2, 1x1 and LDS-tiled kernels leave max|y| there
-    if desc.mode == 0:
-        name, flop = "conv_gather_fwd", 2.0 * desc.N * desc.Ho * desc.Wo * desc.M * (desc.C1 + desc.C2) * t
-    else:  # transposed gather: MACs of the forward conv restricted to this source
-        name, flop = "conv_gather_dgrad", 2.0 * desc.N * desc.Hs * desc.Ws * desc.C1 * desc.M * t
-    kname = ""
-    if _prof["on"]:
-        buf = ctypes.create_string_buffer(96)
-        _call("vunet_conv2d_variant", ctypes.byref(desc), 0 if aux is None else 1, 0 if wx is None else scheme, 0, buf, 96)
-        kname = buf.value.decode()
-    with (_Timed((name, desc.N, desc.C1, desc.C2, desc.Hs, desc.Ws, desc.M, desc.KH, desc.stride, desc.in_act, kname),
-                flop) if _prof["on"] else _NO_TIMER):
+    with _timed(_gather_key, desc, 0 if aux is None else 1, 0 if wx is None else scheme, 0):
         a1, a2 = _amax_pair(amax)
         rc = _lib.lib().vunet_conv2d_a2(ctypes.byref(desc), _p(x1), _p(x2), _p(wt), _p(wx), _p(shift), _p(res), _p(res2),
                                         _p(aux), _p(y), _p(a1), _p(a2), _p(amax_out), _stream())
@@ -517,6 +542,30 @@ def _conv_gather(desc: ConvDesc, x1, x2, wt, shift, res, aux, y, wx=None, amax=N
     return amax
 
 
+# ---- one builder per descriptor: the forward gather, the transposed gather of a data gradient, the weight gradient
+def _fwd_desc(n, c1, c2, hs, ws, cout, ho, wo, k, stride, pad, mpad, in_act=ACT_NONE, in_slope=0.0, drop_p=0.0, drop_seed=0,
+              out_act=ACT_NONE, d2s=0):
+    return ConvDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, M=cout, m_off=0, Mpad=mpad, Ho=ho, Wo=wo, KH=k, KW=k, stride=stride,
+                    pad=pad, mode=0, in_act=in_act, in_slope=in_slope, drop_p=drop_p, drop_seed=drop_seed, out_act=out_act,
+                    d2s=d2s)
+
+
+def _dgrad_desc(n, cout, ho, wo, cs, hs, ws, k, stride, pad, mpad, m_off=0, aux_act=ACT_NONE, aux_slope=0.0, aux_drop_p=0.0,
+                aux_drop_seed=0):
+    """w.r.t. the ``cs`` input channels from ``m_off`` on: dy is the source of a transposed gather, the forward's prologue its ``aux_*``"""
+    return ConvDesc(N=n, C1=cout, C2=0, Hs=ho, Ws=wo, M=cs, m_off=m_off, Mpad=mpad, Ho=hs, Wo=ws, KH=k, KW=k, stride=stride,
+                    pad=pad, mode=1, in_act=ACT_NONE, in_slope=0.0, drop_p=0.0, drop_seed=0, out_act=ACT_NONE, d2s=0,
+                    aux_act=aux_act, aux_slope=aux_slope, aux_drop_p=aux_drop_p, aux_drop_seed=aux_drop_seed)
+
+
+def _wgrad_desc(n, c1, c2, hs, ws, cout, ho, wo, k, stride, pad, scheme, in_act=ACT_NONE, in_slope=0.0, drop_p=0.0,
+                drop_seed=0):
+    """``scheme`` (_SCHEMES): f32 keeps the fp32-input kernels (flags bit 0), h2 asks for the fp16 split (bit 1; the caller owes the maxima)"""
+    return WgradDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, Cout=cout, Ho=ho, Wo=wo, KH=k, KW=k, stride=stride, pad=pad,
+                     in_act=in_act, in_slope=in_slope, drop_p=drop_p, drop_seed=drop_seed, nsplit=1,
+                     flags=(1, 0, 2)[scheme])
+
+
 # ------------------------------------------------------------------------------------------------
 # Plain convolution primitives that are closed under differentiation (forward / data gradient / weight
 # gradient each differentiate into the other two).  They back the *double-backward* path only (R1 penalty,
@@ -526,12 +575,6 @@ def _conv_gather(desc: ConvDesc, x1, x2, wt, shift, res, aux, y, wx=None, amax=N
 def _plain_pack(w, need_dgrad):
     cout, cin = w.shape[0], w.shape[1]
     return pack_weights(w.contiguous(), None, None, None, None, cin, 0, 1, need_dgrad)   # (wt_f, wt_d, ..., wx_f, wx_d)
-
-
-def _plain_desc(n, cin, hs, ws, m, ho, wo, k, stride, pad, mode, mpad):
-    return ConvDesc(N=n, C1=cin, C2=0, Hs=hs, Ws=ws, M=m, m_off=0, Mpad=mpad, Ho=ho, Wo=wo, KH=k, KW=k,
-                    stride=stride, pad=pad, mode=mode, in_act=ACT_NONE, in_slope=0.0, drop_p=0.0, drop_seed=0,
-                    out_act=ACT_NONE, d2s=0, aux_act=ACT_NONE, aux_slope=0.0, aux_drop_p=0.0, aux_drop_seed=0)
 
 
 class ConvPlainFwd(torch.autograd.Function):
@@ -547,7 +590,7 @@ class ConvPlainFwd(torch.autograd.Function):
         pk = _plain_pack(w, False)
         wt_f = pk[0]
         y = torch.empty(n, cout, ho, wo, device=x.device, dtype=torch.float32)
-        _conv_gather(_plain_desc(n, cin, hs, ws, cout, ho, wo, k, stride, pad, 0, wt_f.shape[1]), x, None, wt_f, None,
+        _conv_gather(_fwd_desc(n, cin, 0, hs, ws, cout, ho, wo, k, stride, pad, wt_f.shape[1]), x, None, wt_f, None,
                      None, None, y, pk[5])
         ctx.save_for_backward(x, w)
         ctx.geo = (stride, pad)
@@ -574,7 +617,7 @@ class ConvPlainDgrad(torch.autograd.Function):
         pk = _plain_pack(w, True)
         wt_d = pk[1]
         dx = torch.empty(n, cin, hs, ws, device=dy.device, dtype=torch.float32)
-        _conv_gather(_plain_desc(n, cout, ho, wo, cin, hs, ws, k, stride, pad, 1, wt_d.shape[1]), dy, None, wt_d, None,
+        _conv_gather(_dgrad_desc(n, cout, ho, wo, cin, hs, ws, k, stride, pad, wt_d.shape[1]), dy, None, wt_d, None,
                      None, None, dx, pk[6])
         ctx.save_for_backward(dy, w)
         ctx.geo = (stride, pad)
@@ -598,9 +641,8 @@ class ConvPlainWgrad(torch.autograd.Function):
         x, dy = _c(x), _c(dy)
         n, cin, hs, ws = x.shape
         cout, ho, wo = dy.shape[1], dy.shape[2], dy.shape[3]
-        wd = WgradDesc(N=n, C1=cin, C2=0, Hs=hs, Ws=ws, Cout=cout, Ho=ho, Wo=wo, KH=k, KW=k, stride=stride, pad=pad,
-                       in_act=ACT_NONE, in_slope=0.0, drop_p=0.0, drop_seed=0, nsplit=1,
-                       flags=0 if _scheme() else 1)
+        # (no maxima at hand here: the bf16 split wherever a split scheme is on)
+        wd = _wgrad_desc(n, cin, 0, hs, ws, cout, ho, wo, k, stride, pad, 1 if _scheme() else 0)
         ns = _lib.lib().vunet_conv2d_wgrad_nsplit(ctypes.byref(wd))
         wd.nsplit = ns
         ktot = k * k * cin
@@ -934,6 +976,37 @@ def _wn_buffers(n_slab: int, n_work: int, dev):
     return ar[0][off:off + n_slab], ar[0][off + ((n_slab + 63) & ~63):off + ((n_slab + 63) & ~63) + n_work]
 
 
+# One deferred layer: ``layer`` is what the batched weight-norm backward needs of it, as device addresses (None: absent) --
+# the tuple of a group's ``layer`` records IS the key of its uploaded item table (the buffers are persistent, so it repeats
+# from step to step); ``params``: the parameters whose .grad the flush completes (grad hooks); ``keep``: tensors the records
+# point at that nothing else is guaranteed to hold until the flush; ``late``: the layer's weight-gradient launch (descriptor
+# bytes + addresses) where that waits for the flush too (vunet_conv2d_wgrad_multi), else None.
+_WnLayer = namedtuple("_WnLayer", "slabs dshift v g bias gamma invnorm dv dg dbias dgamma dbeta workspace "
+                                  "cout c1 c2 k kind nsplit")
+_LateWgrad = namedtuple("_LateWgrad", "desc x1 x2 dy slabs dshift amax_x amax_x2 amax_dy")
+_Deferred = namedtuple("_Deferred", "layer params keep late")
+
+
+def _wn_table(items, dev_idx):
+    """Build and upload the item table of a group -> (table, n, max_cout, max_reduce_blocks)."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("batched weight-norm backward: this group's item table has not been built yet and cannot be "
+                           "uploaded while a hipGraph is being captured -- run an eager step of the same geometry on "
+                           "the capture stream first (ShapePoseNet does)")
+    arr = (WnBwdItem * len(items))()
+    max_cout = max_blocks = 1
+    for it, item in zip(arr, items):
+        L = item.layer
+        it.slabs, it.dshift, it.v, it.g, it.bias, it.gamma, it.invnorm = L.slabs, L.dshift, L.v, L.g, L.bias, L.gamma, L.invnorm
+        it.dv, it.dg, it.dbias, it.dgamma, it.dbeta, it.workspace = L.dv, L.dg, L.dbias, L.dgamma, L.dbeta, L.workspace
+        it.d = WnDesc(L.cout, L.c1, L.c2, L.k, L.k, L.kind, 0)
+        it.nsplit, it.accumulate = L.nsplit, 1
+        max_cout = max(max_cout, L.cout)
+        max_blocks = max(max_blocks, L.cout * ((L.k * L.k * (L.c1 + L.c2) + 63) // 64))
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(torch.device("cuda", dev_idx))
+    return table, len(items), max_cout, max_blocks
+
+
 def _wn_flush_stream(stream_key):
     items = _wn_batch["pending"].pop(stream_key, None)
     ar = _wn_batch["arena"].get(stream_key)
@@ -942,44 +1015,30 @@ def _wn_flush_stream(stream_key):
     if not items:
         return
     dev_idx, raw = stream_key
-    sig = tuple(it[0] for it in items)
+    sig = tuple(item.layer for item in items)
     tab = _wn_batch["tables"].get(sig)
     if tab is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("batched weight-norm backward: this group's item table has not been built yet and cannot be "
-                               "uploaded while a hipGraph is being captured -- run an eager step of the same geometry on "
-                               "the capture stream first (ShapePoseNet does)")
-        arr = (WnBwdItem * len(items))()
-        max_cout = max_blocks = 1
-        for i, item in enumerate(items):
-            fields = item[0]
-            (slabs, dshift, v, g, bias, gamma, invnorm, dv, dg, dbias, dgamma, dbeta, work, dsc, ns) = fields
-            it = arr[i]
-            it.slabs, it.dshift, it.v, it.g, it.bias, it.gamma, it.invnorm = slabs, dshift, v, g, bias, gamma, invnorm
-            it.dv, it.dg, it.dbias, it.dgamma, it.dbeta, it.workspace = dv, dg, dbias, dgamma, dbeta, work
-            cout, c1, c2, kh, kw, kind = dsc
-            it.d = WnDesc(cout, c1, c2, kh, kw, kind, 0)
-            it.nsplit, it.accumulate = ns, 1
-            max_cout = max(max_cout, cout)
-            max_blocks = max(max_blocks, cout * ((kh * kw * (c1 + c2) + 63) // 64))
-        table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(torch.device("cuda", dev_idx))
-        tab = _wn_batch["tables"][sig] = (table, len(items), max_cout, max_blocks)
+        tab = _wn_batch["tables"][sig] = _wn_table(items, dev_idx)
     table, n, max_cout, max_blocks = tab
     # layers whose weight-gradient LAUNCH was deferred too (short launches on small maps): all of them now, grouped by
     # kernel form -- a handful of launches instead of one per layer, ordered before the reduction that reads their slabs
-    wg = [it[3] for it in items if len(it) > 3 and it[3] is not None]
-    if wg:
-        arr = (WgradItem * len(wg))()
-        for i, (wd_bytes, ptrs) in enumerate(wg):
-            ctypes.memmove(ctypes.addressof(arr[i].d), wd_bytes, ctypes.sizeof(WgradDesc))
-            (arr[i].x1, arr[i].x2, arr[i].dy, arr[i].slabs, arr[i].dshift, arr[i].amax_x, arr[i].amax_x2,
-             arr[i].amax_dy) = ptrs
-        _call("vunet_conv2d_wgrad_multi", arr, len(wg), ctypes.c_void_p(raw))
+    late = [item.late for item in items if item.late is not None]
+    if late:
+        arr = (WgradItem * len(late))()
+        for it, w in zip(arr, late):
+            ctypes.memmove(ctypes.addressof(it.d), w.desc, ctypes.sizeof(WgradDesc))
+            it.x1, it.x2, it.dy, it.slabs, it.dshift = w.x1, w.x2, w.dy, w.slabs, w.dshift
+            it.amax_x, it.amax_x2, it.amax_dy = w.amax_x, w.amax_x2, w.amax_dy
+        _call("vunet_conv2d_wgrad_multi", arr, len(late), ctypes.c_void_p(raw))
     _call("vunet_weightnorm_bwd_multi", _p(table), n, max_cout, max_blocks, ctypes.c_void_p(raw))
-    for it in items:
-        for p_ in it[1]:
-            for hook in _grad_hooks:
-                hook(p_)
+    for item in items:
+        _notify_grad_hooks(item.params)
+
+
+def _notify_grad_hooks(params):
+    for p_ in params:
+        for hook in _grad_hooks:
+            hook(p_)
 
 
 def flush_weight_grads():
@@ -989,13 +1048,11 @@ def flush_weight_grads():
     _wn_batch["callback_queued"] = False
 
 
-def _wn_defer(fields, params, keep, wgrad=None):
-    """``keep``: tensors the item points at that nothing else is guaranteed to hold until the flush.  ``wgrad``: (descriptor
-    bytes, pointers) of the layer's weight-gradient launch when that is deferred to the flush as well."""
+def _wn_defer(item: _Deferred):
     idx = torch.cuda.current_device()
     key = (idx, _raw_stream(idx))
     lst = _wn_batch["pending"].setdefault(key, [])
-    lst.append((fields, params, keep, wgrad))
+    lst.append(item)
     if len(lst) >= _WN_GROUP:
         _wn_flush_stream(key)
     elif not _wn_batch["callback_queued"]:
@@ -1003,6 +1060,242 @@ def _wn_defer(fields, params, keep, wgrad=None):
         # that called backward(), after every node has run)
         _wn_batch["callback_queued"] = True
         torch.autograd.Variable._execution_engine.queue_callback(flush_weight_grads)
+
+
+# ---- FusedConv: forward and backward orchestrate the functions below ("How a backward is scheduled")
+def _packed_weights(cfg, v, g, bias, gamma, beta, c1, c2, need_x):
+    """-> ((wt_f, wt_d, scale, shift, invnorm, wx_f, wx_d), from the active ``prepacked`` set?)"""
+    frozen = not any(t is not None and t.requires_grad for t in (v, g, bias, gamma, beta))
+    if cfg.owner is not None and not frozen:
+        old = cfg.owner.__dict__.get("_last_split")
+        new = (c1, c2, bool(need_x) or (old is not None and old[2]))
+        if new != old:
+            object.__setattr__(cfg.owner, "_last_split", new)   # (nn.Module.__setattr__ costs ~2 us per call)
+        pre = _active_prepack.get(id(cfg.owner))
+        if pre is not None and pre[0][:2] == (c1, c2) and not (need_x and pre[2] is None):
+            return pre[1:], True
+    if not frozen:
+        return pack_weights(v, g, bias, gamma, beta, c1, c2, cfg.kind, need_x), False
+    # frozen feature extractor (VGG19): pack once, reuse for every pass.  The packed buffers hang off the weight
+    # tensor itself (they die with it) and are stamped with every operand's storage address and version counter.
+    sub = (c1, c2, cfg.kind, bool(need_x), _scheme())
+    stamp = tuple(None if t is None else (t.data_ptr(), t._version) for t in (v, g, bias, gamma, beta))
+    hit = getattr(v, "_vunet_frozen_pack", {}).get(sub)
+    if hit is not None and hit[0] == stamp:
+        return hit[1], False
+    pack = pack_weights(v, g, bias, gamma, beta, c1, c2, cfg.kind, need_x)
+    if not hasattr(v, "_vunet_frozen_pack"):
+        v._vunet_frozen_pack = {}
+    v._vunet_frozen_pack[sub] = (stamp, pack)
+    return pack, False
+
+
+_NO_GRADS = (None, None, None, None, None)   # (dv, dg, dbias, dgamma, dbeta) of a layer that writes all of them in place
+
+
+class _LazyAmax:
+    """|t| partial maxima, taken at most once (on the stream current at the first ``get``) and shared by whoever asks."""
+    __slots__ = ("t", "amax")
+
+    def __init__(self, t):
+        self.t, self.amax = t, None
+
+    def get(self):
+        if self.amax is None:
+            self.amax = _amax_for(self.t)
+        return self.amax
+
+
+def _double_backward(ctx, x1, x2, v, g, bias, gamma, dy, g_alias):
+    """create_graph=True (the R1 penalty): differentiate the layer re-expressed with primitives autograd can differentiate again."""
+    cfg = ctx.cfg
+    res, beta = ctx.res_ref, ctx.param_refs[4]
+    with torch.enable_grad():
+        y2 = _differentiable_layer(x1, x2, res, v, g, bias, gamma, beta, cfg)
+    needs = list(ctx.needs_input_grad[:8])
+    if cfg.res_is_x1:
+        needs[2] = False   # the residual IS source 1: its gradient is already part of d/dx1
+    tensors = (x1, x2, res, v, g, bias, gamma, beta)
+    wanted = [t for t, need in zip(tensors, needs) if need and t is not None]
+    grads = iter(torch.autograd.grad(y2, wanted, dy, create_graph=True, allow_unused=True))
+    out = [next(grads) if (need and t is not None) else None for t, need in zip(tensors, needs)]
+    if g_alias is not None:
+        out[0] = g_alias if out[0] is None else out[0] + g_alias
+    return (*out, None)
+
+
+def _relu_dgrad(ctx, x1, y, wt_d, wx_d, dy, g_alias):
+    """Frozen ReLU layers (VGG19): the ReLU backward rides in the data-gradient kernel's staging -> dx1; None: not covered."""
+    n, c1, _, hs, ws, cout, ho, wo = ctx.dims
+    cfg = ctx.cfg
+    dx = torch.empty_like(x1)
+    d = _dgrad_desc(n, cout, ho, wo, c1, hs, ws, cfg.k, cfg.stride, cfg.pad, wt_d.shape[1])
+    add = dy if cfg.res_is_x1 else g_alias
+    with _timed(_gather_key, d, 0, 0 if wx_d is None else _scheme(), 1):
+        rc = -3
+        if wx_d is not None and _wants_split(d, False, cfg.res_is_x1, True):
+            amax = _amax_for(dy) if _scheme() == 2 else None
+            amax_out = _new_amax_out(dx.device) if _scheme() == 2 else None
+            rc = _lib.lib().vunet_conv2d_dgrad_relu_x6(ctypes.byref(d), _p(dy), _p(y), _p(wx_d), _p(add), _p(dx), _p(amax),
+                                                       _p(amax_out), _stream())
+            if rc == 0 and amax_out is not None:
+                _tag_amax(dx, amax_out)
+        if rc == -3:
+            rc = _lib.lib().vunet_conv2d_dgrad_relu(ctypes.byref(d), _p(dy), _p(y), _p(wt_d), _p(add), _p(dx), _stream())
+    if rc == 0:
+        if cfg.res_is_x1 and g_alias is not None:
+            dx.add_(g_alias)
+        return dx
+    if rc != -3:   # anything but VUNET_ERR_UNSUPPORTED is an error; unsupported geometries take the two-pass route
+        raise RuntimeError(f"vunet_conv2d_dgrad_relu failed with code {rc}")
+    if _prof["on"] and _prof["recs"]:
+        _prof["recs"].pop()
+    return None
+
+
+def _out_act_bwd(ctx, y, dy, premasked):
+    """dy -> the gradient at the convolution's own output (``premasked``: dy's producer has applied the ReLU mask)."""
+    n, _, _, _, _, cout, ho, wo = ctx.dims
+    cfg = ctx.cfg
+    dconv = dy
+    if cfg.out_act != ACT_NONE and not premasked:
+        dconv = torch.empty_like(dy)
+        _call("vunet_act_bwd_from_out", _p(y), _p(dy), _p(dconv), cfg.out_act, cfg.in_slope, dy.numel(), _stream())
+    if cfg.d2s:
+        t = torch.empty(n, cout, ho, wo, device=dy.device, dtype=torch.float32)
+        _call("vunet_space_to_depth", _p(dconv), _p(t), n, cout // 4, 2 * ho, 2 * wo, _stream())
+        carry_amax_tag(dconv, t)   # a permutation: the same values, the same maxima
+        dconv = t
+    return dconv
+
+
+def _wgrad_launch(wd, x1, x2, dconv, slabs, dshift, amax_x, amax_dy, deferred):
+    """Launch the weight gradient into ``slabs`` -> None; a deferred layer's SHORT launch (small maps, 1x1) only -> its record:
+    it waits for the flush, where the layers of one kernel form share a launch (per-launch timing runs keep them apart)."""
+    ax1, ax2 = _amax_pair(amax_x)
+    if deferred and _wn_batch["wgrad"] and not _prof["on"] and _wgrad_batchable(wd):
+        return _LateWgrad(bytes(wd), x1.data_ptr(), _ptr_or_none(x2), dconv.data_ptr(), slabs.data_ptr(), dshift.data_ptr(),
+                          _ptr_or_none(ax1), _ptr_or_none(ax2), _ptr_or_none(amax_dy))
+    with _timed(_wgrad_key, wd):
+        _call("vunet_conv2d_wgrad_a2", ctypes.byref(wd), _p(x1), _p(x2), _p(dconv), _p(slabs), _p(dshift), _p(ax1), _p(ax2),
+              _p(amax_dy), _stream())
+    return None
+
+
+def _wn_bwd_now(ctx, slabs, dshift, ns, v, g, bias, gamma, invnorm):
+    """Weight-norm backward at once: a launch for the gradients written in place (+=), one for those returned (-> those)."""
+    _, c1, c2, _, _, cout, _, _ = ctx.dims
+    k = ctx.cfg.k
+    wanted = [p_ is not None and need for p_, need in zip(ctx.param_refs, ctx.needs_input_grad[3:8])]
+    direct = [w_ and _has_direct_grad(p_) for p_, w_ in zip(ctx.param_refs, wanted)]   # written in place (+=) by the kernel
+    outs = [None if not w_ else p_.grad if d_ else torch.empty_like(like)   # (beta has gamma's shape)
+            for p_, w_, d_, like in zip(ctx.param_refs, wanted, direct, (v, g, bias, gamma, gamma))]
+    n_direct = sum(direct)
+    n_returned = sum(o is not None for o in outs) - n_direct
+    wn = WnDesc(cout, c1, c2, k, k, ctx.cfg.kind, 0)
+    work = torch.empty(cout * (k * k * (c1 + c2) + 1), device=slabs.device, dtype=torch.float32)
+    for sel_direct, count in ((True, n_direct), (False, n_returned)):
+        if count:
+            sel = [o if (o is not None and d_ == sel_direct) else None for o, d_ in zip(outs, direct)]
+            _call("vunet_weightnorm_bwd", ctypes.byref(wn), _p(slabs), _p(dshift), ns, _p(v), _p(g), _p(bias), _p(gamma),
+                  _p(invnorm), _p(sel[0]), _p(sel[1]), _p(sel[2]), _p(sel[3]), _p(sel[4]), _p(work),
+                  1 if sel_direct else 0, _stream())
+    _notify_grad_hooks([p_ for p_, d_ in zip(ctx.param_refs, direct) if d_])
+    return tuple(None if d_ else o for o, d_ in zip(outs, direct))
+
+
+def _wn_bwd_defer(ctx, slabs, dshift, work, ns, v, g, bias, gamma, invnorm, late, keep):
+    """Every needed gradient is a view of a flat bucket: hand the layer to the batched weight-norm backward."""
+    _, c1, c2, _, _, cout, _, _ = ctx.dims
+    outs = [p_.grad if (p_ is not None and need) else None for p_, need in zip(ctx.param_refs, ctx.needs_input_grad[3:8])]
+    layer = _WnLayer(*[_ptr_or_none(t) for t in (slabs, dshift, v, g, bias, gamma, invnorm, *outs, work)],
+                     cout, c1, c2, ctx.cfg.k, ctx.cfg.kind, ns)
+    _wn_defer(_Deferred(layer, [p_ for p_, o in zip(ctx.param_refs, outs) if o is not None], keep, late))
+
+
+def _weight_gradients(ctx, wd, x1, x2, dconv, v, g, bias, gamma, invnorm, amax_x, amax_dy, defer):
+    """Weight-gradient launch + weight-norm backward on the current stream -> (dv, dg, dbias, dgamma, dbeta)."""
+    _, c1, c2, _, _, cout, _, _ = ctx.dims
+    ns = _lib.lib().vunet_conv2d_wgrad_nsplit(ctypes.byref(wd))
+    if ns < 1:
+        raise RuntimeError(f"vunet_conv2d_wgrad_nsplit failed with code {ns}")
+    wd.nsplit = ns
+    ktot = ctx.cfg.k * ctx.cfg.k * (c1 + c2)
+    n_slab = ns * _r32(cout) * ktot + ns * _r32(cout)
+    if defer:   # per-layer persistent buffers: the batched reduction reads them after backward has moved on
+        slabs, work = _wn_buffers(n_slab, cout * (ktot + 1), dconv.device)
+    else:
+        slabs = torch.empty(n_slab, device=dconv.device, dtype=torch.float32)
+    dshift = slabs[ns * _r32(cout) * ktot:]
+    late = _wgrad_launch(wd, x1, x2, dconv, slabs, dshift, amax_x, amax_dy, defer)
+    if not defer:
+        return _wn_bwd_now(ctx, slabs, dshift, ns, v, g, bias, gamma, invnorm)
+    keep = (invnorm,) if late is None else (invnorm, x1, x2, dconv, *_amax_pair(amax_x), amax_dy)
+    _wn_bwd_defer(ctx, slabs, dshift, work, ns, v, g, bias, gamma, invnorm, late, keep)
+    return _NO_GRADS
+
+
+def _schedule_wgrad(ctx, x1, x2, dconv, v, g, bias, gamma, invnorm, dy_amax):
+    """Where and when the weight gradients run, decided HERE: on the ``companion`` stream instead of this one, and/or with
+    the weight-norm backward (and a short launch) ``defer``red to the stream's batched flush.  Maxima: before any switch."""
+    n, c1, c2, hs, ws, cout, ho, wo = ctx.dims
+    cfg = ctx.cfg
+    wd = _wgrad_desc(n, c1, c2, hs, ws, cout, ho, wo, cfg.k, cfg.stride, cfg.pad, _scheme(), cfg.in_act, cfg.in_slope,
+                     cfg.drop_p, cfg.drop_seed)
+    amax_x = amax_dy = None
+    if _scheme() == 2 and _wgrad_wants_split(wd):
+        # (the forward may not have needed the |x| maxima -- 1x1 / fp32 kernels -- but the producers' tags are still there)
+        amax_x = ctx.amax_x if ctx.amax_x is not None else _amax_for(x1, x2)
+        amax_dy = dy_amax.get()
+    ni = ctx.needs_input_grad
+    all_direct = all((not ni[3 + i]) or p_ is None or _has_direct_grad(p_) for i, p_ in enumerate(ctx.param_refs))
+    # While a hipGraph is being captured the item tables of the batched backward must already exist (they are uploaded from
+    # host memory on first use): the trainer runs its eager steps on the capture stream first, so that arenas, companion
+    # streams and tables are the captured step's own (_wn_table raises otherwise)
+    defer = (_wn_batch["on"] and ctx.prepacked and all_direct
+             and (_wn_batch["capture"] or not torch.cuda.is_current_stream_capturing()))
+    companion = _wgrad_streams["on"] and all_direct
+    if not companion:
+        return _weight_gradients(ctx, wd, x1, x2, dconv, v, g, bias, gamma, invnorm, amax_x, amax_dy, defer)
+    # weight gradients are off the critical path of backward (only the data gradient feeds the next layer): wgrad + slab
+    # reduce + weight-norm backward run on a companion stream; the results land in the flat gradient buckets, ordered
+    # before the optimiser by ops.join_wgrad_streams()
+    cur = _current_stream_obj()
+    wstream = _wgrad_stream_for(cur)
+    wstream.wait_stream(cur)
+    # tensors the caching allocator may hand out again before the companion stream has read them: the activations and
+    # dy (freed as backward moves on), the maxima if they are not arena slices, invnorm if it is not part of the model's
+    # persistent pack set (the parameters themselves outlive the step)
+    for t_ in (x1, x2, dconv, *_amax_pair(amax_x), amax_dy, None if ctx.prepacked else invnorm):
+        if t_ is not None:
+            t_.record_stream(wstream)
+    torch.cuda.set_stream(wstream)   # (the context-manager form costs 6 us per layer, this pair 0.8)
+    try:
+        _weight_gradients(ctx, wd, x1, x2, dconv, v, g, bias, gamma, invnorm, amax_x, amax_dy, defer)
+    finally:
+        torch.cuda.set_stream(cur)
+    return _NO_GRADS
+
+
+def _dgrad_source(ctx, x, cs, m_off, seed, add, add2, mask_by_x, dconv, wt_d, wx_d, dy_amax):
+    """The data gradient w.r.t. one source (``cs`` channels from ``m_off`` on), ``add`` / ``add2`` added in the epilogue."""
+    n, _, _, hs, ws, cout, ho, wo = ctx.dims
+    cfg = ctx.cfg
+    dx = torch.empty_like(x)
+    has_aux = cfg.in_act != ACT_NONE or cfg.drop_p > 0
+    # x is a ReLU output and this layer has no prologue of its own: the epilogue's act'(aux) slot applies
+    # [x > 0] for the layer below (see _relu_premask)
+    mask_by_x = mask_by_x and not has_aux
+    d = _dgrad_desc(n, cout, ho, wo, cs, hs, ws, cfg.k, cfg.stride, cfg.pad, wt_d.shape[1], m_off,
+                    ACT_RELU if mask_by_x else cfg.in_act, cfg.in_slope, cfg.drop_p, seed)
+    has_aux = has_aux or mask_by_x
+    amax = None
+    if wx_d is not None and _scheme() == 2 and _wants_split(d, has_aux, add is not None):
+        amax = dy_amax.get()
+    _conv_gather(d, dconv, None, wt_d, None, add, x if has_aux else None, dx, wx_d, amax, res2=add2)
+    if mask_by_x:
+        _tag_masked(dx, x)
+    return dx
 
 
 class FusedConv(torch.autograd.Function):
@@ -1019,59 +1312,30 @@ class FusedConv(torch.autograd.Function):
         k = cfg.k
         ho, wo = conv_out_size(hs, k, cfg.stride, cfg.pad), conv_out_size(ws, k, cfg.stride, cfg.pad)
         need_x = (ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]))
-        need_w = any(ctx.needs_input_grad[3:8])
-        frozen = not any(t is not None and t.requires_grad for t in (v, g, bias, gamma, beta))
-        # frozen feature extractor (VGG19): pack once, reuse for every pass.  The packed buffers hang off the weight
-        # tensor itself (they die with it) and are stamped with every operand's storage address and version counter.
-        sub = stamp = hit = pre = None
-        if frozen:
-            sub = (c1, c2, cfg.kind, bool(need_x), _scheme())
-            stamp = tuple(None if t is None else (t.data_ptr(), t._version) for t in (v, g, bias, gamma, beta))
-            hit = getattr(v, "_vunet_frozen_pack", {}).get(sub)
-        if cfg.owner is not None and not frozen:
-            old = cfg.owner.__dict__.get("_last_split")
-            new = (c1, c2, bool(need_x) or (old is not None and old[2]))
-            if new != old:
-                object.__setattr__(cfg.owner, "_last_split", new)   # (nn.Module.__setattr__ costs ~2 us per call)
-            pre = _active_prepack.get(id(cfg.owner))
-            if pre is not None and (pre[0][:2] != (c1, c2) or (need_x and pre[2] is None)):
-                pre = None
-        if pre is not None:
-            _, wt_f, wt_d, scale, shift, invnorm, wx_f, wx_d = pre
-        elif hit is not None and hit[0] == stamp:
-            wt_f, wt_d, scale, shift, invnorm, wx_f, wx_d = hit[1]
-        else:
-            wt_f, wt_d, scale, shift, invnorm, wx_f, wx_d = pack_weights(v, g, bias, gamma, beta, c1, c2, cfg.kind,
-                                                                          need_x)
-            if frozen:
-                if not hasattr(v, "_vunet_frozen_pack"):
-                    v._vunet_frozen_pack = {}
-                v._vunet_frozen_pack[sub] = (stamp, (wt_f, wt_d, scale, shift, invnorm, wx_f, wx_d))
+        # prepacked: invnorm lives in the model's persistent pack set (the batched weight-norm backward keeps raw pointers
+        # to it in a table that is uploaded once)
+        (wt_f, wt_d, scale, shift, invnorm, wx_f, wx_d), ctx.prepacked = _packed_weights(cfg, v, g, bias, gamma, beta, c1, c2,
+                                                                                         need_x)
         if cfg.d2s:
             y = torch.empty(n, cout // 4, 2 * ho, 2 * wo, device=x1.device, dtype=torch.float32)
         else:
             y = torch.empty(n, cout, ho, wo, device=x1.device, dtype=torch.float32)
-        d = ConvDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, M=cout, m_off=0, Mpad=wt_f.shape[1], Ho=ho, Wo=wo, KH=k, KW=k,
-                     stride=cfg.stride, pad=cfg.pad, mode=0, in_act=cfg.in_act, in_slope=cfg.in_slope,
-                     drop_p=cfg.drop_p, drop_seed=cfg.drop_seed, out_act=cfg.out_act, d2s=int(cfg.d2s))
+        d = _fwd_desc(n, c1, c2, hs, ws, cout, ho, wo, k, cfg.stride, cfg.pad, wt_f.shape[1], cfg.in_act, cfg.in_slope,
+                      cfg.drop_p, cfg.drop_seed, cfg.out_act, int(cfg.d2s))
         ctx.amax_x = None
         if cfg.bf16 and _lib.lib().vunet_conv2d_bf16_supported(ctypes.byref(d)) == 1:
             # render path (models/vunets.py:508-515 under no_grad): bf16 operands, fp32 accumulate
             wb = torch.empty((c1 + c2) * 9 * wt_f.shape[1], device=x1.device, dtype=torch.bfloat16)
             _call("vunet_pack_bf16", _p(wt_f), _p(wb), c1, c2, wt_f.shape[1], _stream())
-            with (_Timed(("conv_bf16_fwd", n, c1, c2, hs, ws, cout, k, cfg.stride, cfg.in_act, "conv_bf16_kernel"),
-                        2.0 * n * ho * wo * cout * (c1 + c2) * k * k) if _prof["on"] else _NO_TIMER):
+            with _timed(_bf16_key, d):
                 _call("vunet_conv2d_bf16", ctypes.byref(d), _p(x1), _p(x2), _p(wb), _p(shift), _p(res), _p(y), _stream())
         else:
             ctx.amax_x = _conv_gather(d, x1, x2, wt_f, shift, res, None, y, wx_f)   # reused by the weight gradient
         ctx.cfg = cfg
-        # packed by ops.prepacked: invnorm lives in the model's persistent pack set (the batched weight-norm backward keeps
-        # raw pointers to it in a table that is uploaded once)
-        ctx.prepacked = pre is not None
         ctx.param_refs = (v, g, bias, gamma, beta)  # the caller's tensors (Parameters): direct .grad writes
         ctx.res_ref = res
         ctx.dims = (n, c1, c2, hs, ws, cout, ho, wo)
-        ctx.need_w = need_w
+        ctx.need_w = any(ctx.needs_input_grad[3:8])
         ctx.save_for_backward(x1, x2, v, g, bias, gamma, invnorm, wt_d,
                               y if cfg.out_act in (ACT_SIGMOID, ACT_RELU, ACT_LRELU, ACT_ELU) else None, wx_d)
         if cfg.out_act == ACT_RELU:
@@ -1094,216 +1358,30 @@ class FusedConv(torch.autograd.Function):
         if g_alias is not None:
             g_alias = _c(g_alias)
         if torch.is_grad_enabled():
-            # create_graph=True (e.g. the R1 penalty): build a differentiable backward by re-expressing the layer
-            # with primitives that autograd can differentiate again, and differentiating that expression
-            res, beta = ctx.res_ref, ctx.param_refs[4]
-            with torch.enable_grad():
-                y2 = _differentiable_layer(x1, x2, res, v, g, bias, gamma, beta, cfg)
-            needs = list(ctx.needs_input_grad[:8])
-            if cfg.res_is_x1:
-                needs[2] = False   # the residual IS source 1: its gradient is already part of d/dx1
-            tensors = (x1, x2, res, v, g, bias, gamma, beta)
-            wanted = [t for t, need in zip(tensors, needs) if need and t is not None]
-            grads = iter(torch.autograd.grad(y2, wanted, dy, create_graph=True, allow_unused=True))
-            out = [next(grads) if (need and t is not None) else None for t, need in zip(tensors, needs)]
-            if g_alias is not None:
-                out[0] = g_alias if out[0] is None else out[0] + g_alias
-            return (*out, None)
-        n, c1, c2, hs, ws, cout, ho, wo = ctx.dims
+            return _double_backward(ctx, x1, x2, v, g, bias, gamma, dy, g_alias)
+        ni = ctx.needs_input_grad
+        _, c1, c2, _, _, _, _, _ = ctx.dims
         dy = _c(dy)
-        dres = dy if (ctx.needs_input_grad[2] and not cfg.res_is_x1) else None
-        k = cfg.k
-        # frozen ReLU layers (the VGG19 stack): the ReLU backward rides in the data-gradient kernel's staging
+        dres = dy if (ni[2] and not cfg.res_is_x1) else None
         premasked = cfg.out_act == ACT_RELU and _is_masked_by(dy, y)   # the producer of dy already applied [y > 0]
-        if (cfg.out_act == ACT_RELU and not premasked and not ctx.need_w and not cfg.d2s and x2 is None
-                and ctx.needs_input_grad[0] and cfg.in_act == ACT_NONE and cfg.drop_p == 0 and wt_d is not None):
-            dx = torch.empty_like(x1)
-            d = ConvDesc(N=n, C1=cout, C2=0, Hs=ho, Ws=wo, M=c1, m_off=0, Mpad=wt_d.shape[1], Ho=hs, Wo=ws, KH=k, KW=k,
-                         stride=cfg.stride, pad=cfg.pad, mode=1, in_act=ACT_NONE, in_slope=0.0, drop_p=0.0, drop_seed=0,
-                         out_act=ACT_NONE, d2s=0)
-            kname = ""
-            if _prof["on"]:
-                buf = ctypes.create_string_buffer(96)
-                _call("vunet_conv2d_variant", ctypes.byref(d), 0, 0 if wx_d is None else _scheme(), 1, buf, 96)
-                kname = buf.value.decode()
-                if kname.startswith("conv_tiled"):
-                    kname = kname.replace(", 1, 0, ", ", 1, 4, ")
-            with (_Timed(("conv_gather_dgrad", n, cout, 0, ho, wo, c1, k, cfg.stride, 0, kname),
-                        2.0 * n * ho * wo * cout * c1 * k * k) if _prof["on"] else _NO_TIMER):
-                rc = -3
-                if wx_d is not None and _wants_split(d, False, cfg.res_is_x1, True):
-                    amax = _amax_for(dy) if _scheme() == 2 else None
-                    amax_out = _new_amax_out(dx.device) if _scheme() == 2 else None
-                    rc = _lib.lib().vunet_conv2d_dgrad_relu_x6(ctypes.byref(d), _p(dy), _p(y), _p(wx_d),
-                                                               _p(dy if cfg.res_is_x1 else g_alias), _p(dx), _p(amax),
-                                                               _p(amax_out), _stream())
-                    if rc == 0 and amax_out is not None:
-                        _tag_amax(dx, amax_out)
-                if rc == -3:
-                    rc = _lib.lib().vunet_conv2d_dgrad_relu(ctypes.byref(d), _p(dy), _p(y), _p(wt_d),
-                                                            _p(dy if cfg.res_is_x1 else g_alias), _p(dx), _stream())
-            if rc == 0:
-                if cfg.res_is_x1 and g_alias is not None:
-                    dx.add_(g_alias)
-                return dx, None, dres, None, None, None, None, None, None
-            if rc != -3:   # anything but VUNET_ERR_UNSUPPORTED is an error; unsupported geometries take the two-pass route
-                raise RuntimeError(f"vunet_conv2d_dgrad_relu failed with code {rc}")
-            if _prof["on"] and _prof["recs"]:
-                _prof["recs"].pop()
-        dconv = dy
-        if cfg.out_act != ACT_NONE and not premasked:
-            dconv = torch.empty_like(dy)
-            _call("vunet_act_bwd_from_out", _p(y), _p(dy), _p(dconv), cfg.out_act, cfg.in_slope, dy.numel(), _stream())
-        if cfg.d2s:
-            t = torch.empty(n, cout, ho, wo, device=dy.device, dtype=torch.float32)
-            _call("vunet_space_to_depth", _p(dconv), _p(t), n, cout // 4, 2 * ho, 2 * wo, _stream())
-            carry_amax_tag(dconv, t)   # a permutation: the same values, the same maxima
-            dconv = t
-        dv = dg = dbias = dgamma = dbeta = None
-        dy_amax = []   # |dconv| maxima of the h2 scheme: computed once (on this stream), shared by dgrad and wgrad
-
-        def get_dy_amax():
-            if not dy_amax:
-                dy_amax.append(_amax_for(dconv))
-            return dy_amax[0]
-
-        wd = WgradDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, Cout=cout, Ho=ho, Wo=wo, KH=k, KW=k, stride=cfg.stride,
-                       pad=cfg.pad, in_act=cfg.in_act, in_slope=cfg.in_slope, drop_p=cfg.drop_p,
-                       drop_seed=cfg.drop_seed, nsplit=1, flags=(0, 0, 2)[_scheme()] if _scheme() else 1)
-        wg_amax = (None, None)
-        if ctx.need_w and _scheme() == 2 and _wgrad_wants_split(wd):
-            # (the forward may not have needed the |x| maxima -- 1x1 / fp32 kernels -- but the producers' tags are still there)
-            wg_amax = (ctx.amax_x if ctx.amax_x is not None else _amax_for(x1, x2), get_dy_amax())
-
-        def weight_gradients(defer: bool = False):
-            ns = _lib.lib().vunet_conv2d_wgrad_nsplit(ctypes.byref(wd))
-            if ns < 1:
-                raise RuntimeError(f"vunet_conv2d_wgrad_nsplit failed with code {ns}")
-            wd.nsplit = ns
-            ktot = k * k * (c1 + c2)
-            n_slab = ns * _r32(cout) * ktot + ns * _r32(cout)
-            if defer:   # per-layer persistent buffers: the batched reduction reads them after backward has moved on
-                slabs, work = _wn_buffers(n_slab, cout * (ktot + 1), dy.device)
-            else:
-                slabs = torch.empty(n_slab, device=dy.device, dtype=torch.float32)
-            dshift = slabs[ns * _r32(cout) * ktot:]
-            kname = ""
-            if _prof["on"]:
-                buf = ctypes.create_string_buffer(96)
-                _call("vunet_conv2d_wgrad_variant", ctypes.byref(wd), buf, 96)
-                kname = buf.value.decode()
-            ax1, ax2 = _amax_pair(wg_amax[0])
-            # short launches (small maps, 1x1, the small stride-2 layers): the launch itself waits for the flush, where the
-            # layers of one kernel form share a launch (vunet_conv2d_wgrad_multi); per-launch timing runs keep them apart
-            late = (defer and _wn_batch["wgrad"] and not _prof["on"]
-                    and _wgrad_batchable(wd))
-            if not late:
-                with (_Timed(("conv_wgrad", n, c1, c2, hs, ws, cout, k, cfg.stride, cfg.in_act, kname),
-                            2.0 * n * ho * wo * cout * (c1 + c2) * k * k) if _prof["on"] else _NO_TIMER):
-                    _call("vunet_conv2d_wgrad_a2", ctypes.byref(wd), _p(x1), _p(x2), _p(dconv), _p(slabs), _p(dshift),
-                          _p(ax1), _p(ax2), _p(wg_amax[1]), _stream())
-            ni = ctx.needs_input_grad
-            if defer:   # every needed gradient is a view of a flat bucket: hand the layer to the batched backward
-                outs = [p_.grad if (p_ is not None and need) else None for p_, need in zip(ctx.param_refs, ni[3:8])]
-                ptrs = tuple(None if t is None else t.data_ptr() for t in
-                             (slabs, dshift, v, g, bias, gamma, invnorm, outs[0], outs[1], outs[2], outs[3], outs[4], work))
-                wg_item, keep = None, (invnorm,)
-                if late:
-                    wg_item = (bytes(wd), tuple(None if t is None else t.data_ptr() for t in
-                                                (x1, x2, dconv, slabs, dshift, ax1, ax2, wg_amax[1])))
-                    keep = (invnorm, x1, x2, dconv, ax1, ax2, wg_amax[1])
-                _wn_defer(ptrs + ((cout, c1, c2, k, k, cfg.kind), ns),
-                          [p_ for p_, o in zip(ctx.param_refs, outs) if o is not None], keep, wg_item)
-                return None, None, None, None, None
-            params = (v, g, bias, gamma, gamma)  # beta has gamma's shape
-            outs, direct = [], []
-            for idx, (p_, need) in enumerate(zip(ctx.param_refs, ni[3:8])):
-                if p_ is None or not need:
-                    outs.append(None)
-                    direct.append(False)
-                elif _has_direct_grad(p_):
-                    outs.append(p_.grad)      # written in place (+=) by the kernel: no autograd accumulation pass
-                    direct.append(True)
-                else:
-                    outs.append(torch.empty_like(params[idx]))
-                    direct.append(False)
-            n_direct = sum(direct)
-            n_needed = sum(o is not None for o in outs)
-            wn = WnDesc(cout, c1, c2, k, k, cfg.kind, 0)
-            work = torch.empty(cout * (ktot + 1), device=dy.device, dtype=torch.float32)
-
-            def run(sel_direct: bool):
-                sel = [o if (o is not None and d_ == sel_direct) else None for o, d_ in zip(outs, direct)]
-                _call("vunet_weightnorm_bwd", ctypes.byref(wn), _p(slabs), _p(dshift), ns, _p(v), _p(g), _p(bias),
-                      _p(gamma), _p(invnorm), _p(sel[0]), _p(sel[1]), _p(sel[2]), _p(sel[3]), _p(sel[4]), _p(work),
-                      1 if sel_direct else 0, _stream())
-            if n_direct:
-                run(True)
-            if n_needed > n_direct:
-                run(False)
-            dv, dg, dbias, dgamma, dbeta = [None if d_ else o for o, d_ in zip(outs, direct)]
-            for p_, d_ in zip(ctx.param_refs, direct):
-                if d_:
-                    for hook in _grad_hooks:
-                        hook(p_)
-            return dv, dg, dbias, dgamma, dbeta
-
-        if ctx.need_w:
-            ni_ = ctx.needs_input_grad
-            all_direct = all((not ni_[3 + i]) or p_ is None or _has_direct_grad(p_) for i, p_ in enumerate(ctx.param_refs))
-            # batched weight-norm backward.  While a hipGraph is being captured its item tables must already exist (they are
-            # uploaded from host memory on first use): the trainer runs its eager steps on the capture stream first, so
-            # that arenas, companion streams and tables are the captured step's own (_wn_flush_stream raises otherwise)
-            defer_ok = (_wn_batch["on"] and ctx.prepacked and all_direct and dy.is_cuda
-                        and (_wn_batch["capture"] or not torch.cuda.is_current_stream_capturing()))
-            if _wgrad_streams["on"] and all_direct and dy.is_cuda:
-                # weight gradients are off the critical path of backward (only the data gradient feeds the next
-                # layer): run wgrad + slab reduce + weight-norm backward on a companion stream; the results land in
-                # the flat gradient buckets, ordered before the optimiser by ops.join_wgrad_streams()
-                cur = _current_stream_obj()
-                wstream = _wgrad_stream_for(cur)
-                wstream.wait_stream(cur)
-                # tensors the caching allocator may hand out again before the companion stream has read them: the
-                # activations and dy (freed as backward moves on), the |x| maxima if they are not arena slices, invnorm if
-                # it is not part of the model's persistent pack set (the parameters themselves outlive the step)
-                for t_ in (x1, x2, dconv, *_amax_pair(wg_amax[0]), wg_amax[1], None if ctx.prepacked else invnorm):
-                    if t_ is not None:
-                        t_.record_stream(wstream)
-                torch.cuda.set_stream(wstream)   # (the context-manager form costs 6 us per layer, this pair 0.8)
-                try:
-                    weight_gradients(defer_ok)
-                finally:
-                    torch.cuda.set_stream(cur)
-            else:
-                dv, dg, dbias, dgamma, dbeta = weight_gradients(defer_ok)
+        if (cfg.out_act == ACT_RELU and not premasked and not ctx.need_w and not cfg.d2s and x2 is None and ni[0]
+                and cfg.in_act == ACT_NONE and cfg.drop_p == 0 and wt_d is not None):
+            dx1 = _relu_dgrad(ctx, x1, y, wt_d, wx_d, dy, g_alias)
+            if dx1 is not None:
+                return dx1, None, dres, None, None, None, None, None, None
+        dconv = _out_act_bwd(ctx, y, dy, premasked)
+        dy_amax = _LazyAmax(dconv)   # shared by the weight gradient and both data gradients
+        dv, dg, dbias, dgamma, dbeta = (_schedule_wgrad(ctx, x1, x2, dconv, v, g, bias, gamma, invnorm, dy_amax)
+                                        if ctx.need_w else _NO_GRADS)
         dx1 = dx2 = None
-        if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):
-            def dgrad(x, cs, m_off, seed, add, mask_by_x=False, add2=None):
-                dx = torch.empty_like(x)
-                has_aux = cfg.in_act != ACT_NONE or cfg.drop_p > 0
-                # x is a ReLU output and this layer has no prologue of its own: the epilogue's act'(aux) slot applies
-                # [x > 0] for the layer below (see _relu_premask)
-                mask_by_x = mask_by_x and not has_aux
-                d = ConvDesc(N=n, C1=cout, C2=0, Hs=ho, Ws=wo, M=cs, m_off=m_off, Mpad=wt_d.shape[1], Ho=hs, Wo=ws,
-                             KH=k, KW=k, stride=cfg.stride, pad=cfg.pad, mode=1, in_act=ACT_NONE, in_slope=0.0,
-                             drop_p=0.0, drop_seed=0, out_act=ACT_NONE, d2s=0,
-                             aux_act=ACT_RELU if mask_by_x else cfg.in_act,
-                             aux_slope=cfg.in_slope, aux_drop_p=cfg.drop_p, aux_drop_seed=seed)
-                has_aux = has_aux or mask_by_x
-                amax = None
-                if wx_d is not None and _scheme() == 2 and _wants_split(d, has_aux, add is not None):
-                    amax = get_dy_amax()
-                _conv_gather(d, dconv, None, wt_d, None, add, x if has_aux else None, dx, wx_d, amax, res2=add2)
-                if mask_by_x:
-                    _tag_masked(dx, x)
-                return dx
-            if ctx.needs_input_grad[0]:
-                # (x is the residual AND has another reader: dy in the epilogue's first slot, that reader's gradient in its second)
-                dx1 = dgrad(x1, c1, 0, cfg.drop_seed, dy if cfg.res_is_x1 else g_alias, ctx.x1_relu_out,
-                            add2=g_alias if cfg.res_is_x1 else None)
-                g_alias = None
-            if x2 is not None and ctx.needs_input_grad[1]:
-                dx2 = dgrad(x2, c2, c1, (cfg.drop_seed + SEED2_OFFSET) & 0xFFFFFFFF, None)
+        if ni[0]:
+            # (x is the residual AND has another reader: dy in the epilogue's first slot, that reader's gradient in its second)
+            dx1 = _dgrad_source(ctx, x1, c1, 0, cfg.drop_seed, dy if cfg.res_is_x1 else g_alias,
+                                g_alias if cfg.res_is_x1 else None, ctx.x1_relu_out, dconv, wt_d, wx_d, dy_amax)
+            g_alias = None
+        if x2 is not None and ni[1]:
+            dx2 = _dgrad_source(ctx, x2, c2, c1, (cfg.drop_seed + SEED2_OFFSET) & 0xFFFFFFFF, None, None, False, dconv, wt_d,
+                                wx_d, dy_amax)
         if g_alias is not None:   # x1 itself needed no gradient from this layer
             dx1 = g_alias
         return dx1, dx2, dres, dv, dg, dbias, dgamma, dbeta, None
@@ -1928,6 +2006,11 @@ def p2_conv_supported(n, c, h, w, m) -> bool:
     return _lib.lib().vunet_p2_conv_supported(ctypes.byref(d)) == 1
 
 
+def _p2_key(d, dgrad):
+    return (("conv_gather_dgrad" if dgrad else "conv_gather_fwd", d.N, d.C, 0, d.H, d.W, d.M, 3, 1, 0,
+             _kernel_name("vunet_p2_conv_variant", ctypes.byref(d))), 2.0 * d.N * d.H * d.W * d.C * d.M * 9)
+
+
 def p2_conv(x: Planes, wts: P2Weights, out: Planes, relu: bool = True, dgrad: bool = False, mask: Planes = None):
     """out = relu(conv(x) + bias) (forward) or conv^T(x) [* (mask != 0)] (data gradient).  ``out.meta``'s maximum slots
     must be zero (the caller zeroes the metas of a pass in one fill)."""
@@ -1936,13 +2019,7 @@ def p2_conv(x: Planes, wts: P2Weights, out: Planes, relu: bool = True, dgrad: bo
     assert c == (wts.cout if dgrad else wts.cin) and out.shape == (n, m, h, w)
     img, wk = wts.image(dgrad)
     d = P2Desc(n, c, h, w, m, int(relu and not dgrad))
-    timer = _NO_TIMER
-    if _prof["on"]:
-        buf = ctypes.create_string_buffer(96)
-        _call("vunet_p2_conv_variant", ctypes.byref(d), buf, 96)
-        timer = _Timed(("conv_gather_dgrad" if dgrad else "conv_gather_fwd", n, c, 0, h, w, m, 3, 1, 0, buf.value.decode()),
-                       2.0 * n * h * w * c * m * 9)
-    with timer:
+    with _timed(_p2_key, d, dgrad):
         _call("vunet_p2_conv", ctypes.byref(d), _p(x.buf), _p(x.meta), _p(img), _p(wk),
               _p(None if dgrad or wts.bias is None else wts.bias), _p(None if mask is None else mask.buf), _p(out.buf), _p(out.meta),
               _stream())

@@ -21,7 +21,13 @@ import torch
 
 from . import _lib, ops
 from .lib.modules import NormConv2d, _act_code
-from .ops import ACT_ELU, ACT_NONE, ConvDesc, _call, _p, _stream, conv_out_size
+from .ops import ACT_ELU, ACT_NONE, _call, _p, _stream, conv_out_size
+
+
+def _blk_key(d, has_res, out_nchw, kname, macs):
+    """Profiler key + FLOPs of a blocked-bf16 launch (``macs``: multiply-adds per output element)."""
+    return (("conv_blk_fwd", d.N, d.C1, d.C2, d.Hs, d.Ws, d.M, d.KH, d.stride, has_res, out_nchw, kname),
+            2.0 * d.N * d.Ho * d.Wo * d.M * macs)
 
 
 class _Packed:
@@ -120,13 +126,10 @@ class BlockedTransfer:
             y = blk_empty(n, L.cout // 4, 2 * ho, 2 * wo, x1.device)
         else:
             y = blk_empty(n, L.cout, ho, wo, x1.device)
-        d = ConvDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, M=L.cout, m_off=0, Mpad=L.mpad, Ho=ho, Wo=wo, KH=L.k, KW=L.k,
-                     stride=L.stride, pad=L.pad, mode=0, in_act=in_act, in_slope=0.0, drop_p=0.0, drop_seed=0,
-                     out_act=ACT_NONE, d2s=int(d2s))
+        d = ops._fwd_desc(n, c1, c2, hs, ws, L.cout, ho, wo, L.k, L.stride, L.pad, L.mpad, in_act, d2s=int(d2s))
         tiled = _lib.lib().vunet_conv2d_blk_tiled(ctypes.byref(d)) == 1
-        with (ops._Timed(("conv_blk_fwd", n, c1, c2, hs, ws, L.cout, L.k, L.stride, int(res is not None), int(out_nchw),
-                          "conv_blk_tiled_kernel" if tiled else "conv_blk_direct_kernel"),
-                         2.0 * n * ho * wo * L.cout * (c1 + c2) * L.k * L.k) if ops._prof["on"] else ops._NO_TIMER):
+        with ops._timed(_blk_key, d, int(res is not None), int(out_nchw),
+                        "conv_blk_tiled_kernel" if tiled else "conv_blk_direct_kernel", (c1 + c2) * L.k * L.k):
             _call("vunet_conv2d_blk", ctypes.byref(d), _p(x1), _p(x2), _p(L.wb), _p(L.shift), _p(res), _p(y),
                   int(out_nchw), _stream())
         return y
@@ -148,14 +151,11 @@ class BlockedTransfer:
         n, c8, hs, ws, _ = x.shape
         c = c8 * 8
         L, Ln = self._pack(blk.conv, c, c), self._pack(blk.nin, c)
-        d = ConvDesc(N=n, C1=c, C2=c, Hs=hs, Ws=ws, M=L.cout, m_off=0, Mpad=L.mpad, Ho=hs, Wo=ws, KH=L.k, KW=L.k,
-                     stride=L.stride, pad=L.pad, mode=0, in_act=ACT_ELU, in_slope=0.0, drop_p=0.0, drop_seed=0,
-                     out_act=ACT_NONE, d2s=0)
+        d = ops._fwd_desc(n, c, c, hs, ws, L.cout, hs, ws, L.k, L.stride, L.pad, L.mpad, ACT_ELU)
         if Ln.k != 1 or Ln.cout != c or _lib.lib().vunet_conv2d_blk_rnb_supported(ctypes.byref(d)) != 1:
             return None
         y = blk_empty(n, L.cout, hs, ws, x.device)
-        with (ops._Timed(("conv_blk_fwd", n, c, c, hs, ws, L.cout, L.k, L.stride, 1, 0, "conv_blk_rnb_kernel"),
-                         2.0 * n * hs * ws * L.cout * (2 * c * 9 + c)) if ops._prof["on"] else ops._NO_TIMER):
+        with ops._timed(_blk_key, d, 1, 0, "conv_blk_rnb_kernel", 2 * c * 9 + c):
             _call("vunet_conv2d_blk_rnb", ctypes.byref(d), _p(x), _p(a), _p(Ln.wb), _p(Ln.shift), Ln.mpad, _p(L.wb), _p(L.shift),
                   _p(x), _p(y), _stream())
         return y
