@@ -26,7 +26,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from .. import ops
+from .. import inplane, ops
 from ..lib.losses import compute_kl_with_prior, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
 from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, p2_precision, vgg19
@@ -74,6 +74,14 @@ class ShapePoseNet:
         self.vunet = VunetAlter(init_fn=init_fn, n_channels_x=n_channels_x, **kw).to(self.device)
         overlap = self.device.type == "cuda" and bool(tr.get("two_streams", os.environ.get("VUNET_TWO_STREAMS", "1") != "0"))
         self.vunet.enable_two_streams(overlap)   # pose encoder (du) beside appearance encoder (eu, ed)
+        # a multi-part appearance input the batch does not carry is cut out of ``pose_img`` on the GPU (inplane.part_crops) from
+        # ``batch["inplane_keypoints"]``: the part model of ``data`` (``inplane_parts`` or the dataset's), its tables uploaded now
+        self.inplane_parts = inplane.configured_parts(data) if n_channels_x > 3 else None
+        if self.inplane_parts is not None:
+            if n_channels_x != 3 * self.inplane_parts.n_parts:
+                raise ValueError(f"{self.inplane_parts!r} makes {3 * self.inplane_parts.n_parts} channels, the model takes {n_channels_x}")
+            if self.device.type == "cuda":
+                self.inplane_parts.tables(self.device)
         ops.enable_wgrad_streams(overlap)        # weight gradients beside the data-gradient chain (process-wide switch)
         self.vgg = vgg19(pretrained=True, weights_path=vgg_weights_path, width_div=vgg_width_div, seed=vgg_seed,
                          synthetic=vgg_synthetic).to(self.device)
@@ -377,6 +385,9 @@ class ShapePoseNet:
         target_img = batch["pose_img"]
         shape_img = batch["stickman"]
         pose_img = batch.get("pose_img_inplane", target_img)
+        crops = self._inplane_crops(batch)   # (inside a captured step the keypoints are one more static input)
+        if crops is not None:
+            pose_img = crops
         # (inside a hipGraph capture too: ``wait_stream`` on a capturing stream forks the target stream into the capture, the
         # wait on it below joins it back -- the recorded graph keeps the branch)
         tstream = self._target_stream if (target_features is None and self._target_overlap and target_img.is_cuda
@@ -444,6 +455,12 @@ class ShapePoseNet:
         out.update({k: packed[i].view(t.shape) for i, (k, t) in enumerate(zip(names, terms))})
         return out
 
+    def _inplane_crops(self, batch):
+        """``pose_img_inplane`` built on the GPU where ``inplane_normalize`` is set and the batch brings ``inplane_keypoints`` instead
+        of the crops (None otherwise): ten part warps of ``spatial_size // 2**box_factor`` pixels a side."""
+        data = self.config["data"]
+        return inplane.batch_crops(batch, self.inplane_parts, data["spatial_size"] // 2 ** data["box_factor"], data["spatial_size"])
+
     def _regressor_steps(self, batch, reg_eps=None):
         """:407-425.  The reference runs ``ed(eu(reg_imgs[:, i]))`` inside the loop; the encoder is frozen there
         (``no_grad``, no VUnet update until the outer step), so the ``reg_steps`` encoder passes do not depend on the
@@ -502,9 +519,15 @@ class ShapePoseNet:
         return run_probe(regressor, encode, batches, n_epochs, lr, eps)
 
     @torch.no_grad()
-    def transfer(self, app_img, stickman, dtype: str = "f32"):
-        """Inference path used by the render loop (models/vunets.py:508-515); ``dtype="bf16"``: BASELINE config 5."""
+    def transfer(self, app_img, stickman, dtype: str = "f32", app_keypoints=None):
+        """Inference path used by the render loop (models/vunets.py:508-515); ``dtype="bf16"``: BASELINE config 5.
+        ``app_keypoints`` [N, J, 2]: with an in-plane model, ``app_img`` is the 3-channel image those keypoints belong to and
+        the part crops are cut from it here (inplane.part_crops); an ``app_img`` that already holds the crops needs none."""
         self.vunet.eval()
+        if app_keypoints is not None and self.inplane_parts is not None and app_img.shape[1] == 3:
+            data = self.config["data"]
+            app_img = inplane.part_crops(app_img, app_keypoints, self.inplane_parts, data["spatial_size"] // 2 ** data["box_factor"],
+                                         data["spatial_size"])
         with ops.inference_precision(dtype):
             return self.vunet.transfer(app_img, stickman)
 

@@ -15,7 +15,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from .. import ops
+from .. import inplane, ops
 from ..lib.losses import compute_kl_loss, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
 from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, vgg19
@@ -52,6 +52,10 @@ class Vunet:
         self.vunet = VunetOrg(n_channels_x=n_channels_x, **kw).to(self.device)
         overlap = self.device.type == "cuda" and os.environ.get("VUNET_TWO_STREAMS", "1") != "0"
         self.vunet.enable_two_streams(overlap)   # pose encoder (du) on a second HIP stream beside eu / ed
+        # as ShapePoseNet: the crops a batch does not carry are cut from ``pose_img`` and ``batch["inplane_keypoints"]`` on the GPU
+        self.inplane_parts = inplane.configured_parts(data) if n_channels_x > 3 else None
+        if self.inplane_parts is not None and n_channels_x != 3 * self.inplane_parts.n_parts:
+            raise ValueError(f"{self.inplane_parts!r} makes {3 * self.inplane_parts.n_parts} channels, the model takes {n_channels_x}")
         ops.enable_wgrad_streams(overlap)
         self.vgg = vgg19(pretrained=True, weights_path=vgg_weights_path, width_div=vgg_width_div, seed=vgg_seed,
                          synthetic=vgg_synthetic).to(self.device)
@@ -90,6 +94,10 @@ class Vunet:
         self.averager.start_step()
         self.optimizer.zero_grad()
         app_img = batch.get("pose_img_inplane", batch["pose_img"])
+        data = self.config["data"]
+        crops = inplane.batch_crops(batch, self.inplane_parts, data["spatial_size"] // 2 ** data["box_factor"], data["spatial_size"])
+        if crops is not None:
+            app_img = crops
         target_img, shape_img = batch["pose_img"], batch["stickman"]
         out_img, q_means, p_means, _ = self.vunet(app_img, shape_img, eps, prior_eps)
         ld = vgg_loss(self.custom_vgg, target_img, out_img)

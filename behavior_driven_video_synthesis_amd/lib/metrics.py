@@ -55,9 +55,22 @@ def psnr(rec: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> to
     return 10.0 * torch.log10(data_range * data_range / mse)
 
 
+def _inplane_app(model, batch, inplane_parts):
+    """The appearance input of an ``inplane_normalize`` model: ``batch["pose_img_inplane"]`` where the batch carries it, else the
+    part crops cut on the GPU from ``batch["pose_img"]`` and ``batch["inplane_keypoints"]`` with ``inplane_parts`` (a
+    ``inplane.PartModel``, a dataset name or a part list), at the size the model's appearance encoder takes."""
+    if "pose_img_inplane" in batch or "inplane_keypoints" not in batch:
+        return batch["pose_img_inplane"]
+    from .. import inplane
+    if inplane_parts is None:
+        raise ValueError("inplane_keypoints without pose_img_inplane: pass inplane_parts (inplane.MARKET_PARTS, ...) to cut the crops")
+    s_out = model.spatial_size // 2 ** (model.n_scales - model.n_scales_x)
+    return inplane.part_crops(batch["pose_img"], batch["inplane_keypoints"], inplane_parts, s_out, model.spatial_size)
+
+
 @torch.no_grad()
 def compute_ssim(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor]], max_n_samples: int = 8000,
-                 inplane_normalize: bool = False) -> float:
+                 inplane_normalize: bool = False, inplane_parts=None) -> float:
     """lib/metrics.py:22-116 on an iterable of batches: reconstruct (``model(app, stickman)[0]``), scale both images
     to [0, 1] (:86-92) and average the per-image SSIM over at most ``max_n_samples`` samples."""
     was_training = model.training
@@ -68,7 +81,7 @@ def compute_ssim(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tenso
         if "app_img" in batch and type(model).__name__ == "VunetOrg":   # :71-74
             app = batch["app_img"]
         else:
-            app = batch["pose_img_inplane"] if inplane_normalize else target
+            app = _inplane_app(model, batch, inplane_parts) if inplane_normalize else target
         rec = model(app, batch["stickman"])[0]
         vals = ssim(utils.scale_img(rec), utils.scale_img(target))
         take = min(vals.numel(), max_n_samples - count)
@@ -115,7 +128,7 @@ def fid_from_features(gt_features: np.ndarray, gen_features: np.ndarray) -> floa
 @torch.no_grad()
 def compute_fid(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor]], feature_extractor: Callable,
                 gt_features: Optional[np.ndarray] = None, max_n_samples: int = 8000,
-                inplane_normalize: bool = False) -> float:
+                inplane_normalize: bool = False, inplane_parts=None) -> float:
     """lib/metrics.py:119-282 on an iterable of batches.  ``feature_extractor(images) -> [N, D]`` stands for the
     reference's ``FIDInceptionModel`` (user-supplied pretrained Inception-v3 pool features); ground-truth features are
     computed from ``batch["pose_img"]`` unless ``gt_features`` (the reference's cached ``<dataset>-fid-features.npy``) is
@@ -128,7 +141,7 @@ def compute_fid(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor
         if "app_img" in batch and type(model).__name__ == "VunetOrg":
             app = batch["app_img"]
         else:
-            app = batch["pose_img_inplane"] if inplane_normalize else target
+            app = _inplane_app(model, batch, inplane_parts) if inplane_normalize else target
         if gt_features is None:
             gts.append(feature_extractor(target).detach().double().cpu().numpy())
         gens.append(feature_extractor(model(app, batch["stickman"])[0]).detach().double().cpu().numpy())
