@@ -26,7 +26,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from .. import inplane, ops
+from .. import image_input, inplane, ops
 from ..lib.losses import compute_kl_with_prior, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
 from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, p2_precision, vgg19
@@ -335,10 +335,13 @@ class ShapePoseNet:
         self.iteration += 1
         it = self.iteration
         self.averager.start_step()
+        # raw frames (``pose_img_u8`` + ``pose_img_geom`` instead of ``pose_img``): on the device from here on -- the step makes the
+        # image itself (image_input.batch_images), and a recorded step takes them as static inputs.  Other batches: untouched.
+        batch = image_input.to_device(batch, self.device)
         if self.gan is not None:
             # one (patch x patch) window per step, the same for the real and the generated batch: drawn on the host, handed
             # to the step through device memory (ops.CropWindow), so that the step's launch arguments never change
-            P, S = self.gan_patch, batch["pose_img"].shape[-1]
+            P, S = self.gan_patch, batch["pose_img"].shape[-1] if "pose_img" in batch else self.config["data"]["spatial_size"]
             off = torch.randint(0, S - P + 1, (2,), generator=self._gan_rng).to(torch.int32)
             self._gan_off.copy_(off, non_blocking=True)
         with ops.kernel_noise():   # posterior noise from the sampling kernels themselves (ops.kernel_noise)
@@ -355,6 +358,9 @@ class ShapePoseNet:
             ops.reset_dropout_counter()
             ops.set_dropout_host_step(it & 0x7FFFFFFF)
             self.optimizer.zero_grad()
+            made = image_input.batch_images(batch, self.config["data"]["spatial_size"])   # (the target pass below reads pose_img)
+            if made:
+                batch = {**batch, **made}
             target_features = None
             side = self.vunet._side_stream
             if side is not None and self.device.type == "cuda" and self._pack_overlap:
@@ -382,6 +388,10 @@ class ShapePoseNet:
 
     def _step(self, batch, it, eps, reg_eps=None, target_features=None):
         tr = self.config["training"]
+        # ``pose_img`` from raw frames where the batch brings ``pose_img_u8`` instead (three launches, recorded with the step)
+        made = image_input.batch_images(batch, self.config["data"]["spatial_size"])
+        if made:
+            batch = {**batch, **made}
         target_img = batch["pose_img"]
         shape_img = batch["stickman"]
         pose_img = batch.get("pose_img_inplane", target_img)

@@ -15,7 +15,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from .. import inplane, ops
+from .. import image_input, inplane, ops
 from ..lib.losses import compute_kl_loss, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
 from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, vgg19
@@ -93,8 +93,11 @@ class Vunet:
         self.iteration += 1
         self.averager.start_step()
         self.optimizer.zero_grad()
-        app_img = batch.get("pose_img_inplane", batch["pose_img"])
         data = self.config["data"]
+        made = image_input.batch_images(batch, data["spatial_size"])   # ``pose_img`` from ``pose_img_u8`` (+ ``pose_img_geom``)
+        if made:
+            batch = {**batch, **made}
+        app_img = batch.get("pose_img_inplane", batch["pose_img"])
         crops = inplane.batch_crops(batch, self.inplane_parts, data["spatial_size"] // 2 ** data["box_factor"], data["spatial_size"])
         if crops is not None:
             app_img = crops

@@ -55,6 +55,16 @@ def psnr(rec: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> to
     return 10.0 * torch.log10(data_range * data_range / mse)
 
 
+def _with_images(model, batch):
+    """``batch`` with ``pose_img`` / ``app_img`` made on the GPU from raw uint8 frames where it brings ``pose_img_u8`` /
+    ``app_img_u8`` (+ ``*_geom``) instead (image_input.batch_images); the batch itself otherwise."""
+    if "pose_img_u8" not in batch and "app_img_u8" not in batch:
+        return batch
+    from .. import image_input
+    made = image_input.batch_images(batch, model.spatial_size)
+    return {**batch, **made} if made else batch
+
+
 def _inplane_app(model, batch, inplane_parts):
     """The appearance input of an ``inplane_normalize`` model: ``batch["pose_img_inplane"]`` where the batch carries it, else the
     part crops cut on the GPU from ``batch["pose_img"]`` and ``batch["inplane_keypoints"]`` with ``inplane_parts`` (a
@@ -77,6 +87,7 @@ def compute_ssim(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tenso
     model.eval()
     total, count = None, 0
     for batch in batches:
+        batch = _with_images(model, batch)
         target = batch["pose_img"]
         if "app_img" in batch and type(model).__name__ == "VunetOrg":   # :71-74
             app = batch["app_img"]
@@ -137,6 +148,7 @@ def compute_fid(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor
     model.eval()
     gts, gens, n = [], [], 0
     for batch in batches:
+        batch = _with_images(model, batch)
         target = batch["pose_img"]
         if "app_img" in batch and type(model).__name__ == "VunetOrg":
             app = batch["app_img"]
