@@ -159,3 +159,42 @@ def make_joint_img(img_shape, joints, joint_model, line_colors=None, color_chann
     if len(img_shape) > 2 and img_shape[-1] == 1:
         img = np.mean(img, axis=-1)[:, :, None]
     return img
+
+
+# ------------------------------------------------------------------------------------------------
+# pose -> skeleton frame (lib/utils.py:733-750 add_joints_to_img; data/data_conversions_3d.py:1101-1114) on csrc/skeleton.hip
+# ------------------------------------------------------------------------------------------------
+# data/human36m.py:172-189 total_relative_joints (the 17-joint model of keypoints_3d_world)
+H36M_LIMBS = ((0, 1), (1, 2), (3, 4), (4, 5), (3, 6), (0, 6), (6, 7), (7, 8), (8, 9), (9, 10), (8, 11), (8, 14), (11, 12),
+              (12, 13), (14, 15), (15, 16))
+_LIMB_SIDE = (0, 0, 1, 1, 1, 0, 1, 1, 1, 1, 1, 0, 1, 1, 0, 0)   # which of the two colours a limb takes (:1102, :1106-1109)
+
+
+def skeleton_colors(color=None, overlay=False):
+    """The per-limb colours of project_onto_image_plane (data/data_conversions_3d.py:1101-1114): red / blue by default, a
+    two-colour list expanded over the sixteen limbs, any other list taken as it is -- and, as upstream, replaced by the
+    red / (0, 102, 255) palette when ``overlay`` is set and the list that was passed in does not have length two."""
+    if color is None:
+        color = [[255, 0, 0] if s == 0 else [0, 0, 255] for s in _LIMB_SIDE]
+    elif len(color) == 2:
+        color = [list(color[s]) for s in _LIMB_SIDE]
+    if overlay and len(color) != 2:
+        color = [[255, 0, 0] if s == 0 else [0, 102, 255] for s in _LIMB_SIDE]
+    return [[int(v) for v in c] for c in color]
+
+
+def add_joints_to_img(img_shape, kps, joints, color_kps=None, color_joints=None, thickness: int = 3, background: int = 0):
+    """Reference signature (lib/utils.py:733-750) for one frame, numpy in / HxWx3 uint8 numpy out: every pair of ``joints`` a
+    ``cv2.line`` of thickness 3 in its ``color_joints`` entry (a one-colour list serves every limb; ``color_kps`` is unused
+    upstream too).  The reference hands in the canvas itself; here ``img_shape`` (an array's shape works: ``img.shape``) and the
+    ``background`` byte it was filled with describe it, and the frame is drawn by the skeleton kernel."""
+    from ..render import skeleton_frames
+    if color_joints is None:
+        color_joints = skeleton_colors()
+    if len(color_joints) == 1:
+        color_joints = [color_joints[0] for _ in range(len(joints))]
+    h, w = int(img_shape[0]), int(img_shape[1])
+    k = torch.as_tensor(np.asarray(kps, dtype=np.float32)).unsqueeze(0).cuda()
+    out = skeleton_frames(k, (h, w), limbs=joints, colors=color_joints, target_size=None, background=background,
+                          thickness=thickness)
+    return out[0].cpu().numpy()

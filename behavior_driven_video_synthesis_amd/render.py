@@ -23,7 +23,7 @@ import torch
 
 from . import ops
 from .render_blk import engine_for
-from .lib.utils import H36M_JOINT_MODEL, make_joint_img_batch, scale_img
+from .lib.utils import H36M_JOINT_MODEL, H36M_LIMBS, make_joint_img_batch, scale_img, skeleton_colors
 
 
 def apply_affine_transform(x: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
@@ -140,10 +140,20 @@ class PoseCamera:
         # (joint_scaling = size / image size, applied to (x, y) with image_size given as (s[0], s[1]): :1139-1140)
         scale = [float(spatial_size) / float(image_size[0]), float(spatial_size) / float(image_size[1])]
         self.cam = torch.as_tensor(np.concatenate([ext.reshape(-1), [fx, x0, fy, y0], scale]), device=device)
+        self.cam_image = torch.as_tensor(np.concatenate([ext.reshape(-1), [fx, x0, fy, y0], [1.0, 1.0]]), device=device)
         self.spatial_size = int(spatial_size)
+        self.image_size = (int(image_size[0]), int(image_size[1]))
 
     def project(self, poses: torch.Tensor) -> torch.Tensor:
         """[T, n_use] decoded (normalised) pose vectors -> [T, J, 2] pixel keypoints at the synthesis resolution."""
+        return self._project(poses, self.cam)
+
+    def project_image(self, poses: torch.Tensor) -> torch.Tensor:
+        """[T, n_use] decoded (normalised) pose vectors -> [T, J, 2] keypoints in pixels of the camera's image (``image_size``):
+        the projection launch of ``project`` with a scale of (1, 1) -- what ``skeleton_frames`` draws."""
+        return self._project(poses, self.cam_image)
+
+    def _project(self, poses: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
         ops._dev(poses)
         x = poses.reshape(-1, poses.shape[-1]).contiguous()
         if x.shape[1] != self.n_use:
@@ -151,7 +161,7 @@ class PoseCamera:
         t, j = x.shape[0], self.dim // 3
         kps = torch.empty(t, j, 2, device=x.device, dtype=torch.float32)
         ops._call("vunet_seq_pose_project", ops._p(x), self.n_use, ops._p(self.dims), ops._p(self.mean), ops._p(self.std), self.dim,
-                  self.f32_math, ops._p(self.cam), ops._p(kps), t, j, ops._stream())
+                  self.f32_math, ops._p(cam), ops._p(kps), t, j, ops._stream())
         return kps
 
 
@@ -178,7 +188,9 @@ class AnglePoseCamera:
         fx, x0, fy, y0 = [float(v) for v in intrinsics]
         scale = [float(spatial_size) / float(image_size[0]), float(spatial_size) / float(image_size[1])]
         self.cam = torch.as_tensor(np.concatenate([ext.reshape(-1), [fx, x0, fy, y0], scale]), device=device)
+        self.cam_image = torch.as_tensor(np.concatenate([ext.reshape(-1), [fx, x0, fy, y0], [1.0, 1.0]]), device=device)
         self.spatial_size = int(spatial_size)
+        self.image_size = (int(image_size[0]), int(image_size[1]))
 
     def joints(self, poses: torch.Tensor) -> torch.Tensor:
         """[T, n_use] decoded (normalised) pose vectors -> [T, J, 3] world joint positions."""
@@ -191,11 +203,18 @@ class AnglePoseCamera:
 
     def project(self, poses: torch.Tensor) -> torch.Tensor:
         """[T, n_use] decoded (normalised) pose vectors -> [T, J, 2] pixel keypoints at the synthesis resolution."""
+        return self._project(poses, self.cam)
+
+    def project_image(self, poses: torch.Tensor) -> torch.Tensor:
+        """``PoseCamera.project_image``: keypoints in pixels of the camera's image, behind the forward kinematics."""
+        return self._project(poses, self.cam_image)
+
+    def _project(self, poses: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
         xyz = self.joints(poses)
         t, j = xyz.shape[0], xyz.shape[1]
         kps = torch.empty(t, j, 2, device=xyz.device, dtype=torch.float32)
         ops._call("vunet_seq_pose_project", ops._p(xyz), 3 * j, ops._p(self._dims), ops._p(self._zero), ops._p(self._one), 3 * j, 0,
-                  ops._p(self.cam), ops._p(kps), t, j, ops._stream())
+                  ops._p(cam), ops._p(kps), t, j, ops._stream())
         return kps
 
 
@@ -350,3 +369,238 @@ def neighbour_video(net, vunet, app_img: Optional[torch.Tensor], behavior_seq: t
     if vunet is None or app_img is None:
         frames = None
     return frames, rows, kps, found
+
+
+# ------------------------------------------------------------------------------------------------
+# The pose-only branch: skeleton frames, crops, overlays and grids (data/data_conversions_3d.py:1068-1228
+# project_onto_image_plane; lib/logging.py:1548-1868 make_eval_grid, :2680-2886 make_enrollment) on csrc/skeleton.hip
+# ------------------------------------------------------------------------------------------------
+def nearest_table(n_src: int, n_dst: int):
+    """The source index of every output index of ``cv2.resize(..., interpolation=cv2.INTER_NEAREST)`` along one axis, int32
+    [n_dst], built in float64 the way OpenCV 4.1.2's resizeNN does: ``ifx = 1 / (n_dst / n_src)``,
+    ``min(floor(x * ifx), n_src - 1)``.  cv2 is absent here: the rule is restated from the published source, not pinned."""
+    import numpy as np
+    ifx = 1.0 / (float(n_dst) / n_src)
+    return np.minimum(np.floor(np.arange(n_dst, dtype=np.float64) * ifx), n_src - 1).astype(np.int32)
+
+
+def crop_spans(kps, image_size, target_size, target_width: int = 128, crop_joints=None, rgb_size: Optional[int] = None):
+    """Host mirror of the kernel's crop rule (data/data_conversions_3d.py:1176-1184, :1194-1205): ``kps`` [F, J, 2] (numpy,
+    image pixels) -> int64 [F, 2, 2], ``(min_x, max_x)`` of the skeleton strip and of the strip of an ``rgb_size``-wide
+    synthesised frame (zeros without one).  float64, the joints added in index order.  Both strips scale x by the HEIGHT
+    ratio, as upstream does (``img.shape[:2]`` over cv2's (w, h) ``dsize``; ``joint_scaling`` over ``(s[0], s[1])``)."""
+    import numpy as np
+    hs, (ht, wt), tw = int(image_size[0]), target_size, int(target_width)
+    k = np.asarray(kps, dtype=np.float32).astype(np.float64)
+    if crop_joints is not None:
+        k = k[:, list(crop_joints)]
+    skel_div = float(hs) / float(wt)
+    rgb_mul = None if rgb_size is None else float(rgb_size) / float(hs)
+    out = np.zeros((k.shape[0], 2, 2), dtype=np.int64)
+    for f in range(k.shape[0]):
+        s0 = s1 = 0.0
+        for x in k[f, :, 0]:
+            s0 += float(x) / skel_div
+            if rgb_mul is not None:
+                s1 += float(x) * rgb_mul
+        o0 = int(min(max(0.0, s0 / k.shape[1] - tw // 2), wt - tw))
+        out[f, 0] = (o0, o0 + tw)
+        if rgb_mul is not None:
+            o1 = int(min(max(0.0, s1 / k.shape[1] - tw // 2), int(rgb_size) - tw))
+            out[f, 1] = (o1, o1 + tw)
+    return out
+
+
+_skeleton_tables = {}
+
+
+def _skeleton_const(key, make):
+    if key not in _skeleton_tables:
+        _skeleton_tables[key] = make()
+    return _skeleton_tables[key]
+
+
+def _frame_strides(t: torch.Tensor, n_lead: int):
+    """(frame stride, row stride) in bytes of a uint8 [*lead, H, W, 3] view whose pixels are packed and whose leading
+    dimensions advance by one common stride."""
+    if t.stride(-1) != 1 or t.stride(-2) != 3:
+        raise ValueError("skeleton_frames: `out` must keep its pixels packed (strides 3 and 1 over the last two dimensions)")
+    for i in range(n_lead - 1):
+        if t.shape[i + 1] != 1 and t.stride(i) != t.stride(i + 1) * t.shape[i + 1]:
+            raise ValueError("skeleton_frames: the leading dimensions of `out` must advance by one common stride")
+    return (t.stride(n_lead - 1) if n_lead else 0), t.stride(-3)
+
+
+@torch.no_grad()
+def skeleton_frames(kps: torch.Tensor, image_size, limbs=H36M_LIMBS, colors=None, target_size=(256, 256), background: int = 255,
+                    thickness: int = 3, crop: bool = False, target_width: int = 128, crop_joints=None,
+                    rgb: Optional[torch.Tensor] = None, overlay: bool = False, out: Optional[torch.Tensor] = None):
+    """Skeleton frames of ``kps`` [..., J, 2] (fp32 device tensor, (x, y) in pixels of an ``image_size`` = (h, w) camera image):
+    what ``project_onto_image_plane`` returns first -- every pair of ``limbs`` a ``cv2.line`` of its ``colors`` entry
+    (``skeleton_colors(None, overlay)`` by default) and of ``thickness`` on a ``background``-filled canvas of the image size,
+    resized to ``target_size`` = (Ht, Wt) with INTER_NEAREST (None: the canvas itself).  One launch for every frame; the canvas
+    is never built (csrc/skeleton.hip).  ``cv2.putText`` is left out.
+
+    ``crop``: cut the ``target_width`` strip around the mean x of the joints (``crop_joints``: a subset, the ``kps_to_use`` of
+    a small joint model) and also return the spans, int32 [..., 2, 2] -- ``(min_x, max_x)`` of the skeleton strip and of the
+    rgb strip, the reference's ``masks``.  ``rgb``: synthesised frames, uint8 [..., Ht, S, 3] (square with ``crop``); cut to
+    their own strip with ``crop``, and with ``overlay`` laid under the skeleton wherever that is (255, 255, 255).
+    ``out``: a uint8 view [..., Ht, W', 3] to draw the skeleton frames into (packed pixels; any row stride, one frame stride).
+
+    Returns the skeleton frames uint8 [..., Ht, Wt or target_width, 3]; with more than one result a tuple in the order
+    (frames, spans if crop, rgb strips if rgb and crop, overlays if rgb and overlay)."""
+    ops._dev(kps)
+    if kps.dim() < 2 or kps.shape[-1] != 2:
+        raise ValueError(f"skeleton_frames: keypoints [..., J, 2] expected, got {tuple(kps.shape)}")
+    lead, j = tuple(kps.shape[:-2]), int(kps.shape[-2])
+    k = kps.reshape(-1, j, 2).contiguous()
+    f, dev = k.shape[0], k.device
+    hs, ws = int(image_size[0]), int(image_size[1])
+    limbs = tuple((int(a), int(b)) for a, b in limbs)
+    colors = skeleton_colors(None, overlay) if colors is None else [[int(v) for v in c] for c in colors]
+    if len(colors) == 1:
+        colors = colors * len(limbs)
+    if len(colors) != len(limbs):
+        raise ValueError(f"skeleton_frames: {len(limbs)} limbs need as many colours, got {len(colors)}")
+    if any(not (0 <= a < j and 0 <= b < j) for a, b in limbs):
+        raise ValueError(f"skeleton_frames: a limb names a joint outside the {j} given")
+    if any(not 0 <= v <= 255 for c in colors for v in c) or any(len(c) != 3 for c in colors):
+        raise ValueError("skeleton_frames: colours are (r, g, b) bytes")
+    ckey = tuple(tuple(c) for c in colors)
+    d_limbs, d_colors = _skeleton_const(("limbs", limbs, ckey, dev), lambda: (
+        torch.tensor(limbs, dtype=torch.int32, device=dev).reshape(-1, 2), torch.tensor(ckey, dtype=torch.uint8, device=dev).reshape(-1, 3)))
+    if target_size is None:
+        ht, wt, sy, sx = hs, ws, None, None
+    else:
+        ht, wt = int(target_size[0]), int(target_size[1])
+        sy = _skeleton_const(("table", hs, ht, dev), lambda: torch.as_tensor(nearest_table(hs, ht), device=dev))
+        sx = _skeleton_const(("table", ws, wt, dev), lambda: torch.as_tensor(nearest_table(ws, wt), device=dev))
+    tw = int(target_width) if crop else 0
+    if crop and not 1 <= tw <= wt:
+        raise ValueError(f"skeleton_frames: a strip of {tw} columns does not fit frames {wt} wide")
+    wo = tw if crop else wt
+    d_cj, n_cj = None, 0
+    if crop and crop_joints is not None:
+        cj = tuple(int(c) for c in crop_joints)
+        if not cj or any(not 0 <= c < j for c in cj):
+            raise ValueError(f"skeleton_frames: crop_joints must name some of the {j} joints")
+        d_cj, n_cj = _skeleton_const(("cj", cj, dev), lambda: torch.tensor(cj, dtype=torch.int32, device=dev)), len(cj)
+    sw, r = 0, None
+    if rgb is not None:
+        if not rgb.is_cuda or rgb.dtype != torch.uint8 or tuple(rgb.shape[:-3]) != lead or rgb.shape[-1] != 3 or rgb.shape[-3] != ht:
+            raise ValueError(f"skeleton_frames: rgb must be a uint8 device tensor [..., {ht}, S, 3] over the same frames, got "
+                             f"{tuple(rgb.shape)} {rgb.dtype}")
+        sw = int(rgb.shape[-2])
+        if (crop and (sw != ht or sw < tw)) or (not crop and sw != wt):
+            raise ValueError(f"skeleton_frames: rgb frames {tuple(rgb.shape[-3:])} do not match "
+                             + (f"a square frame of at least {tw} columns" if crop else f"the {ht} x {wt} skeleton frames"))
+        r = rgb.reshape(-1, ht, sw, 3).contiguous()
+    if out is None:
+        frames = torch.empty(*lead, ht, wo, 3, dtype=torch.uint8, device=dev)
+    else:
+        if not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != lead + (ht, wo, 3):
+            raise ValueError(f"skeleton_frames: `out` must be a uint8 device tensor {lead + (ht, wo, 3)}, got {tuple(out.shape)} {out.dtype}")
+        frames = out
+    fs, rs = _frame_strides(frames, len(lead))
+    span = torch.zeros(*lead, 2, 2, dtype=torch.int32, device=dev) if crop else None
+    strip = torch.empty(*lead, ht, wo, 3, dtype=torch.uint8, device=dev) if (r is not None and crop) else None
+    over = torch.empty(*lead, ht, wo, 3, dtype=torch.uint8, device=dev) if (r is not None and overlay) else None
+    # upstream divides x by img.shape[0] / dsize[0] = Hs / Wt (cv2's dsize is (w, h)) and multiplies it by S / Hs
+    ops._call("vunet_skeleton_raster", ops._p(k), f, j, ops._p(d_limbs), ops._p(d_colors), len(limbs), hs, ws, int(thickness),
+              int(background), ops._p(sy), ops._p(sx), ht, wt, tw, ops._p(d_cj), n_cj, float(hs) / float(wt),
+              (float(sw) / float(hs)) if sw else 0.0, ops._p(r), sw, ops._p(frames), fs, rs, ops._p(over), ops._p(strip),
+              ops._p(span), ops._stream())
+    res = [frames] + [t for t in (span, strip, over) if t is not None]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def skeleton_video(poses, camera, **style):
+    """The pose-only video of the ``poses`` [..., L, n] any of ``transfer_video`` / ``interpolation_video`` /
+    ``neighbour_video`` / ``behavior_video`` returns (a list of such rows: a list, None entries kept): one
+    ``camera.project_image`` launch, then ``skeleton_frames`` at the camera's ``image_size``; ``style``: its keyword arguments."""
+    if isinstance(poses, (list, tuple)):
+        return [None if p is None else skeleton_video(p, camera, **style) for p in poses]
+    kps = camera.project_image(poses.reshape(-1, poses.shape[-1]))
+    return skeleton_frames(kps.reshape(*poses.shape[:-1], kps.shape[-2], 2), camera.image_size, **style)
+
+
+@torch.no_grad()
+def transfer_grid(net, vunet, app_img: Optional[torch.Tensor], behaviors: torch.Tensor, starts: torch.Tensor, camera,
+                  behavior_frames: Optional[torch.Tensor] = None, start_frame: int = 0, target_size=(256, 256),
+                  joint_model=H36M_JOINT_MODEL, dtype: str = "bf16", share_appearance: bool = True, chunk: int = 16, **style):
+    """The evaluation grid of ``make_eval_grid`` (lib/logging.py:1662-1790): ``behaviors`` [Nb, T, n] re-enacted from
+    ``starts[:, start_frame]`` ([Ns, T', n]).  The codes are the posterior means (as ``transfer_video``); all Nb Ns of them are
+    rolled out in ONE ``generate_seq`` batch, the start pose put in front, and the result cut to L = T frames, the length of
+    the behaviour row (upstream's ``min_time``).  Layout, tiles of ``target_size`` = (Ht, Wt): the first column holds each
+    start pose's first skeleton frame held still under a black tile; then one column per behaviour -- its own skeleton video
+    on top, its re-enactment from every start pose below.  Every tile is drawn in place (``skeleton_frames(out=...)``).
+    With ``vunet`` and ``app_img`` a second grid holds the synthesised frames (Ht = Wt = the synthesis size): ``behavior_frames``
+    uint8 [Nb, L, Ht, Wt, 3] on top where given, white where not, and a white first column (the ground-truth stills upstream
+    puts there are the caller's to read).  ``camera``: one camera, or Ns + 1 of them -- one per start pose, then the behaviour
+    row's.  ``style``: ``skeleton_frames`` keywords other than crop / rgb / out.
+
+    Returns (grid uint8 [L, (1 + Ns) Ht, (1 + Nb) Wt, 3], grid_rgb or None, poses [Nb, Ns, L, n])."""
+    if behaviors.dim() != 3 or starts.dim() != 3 or behaviors.shape[-1] != starts.shape[-1]:
+        raise ValueError(f"transfer_grid: behaviours [Nb, T, n] and start sequences [Ns, T', n] expected, got "
+                         f"{tuple(behaviors.shape)} and {tuple(starts.shape)}")
+    if not net.ib:
+        raise ValueError("transfer_grid needs the behaviour net's information bottleneck (its posterior mean is the code)")
+    if any(key in style for key in ("crop", "rgb", "out", "overlay")):
+        raise ValueError("transfer_grid draws plain tiles: crop / rgb / overlay / out are not grid options")
+    nb, t, n = behaviors.shape
+    ns = starts.shape[0]
+    cams = list(camera) if isinstance(camera, (list, tuple)) else [camera] * (ns + 1)
+    if len(cams) != ns + 1:
+        raise ValueError(f"transfer_grid: one camera or {ns + 1} (one per start pose, then the behaviour row's), got {len(cams)}")
+    start_frame = start_frame % starts.shape[1]
+    ht, wt = int(target_size[0]), int(target_size[1])
+    mu = net.engine().infer_b(behaviors.contiguous(), None)[0]
+    x0 = starts[:, start_frame]                                                  # [Ns, n]
+    codes = mu.unsqueeze(1).expand(nb, ns, mu.shape[-1]).reshape(nb * ns, -1).contiguous()
+    first = x0.unsqueeze(0).expand(nb, ns, n).reshape(nb * ns, 1, n).contiguous()
+    if t > 1:
+        xs, *_ = net.generate_seq(codes, first, len=t - 1, start_frame=0)
+        poses = torch.cat([first, xs], dim=1)
+    else:
+        poses = first
+    poses = poses.reshape(nb, ns, t, n)
+    grid = torch.empty(t, (1 + ns) * ht, (1 + nb) * wt, 3, dtype=torch.uint8, device=behaviors.device)
+
+    def tile(g, row, col):
+        return g[:, row * ht:(row + 1) * ht, col * wt:(col + 1) * wt]
+
+    tile(grid, 0, 0).zero_()
+    for b in range(nb):
+        kb = cams[ns].project_image(behaviors[b])
+        skeleton_frames(kb, cams[ns].image_size, target_size=(ht, wt), out=tile(grid, 0, 1 + b), **style)
+    for s in range(ns):
+        ks = cams[s].project_image(poses[:, s].reshape(nb * t, n)).reshape(nb, t, -1, 2)
+        for b in range(nb):
+            skeleton_frames(ks[b], cams[s].image_size, target_size=(ht, wt), out=tile(grid, 1 + s, 1 + b), **style)
+        tile(grid, 1 + s, 0).copy_(tile(grid, 1 + s, 1)[:1].expand(t, ht, wt, 3))
+    grid_rgb = None
+    if vunet is not None and app_img is not None:
+        if any(c.spatial_size != ht or c.spatial_size != wt for c in cams[:ns]):
+            raise ValueError(f"transfer_grid: synthesised tiles are {cams[0].spatial_size} pixels square, the grid's tiles {ht} x {wt}")
+        grid_rgb = torch.full_like(grid, 255)
+        if behavior_frames is not None:
+            if tuple(behavior_frames.shape) != (nb, t, ht, wt, 3) or behavior_frames.dtype != torch.uint8:
+                raise ValueError(f"transfer_grid: behavior_frames must be uint8 {(nb, t, ht, wt, 3)}, got {tuple(behavior_frames.shape)}")
+            for b in range(nb):
+                tile(grid_rgb, 0, 1 + b).copy_(behavior_frames[b])
+        for s in range(ns):
+            ks = cams[s].project(poses[:, s].reshape(nb * t, n)).reshape(nb, t, -1, 2)
+            for b in range(nb):
+                rgb, _ = render_sequence(vunet, app_img, ks[b], spatial_size=cams[s].spatial_size, joint_model=joint_model,
+                                         chunk=chunk, dtype=dtype, share_appearance=share_appearance)
+                tile(grid_rgb, 1 + s, 1 + b).copy_(rgb)
+    return grid, grid_rgb, poses
+
+
+def enrollment(frames: torch.Tensor, step: int = 4) -> torch.Tensor:
+    """The still image of ``make_enrollment`` (lib/logging.py:2823-2828): every ``step``-th frame of ``frames`` [L, H, W, 3] side
+    by side -> [H, ceil(L / step) W, 3]; rows of videos [R, L, H, W, 3] are stacked below each other -> [R H, ..., 3]."""
+    if frames.dim() not in (4, 5) or step < 1:
+        raise ValueError(f"enrollment: frames [L, H, W, 3] or [R, L, H, W, 3] and a positive step expected, got {tuple(frames.shape)}")
+    rows = frames.unsqueeze(0) if frames.dim() == 4 else frames
+    return torch.cat([torch.cat(list(v[::step]), dim=1) for v in rows], dim=0)
