@@ -19,6 +19,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from hip_parity_utils import assert_ulps
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
@@ -58,27 +60,6 @@ def _gen(seed):
 
 def _f64(t):
     return t.detach().cpu().double()
-
-
-def assert_ulps(got, ref, bound, name="", aten=None):
-    """|got - ref| <= bound elementwise where ref is finite; where ``aten`` (ATen's fp32 result) or ref is NaN / inf, got
-    must be NaN / the same inf."""
-    got = _f64(got).reshape(-1)
-    ref = ref.double().reshape(-1)
-    pattern = (aten.double().reshape(-1) if aten is not None else ref)
-    nan = torch.isnan(pattern)
-    assert torch.equal(torch.isnan(got), nan), f"{name}: NaN pattern differs at {torch.nonzero(torch.isnan(got) != nan)[:8].tolist()}"
-    inf = torch.isinf(pattern)
-    assert torch.equal(got[inf], pattern[inf]), f"{name}: inf pattern differs"
-    fin = torch.isfinite(pattern) & torch.isfinite(ref)
-    assert torch.isfinite(got[fin]).all(), f"{name}: non-finite where the reference is finite"
-    b = bound.double().reshape(-1) if torch.is_tensor(bound) else torch.full_like(ref, float(bound))
-    err = (got[fin] - ref[fin]).abs()
-    over = err > b[fin]
-    if over.any():
-        i = int(torch.nonzero(over)[0])
-        raise AssertionError(f"{name}: {int(over.sum())} elements over the bound; first: got {float(got[fin][i])!r} ref "
-                             f"{float(ref[fin][i])!r} err {float(err[i]):.3e} bound {float(b[fin][i]):.3e}")
 
 
 def _special():
