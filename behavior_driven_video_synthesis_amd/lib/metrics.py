@@ -7,11 +7,15 @@ one HIP kernel over the whole batch (``vunet_ssim_partial``); the dataset / samp
 hook takes an iterable of batches.
 
 The Inception-based scores (``compute_fid`` :119-282, ``_calculate_fid`` :285-322, ``inception_score`` :362-415) are
-built as DRIVERS with a pluggable feature extractor / classifier: the pretrained torchvision Inception-v3 weights are
-third-party data this build cannot fetch (like the VGG19 weights, they are user-supplied: any callable mapping an image
-batch to features / logits).  The statistics -- feature mean and covariance, the matrix square root, traces, softmax and
-the KL divergences -- are float64 on the host exactly as the reference computes them (numpy / scipy), pinned against
-the reference's own functions on synthetic features (tests/golden/g7_metrics.npz).
+DRIVERS around a feature extractor / classifier: any callable mapping an image batch to features / logits.  The network the
+reference plugs in -- torchvision's Inception-v3 -- is shipped as ``models.imagenet_pretrained.FIDInceptionModel`` (pool
+features, the reference's class) and ``InceptionV3`` (logits), inference only, on their own HIP kernels (models/inception.py):
+``compute_fid(model, batches, feature_extractor=FIDInceptionModel(state_dict=sd).cuda())``,
+``inception_score(imgs, classifier=InceptionV3(state_dict=sd).cuda(), splits=10, resize=True)``.  Only the pretrained WEIGHTS are
+third-party data this build cannot fetch (like VGG19's): ``sd`` is a torchvision ``inception_v3`` state dict the user supplies.
+The statistics -- feature mean and covariance, the matrix square root, traces, softmax and the KL divergences -- are float64
+on the host exactly as the reference computes them (numpy / scipy), pinned against the reference's own functions on synthetic
+features (tests/golden/g7_metrics.npz).
 """
 from __future__ import annotations
 
@@ -141,7 +145,8 @@ def compute_fid(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor
                 gt_features: Optional[np.ndarray] = None, max_n_samples: int = 8000,
                 inplane_normalize: bool = False, inplane_parts=None) -> float:
     """lib/metrics.py:119-282 on an iterable of batches.  ``feature_extractor(images) -> [N, D]`` stands for the
-    reference's ``FIDInceptionModel`` (user-supplied pretrained Inception-v3 pool features); ground-truth features are
+    reference's ``FIDInceptionModel`` (``models.imagenet_pretrained.FIDInceptionModel`` with the user's torchvision weights, or any
+    other callable); ground-truth features are
     computed from ``batch["pose_img"]`` unless ``gt_features`` (the reference's cached ``<dataset>-fid-features.npy``) is
     given; generated features come from the reconstructions ``model(app, stickman)[0]`` (:243-258)."""
     was_training = model.training
@@ -184,7 +189,7 @@ def inception_score(imgs, classifier: Callable, batch_size: int = 32, resize: bo
                     device=None) -> Tuple[float, float]:
     """lib/metrics.py:362-415.  ``imgs``: tensor [N, 3, H, W] in [-1, 1] (or a dataset of 1-tuples of such images, as the
     reference takes); ``classifier(images) -> logits [n, K]`` stands for torchvision's pretrained ``inception_v3``
-    (user-supplied).  ``resize``: bilinear up-sampling to 299 x 299 first (:385, ``nn.Upsample(size=(299, 299),
+    (``models.imagenet_pretrained.InceptionV3`` with the user's weights, or any other callable).  ``resize``: bilinear up-sampling to 299 x 299 first (:385, ``nn.Upsample(size=(299, 299),
     mode='bilinear')`` -- align_corners False)."""
     if not torch.is_tensor(imgs):
         imgs = torch.stack([imgs[i][0] if isinstance(imgs[i], (tuple, list)) else imgs[i] for i in range(len(imgs))])

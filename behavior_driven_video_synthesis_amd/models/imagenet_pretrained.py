@@ -534,3 +534,7 @@ class PerceptualVGG(nn.Module):
             return pooled
         self._walk(pred, term, term_pool if ops.l1_pool_fusion["on"] else None)
         return losses
+
+
+# The inference-only Inception-v3 behind the reference's class names (models/imagenet_pretrained.py:64-111): models/inception.py
+from .inception import FIDInceptionModel, InceptionV3  # noqa: E402,F401
