@@ -121,11 +121,13 @@ def transfer_metrics(net, x_s: torch.Tensor, x_t: torch.Tensor, x_related: torch
 class BehaviorEvaluator:
     """The reference's metric lists (experiments/behavior_net.py:1112-1121, lib/logging.py APD): per-sequence ASD, FSD and APD,
     per-batch ADE, FDE and transfer metrics.  ``add`` keeps device tensors; ``summary`` copies them to the host once and returns
-    ``np.mean`` of every non-empty list."""
+    ``np.mean`` of every non-empty list -- plus, when an evaluation ran with ``latent_diagnostics``, the numbers of
+    ``latent_diag.LatentDiagnostics.summary``."""
 
     def __init__(self):
         self.per_seq: Dict[str, List[torch.Tensor]] = {k: [] for k in ("APD", "ASD", "FSD")}
         self.per_batch: Dict[str, List[torch.Tensor]] = {k: [] for k in ("ADE", "FDE") + TRANSFER}
+        self.latent = None      # latent_diag.LatentDiagnostics, set by BehaviorNet.evaluate(..., latent_diagnostics=...)
 
     def add(self, metrics: Dict[str, torch.Tensor]):
         for k, v in metrics.items():
@@ -147,7 +149,10 @@ class BehaviorEvaluator:
         return out
 
     def summary(self) -> Dict[str, float]:
-        return {k: float(np.mean(v)) for k, v in self.lists().items()}
+        out = {k: float(np.mean(v)) for k, v in self.lists().items()}
+        if self.latent is not None:      # self_recon_eval and, with a flow, the four FlowLoss means and ks_p_mean
+            out.update(self.latent.summary())
+        return out
 
 
 # ---- the real-vs-fake classifier study (experiments/behavior_net.py:1262-1295 collection, :1302-1521 study)

@@ -56,6 +56,10 @@ ALIASES = {
 
 # names this package defines for its own modules' use but does NOT export under the reference's module name
 HIDDEN = {"lib.modules": ("ActNorm", "BasicFullyConnectedNet", "Linear", "_Marker"),
+          # the unchanged training loop keeps the reference's own FlowLoss (it runs under autograd, where this package's class
+          # evaluates the same torch expression anyway); the float64 kernel path is for evaluation code written against
+          # behavior_driven_video_synthesis_amd.lib.losses / latent_diag
+          "lib.losses": ("FlowLoss", "nll", "flow_loss_expression"),
           # the regressor's mirror is a parameter holder for BehaviorNet's fused step; the reference's loop keeps its own class
           "models.pose_behavior_rnn": ("Regressor_fly",)}
 

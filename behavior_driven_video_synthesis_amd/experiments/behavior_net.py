@@ -17,7 +17,9 @@
 
 ``BehaviorNet.evaluate(batches, stats)`` scores a model as ``run_inference`` does (:1112-1301, APD from lib/logging.py:2079-2093):
 ASD, FSD, APD, ADE and FDE of ``n_samples`` sampled behaviours per scored sequence, and the transfer metrics
-(behavior_eval.py, csrc/seq_eval.hip).
+(behavior_eval.py, csrc/seq_eval.hip).  With ``latent_diagnostics`` it also runs the latent part of ``eval_nets``
+(lib/logging.py:2228-2262, :2549-2562): the flow's held-out ``FlowLoss`` entries, the self-reconstruction error, the KS test of the
+Gaussianised codes and the collected sample sets (latent_diag.py, csrc/seq_latent.hip).
 
 Not on this path, and said here rather than silently dropped:
 * the second pass ``net(seq_2, seq_start_t, seq_len)`` (:600-603): none of its outputs reaches the loss or the log;
@@ -194,7 +196,8 @@ class BehaviorNet:
     # ---- scoring (experiments/behavior_net.py:1112-1301, lib/logging.py:2079-2093)
     @torch.no_grad()
     def evaluate(self, batches, stats, n_samples: int = 50, skip: int = 4, use_flow: bool = True, z=None, eps=None,
-                 classifier_study: bool = False, study_kwargs=None, study_noise=None, euler=None, flow_weights: str = "f32"):
+                 classifier_study: bool = False, study_kwargs=None, study_noise=None, euler=None, flow_weights: str = "f32",
+                 latent_diagnostics=False, latent_noise=None):
         """The reference's per-batch metric recipe of ``run_inference`` over an iterable of dict batches -> a
         ``behavior_eval.BehaviorEvaluator`` (``.summary()``: the means the reference prints; ``.lists()``: the lists).
 
@@ -226,14 +229,37 @@ class BehaviorNet:
         ``flow_weights``: "f32" or "bf16", the flow's weight precision while this call samples through it
         (``seq.flow_weight_mode``; the previous mode is restored afterwards).  bf16 weight images halve the bytes of a pass and
         measured 12-15 % faster at 1 and 16 rows but SLOWER than f32 in 64-row chunks, which is how the
-        ``n_samples`` rows per sequence run here: the default stays "f32"."""
+        ``n_samples`` rows per sequence run here: the default stays "f32".
+
+        ``latent_diagnostics``: False (nothing of this runs, no key is added), True, or {"n_max": 20000, "ks_method":
+        "reference"}: the latent part of ``eval_nets`` (lib/logging.py:1988-1997, :2228-2262, :2549-2562, :2623, :2656-2660) per
+        batch, on the device and without a host sync.  The reconstruction pass ``net(x_s, x_s, T)`` (``eps`` is its noise; shared
+        with ``euler``) gives b, mu, pre and ``self_recon = mean((seq_pred_s - target_s)^2)``; with the flow, ``gauss, logdet =
+        flow(b)`` gives the batch's ``FlowLoss`` entries (``latent_diag.flow_nll``) and ``flow.reverse(randn_like(b))`` the flow
+        samples.  While ``(batch_nr + 1) B < n_max`` -- strict, as in the reference -- b, mu, pre, the prior sample (the noise
+        ``net(x_s, x_s, T, sample=True)[3]`` returns; the pass around it computes nothing else that is kept and is not run),
+        gauss, the flow samples and the batch's optional ``action_labels`` ([B] or [B, T] int64, the last frame's is kept) go
+        into a ``latent_diag.LatentCollector``.  After the loop ``ev.latent`` (``latent_diag.LatentDiagnostics``) holds the
+        collector, ``ks`` = the KS test of every dimension of the collected gauss against N(0, 1), and ``summary()`` gains
+        ``self_recon_eval``, the four ``FlowLoss`` means and ``ks_p_mean`` (without a flow: ``self_recon_eval`` only).
+        ``latent_noise``: per batch (or one for all) {"prior": [B, H], "flow": [B, H], "reference": [B, H]} (None: drawn)."""
         from ..seq import flow_weight_mode
         with flow_weight_mode(self.latent_flow if use_flow else None, flow_weights):
-            return self._evaluate(batches, stats, n_samples, skip, use_flow, z, eps, classifier_study, study_kwargs, study_noise, euler)
+            return self._evaluate(batches, stats, n_samples, skip, use_flow, z, eps, classifier_study, study_kwargs, study_noise, euler,
+                                  latent_diagnostics, latent_noise)
 
-    def _evaluate(self, batches, stats, n_samples, skip, use_flow, z, eps, classifier_study, study_kwargs, study_noise, euler):
+    def _evaluate(self, batches, stats, n_samples, skip, use_flow, z, eps, classifier_study, study_kwargs, study_noise, euler,
+                  latent_diagnostics=False, latent_noise=None):
         from .. import behavior_eval as E
         ev = E.BehaviorEvaluator()
+        latent_kw = None
+        if latent_diagnostics:
+            latent_kw = {"n_max": 20000, "ks_method": "reference"}
+            if isinstance(latent_diagnostics, dict):
+                unknown = set(latent_diagnostics) - set(latent_kw)
+                if unknown:
+                    raise ValueError(f"latent_diagnostics: unknown keys {sorted(unknown)}")
+                latent_kw.update(latent_diagnostics)
         if euler is not None:
             import sys
             from .. import pose_angles as A
@@ -252,9 +278,13 @@ class BehaviorNet:
             zb = z[bi] if isinstance(z, (list, tuple)) else z
             samples = E.sample_behaviors(self.net, flow, target_s[::skip].contiguous(), n_samples, t, start_frame=t - 1, z=zb)
             ev.add(E.sample_metrics(samples, fut, stats))
+            if euler is not None or latent_kw is not None:       # one reconstruction pass serves both
+                self_pass = self.net(x_s, x_s, t, eps=eps[bi] if isinstance(eps, (list, tuple)) else eps)
             if euler is not None:
-                rec = self.net(x_s, x_s, t, eps=eps[bi] if isinstance(eps, (list, tuple)) else eps)[0]
-                ev.euler.add(A.euler_error(rec, target_s, angle_stats, horizons), batch.get("actions") or ["all"] * x_s.shape[0])
+                ev.euler.add(A.euler_error(self_pass[0], target_s, angle_stats, horizons), batch.get("actions") or ["all"] * x_s.shape[0])
+            if latent_kw is not None:
+                self._latent_batch(ev, latent_kw, bi, batch, self_pass, target_s, flow,
+                                   latent_noise[bi] if isinstance(latent_noise, (list, tuple)) else latent_noise)
             if study is not None:
                 if study.full:
                     break
@@ -268,7 +298,45 @@ class BehaviorNet:
         if study is not None:
             ev.study_set = study
             ev.study = E.classifier_study(study, **kw)
+        if ev.latent is not None:
+            ev.latent.finish()
         return ev
+
+    @torch.no_grad()
+    def _latent_batch(self, ev, kw, batch_nr, batch, self_pass, target_s, flow, noise):
+        """One batch of eval_nets' latent part (lib/logging.py:1988-1997, :2228-2262): device work only."""
+        from .. import latent_diag as L
+        seq_pred, _, _, b, mu, _, pre = self_pass
+        rows, h = b.shape[0], b.shape[1]
+        noise = noise or {}
+
+        def draw(key, like):
+            v = noise.get(key)
+            return torch.randn_like(like) if v is None else v.to(like.device, torch.float32).reshape(like.shape).contiguous()
+        if ev.latent is None:
+            dims = {"b": h, "mu": mu.shape[1], "pre": pre.reshape(rows, -1).shape[1], "prior_samples": h}
+            if flow is not None:
+                dims.update(flow_samples=h, gaussian_samples=h)
+            ev.latent = L.LatentDiagnostics(L.LatentCollector(dims, kw["n_max"], b.device), kw["n_max"], kw["ks_method"], flow is not None)
+        lat = ev.latent
+        admit = lat.admits(batch_nr, rows)
+        if flow is not None:
+            gauss, logdet = flow(b)
+            gauss = gauss.reshape(rows, h)
+            lat.flow_scalars.append(L.flow_nll(gauss, logdet, draw("reference", gauss)).scalars)
+            flow_samples = flow.reverse(draw("flow", b)).reshape(rows, h)
+            if admit:
+                lat.collector.add("flow_samples", flow_samples)
+                lat.collector.add("gaussian_samples", gauss)
+        lat.recon.append(torch.mean((seq_pred - target_s) ** 2))
+        if admit:
+            lat.collector.add("b", b)
+            lat.collector.add("mu", mu)
+            lat.collector.add("pre", pre)
+            lat.collector.add("prior_samples", draw("prior", b))
+            if "action_labels" in batch:
+                a = torch.as_tensor(batch["action_labels"]).to(b.device, torch.int64)
+                lat.collector.add("actions", a[:, -1] if a.dim() == 2 else a)
 
     @torch.no_grad()
     def _collect_study(self, batch, x_s, target_s, flow, study, eps, noise, ev):

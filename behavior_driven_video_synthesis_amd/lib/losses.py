@@ -1,6 +1,6 @@
 """MI355X-native counterparts of the hot subset of the reference's ``lib/losses.py`` (:11-14, :26-37,
-:55-119, :129-149, :283-291): same function names, argument meaning and return types; the reductions
-run in the fused HIP kernels (``vunet_l1_mean_*``, ``vunet_kl_*``, ``vunet_sqdiff_*``).
+:55-119, :129-149, :283-291, :295-311): same function names, argument meaning and return types; the reductions
+run in the fused HIP kernels (``vunet_l1_mean_*``, ``vunet_kl_*``, ``vunet_sqdiff_*``, ``vunet_seq_latent_nll``).
 """
 from __future__ import annotations
 
@@ -98,3 +98,43 @@ class GANLoss(nn.Module):
 
     def forward(self, pred, target):
         return self.loss(pred, target)
+
+
+def nll(sample):
+    """:330-331 -- the standard normal's negative log-density without its constant, per row: half the squared norm of
+    everything behind the batch dimension ([B, C] or [B, C, 1, 1])."""
+    return sample.flatten(1).square().sum(dim=1) / 2
+
+
+def flow_loss_expression(sample, logdet, noise):
+    """The four entries of :300-311 in plain, differentiable torch, in the inputs' dtype: -> (loss, log)."""
+    terms = {"nll_loss": nll(sample).mean(), "nlogdet_loss": logdet.mean().neg(), "reference_nll_loss": nll(noise).mean()}
+    terms["flow_loss"] = terms["nll_loss"] + terms["nlogdet_loss"]
+    keys = ("flow_loss", "reference_nll_loss", "nlogdet_loss", "nll_loss")
+    return terms["flow_loss"], {k: terms[k].item() for k in keys}
+
+
+class FlowLoss(nn.Module):
+    """lib/losses.py:295-311: ``forward(sample, logdet) -> (loss, log)``, ``log`` the four entries ``flow_loss``,
+    ``reference_nll_loss``, ``nlogdet_loss``, ``nll_loss`` as Python floats.
+
+    Without a gradient to carry (grad mode off, or neither input requires one: the evaluation loop, lib/logging.py:2231-2232)
+    the entries come from ``latent_diag.flow_nll`` -- float64 accumulation, any batch size -- and ``loss`` is a 0-dim fp32
+    device tensor.  With one, the same four entries are formed in plain torch (``flow_loss_expression``), so a training loop
+    written against the reference's class back-propagates through it unchanged.  ``noise`` (not in the reference's signature): the draw behind
+    ``reference_nll_loss`` instead of ``torch.randn_like(sample)``."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, sample, logdet, noise=None):
+        assert len(logdet.shape) == 1
+        if not sample.is_cuda or not logdet.is_cuda:
+            raise RuntimeError("FlowLoss needs device tensors (hand-written gfx950 kernels; no CPU fallback)")
+        if noise is None:
+            noise = torch.randn_like(sample)
+        if torch.is_grad_enabled() and (sample.requires_grad or logdet.requires_grad):
+            return flow_loss_expression(sample, logdet, noise)
+        from ..latent_diag import flow_nll
+        res = flow_nll(sample, logdet, noise)
+        return res.scalars[0].to(torch.float32), res.log()
