@@ -75,6 +75,29 @@ def save_ckpt(directory: str, key: str, iteration: int, trainer, n_saved: int = 
     return path
 
 
+def save_metric_ckpt(directory: str, trainer, epoch: int, ssim: float, is_rec: float) -> Tuple[str, str]:
+    """The metric-tagged checkpoint of ``compute_eval_metrics`` (experiments/shape_and_pose_net.py:757-773): the model's state
+    dict as ``<directory>/epoch_ckpts/model@e{epoch}@ssim={ssim}-is={is_rec}.pth`` and the optimiser's as ``opt@e...pth`` -- two
+    plain state dicts, not the ``{"model", "optimizer"}`` layout of ``save_ckpt``.  -> (model path, optimiser path)."""
+    save_dir = os.path.join(directory, "epoch_ckpts")
+    os.makedirs(save_dir, exist_ok=True)
+    sd = trainer.state_dict()
+
+    def host(o):
+        if isinstance(o, torch.Tensor):
+            return o.detach().cpu()
+        if isinstance(o, dict):
+            return type(o)((k, host(v)) for k, v in o.items())
+        if isinstance(o, (list, tuple)):
+            return type(o)(host(v) for v in o)
+        return o
+    tag = f"e{epoch}@ssim={ssim}-is={is_rec}.pth"
+    model_path, opt_path = os.path.join(save_dir, "model@" + tag), os.path.join(save_dir, "opt@" + tag)
+    torch.save(host(sd["model"]), model_path)
+    torch.save(host(sd["optimizer"]), opt_path)
+    return model_path, opt_path
+
+
 def restore(directory: str, trainer, key: str = "reg_ckpt") -> bool:
     """Restart ``trainer`` (a ``ShapePoseNet``) from the newest checkpoint of ``directory`` the way the reference does
     (:87-95, :248-255): the ``key`` file for the VUnet + Adam, the ``regressor`` file for the regressor + its Adam

@@ -141,6 +141,15 @@ class Vunet:
             return qs
         return run_probe(regressor, encode, batches, n_epochs, lr, eps)
 
+    def evaluate(self, batches, classifier, crop=None, max_n_samples: int = 8000, splits: int = 1, sampling: str = "reference",
+                 inplane_parts=None) -> dict:
+        """As ``ShapePoseNet.evaluate``, over ``VunetOrg``: ``batch["app_img"]`` is its appearance input where the batch brings
+        one, as ``lib.metrics.compute_ssim`` decides."""
+        from ..lib.metrics import evaluate_image_model
+        inplane_on = bool(self.config["data"].get("inplane_normalize", False)) and self.vunet.n_channels_x > 3
+        return evaluate_image_model(self.vunet, batches, classifier, crop, max_n_samples, splits, sampling, inplane_on,
+                                    inplane_parts if inplane_parts is not None else self.inplane_parts)
+
     def state_dict(self):
         return {"model": self.vunet.state_dict(), "optimizer": self.optimizer.state_dict()}
 

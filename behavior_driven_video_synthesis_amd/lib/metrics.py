@@ -15,7 +15,9 @@ features, the reference's class) and ``InceptionV3`` (logits), inference only, o
 third-party data this build cannot fetch (like VGG19's): ``sd`` is a torchvision ``inception_v3`` state dict the user supplies.
 The statistics -- feature mean and covariance, the matrix square root, traces, softmax and the KL divergences -- are float64
 on the host exactly as the reference computes them (numpy / scipy), pinned against the reference's own functions on synthetic
-features (tests/golden/g7_metrics.npz).
+features (tests/golden/g7_metrics.npz).  The Inception score's statistic also exists on the device (``inception_score_device``,
+``inception_score(..., on_device=True)``: csrc/inception_score.hip), and ``evaluate_image_model`` is the one-pass scoring of an
+image model -- SSIM and both Inception scores, optionally on person-box crops (person_crop.py) -- behind ``ShapePoseNet.evaluate``.
 """
 from __future__ import annotations
 
@@ -184,17 +186,44 @@ def inception_score_from_probs(preds: np.ndarray, splits: int = 1) -> Tuple[floa
     return float(np.mean(split_scores)), float(np.std(split_scores))
 
 
+def inception_score_device(logits: torch.Tensor, splits: int = 1) -> Tuple[float, float]:
+    """``inception_score_from_probs(softmax(logits), splits)`` on the device: logits [N, K] fp32 -> (mean, std) over the splits.
+    The float64 softmax, the split means, the KL divergences and the exponentials are ``vunet_inception_score``
+    (csrc/inception_score.hip); only the ``splits`` doubles are copied to the host."""
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        raise RuntimeError("inception_score_device needs device logits (hand-written gfx950 kernels; no CPU fallback)")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or int(splits) < 1:
+        raise ValueError(f"logits [N >= 1, K >= 1] and splits >= 1 expected, got {tuple(logits.shape)}, splits = {splits}")
+    x = logits.detach().to(torch.float32).contiguous()
+    n, k, splits = int(x.shape[0]), int(x.shape[1]), int(splits)
+    work = torch.empty(4 * n + splits * k, device=x.device, dtype=torch.float64)
+    scores = torch.empty(splits, device=x.device, dtype=torch.float64)
+    with torch.cuda.device(x.device):
+        ops._call("vunet_inception_score", ops._p(x), n, k, splits, ops._p(work), ops._p(scores), ops._stream())
+    s = scores.cpu().numpy()
+    return float(np.mean(s)), float(np.std(s))
+
+
 @torch.no_grad()
 def inception_score(imgs, classifier: Callable, batch_size: int = 32, resize: bool = False, splits: int = 1,
-                    device=None) -> Tuple[float, float]:
+                    device=None, boxes=None, valid=None, crop_size=None, sampling="reference",
+                    on_device: bool = False) -> Tuple[float, float]:
     """lib/metrics.py:362-415.  ``imgs``: tensor [N, 3, H, W] in [-1, 1] (or a dataset of 1-tuples of such images, as the
     reference takes); ``classifier(images) -> logits [n, K]`` stands for torchvision's pretrained ``inception_v3``
     (``models.imagenet_pretrained.InceptionV3`` with the user's weights, or any other callable).  ``resize``: bilinear up-sampling to 299 x 299 first (:385, ``nn.Upsample(size=(299, 299),
-    mode='bilinear')`` -- align_corners False)."""
+    mode='bilinear')`` -- align_corners False).
+
+    ``boxes`` [N, 4] int32 (+ ``valid`` [N], ``crop_size``, ``sampling``: person_crop.py): the score of the person-box crops of
+    ``imgs`` (run_inference's "IS on masks") without the crops being stored -- needs ``resize=True`` and a classifier that takes the
+    boxes (``InceptionV3``): crop and resize are then the classifier's first launch.  ``on_device``: the logits of all batches are
+    gathered in one device buffer and the statistic is one call at the end (``inception_score_device``) instead of one host copy
+    of the probabilities per batch."""
     if not torch.is_tensor(imgs):
         imgs = torch.stack([imgs[i][0] if isinstance(imgs[i], (tuple, list)) else imgs[i] for i in range(len(imgs))])
     n = imgs.shape[0]
     assert batch_size > 0 and n > batch_size
+    if boxes is not None or on_device:
+        return _inception_score_boxed(imgs, classifier, batch_size, resize, splits, device, boxes, valid, crop_size, sampling, on_device)
     preds = []
     for i in range(0, n, batch_size):
         x = imgs[i:i + batch_size]
@@ -204,3 +233,120 @@ def inception_score(imgs, classifier: Callable, batch_size: int = 32, resize: bo
             x = torch.nn.functional.interpolate(x.float(), size=(299, 299), mode="bilinear", align_corners=False)
         preds.append(torch.softmax(classifier(x).double(), dim=1).cpu().numpy())
     return inception_score_from_probs(np.concatenate(preds, axis=0), splits)
+
+
+def _inception_score_boxed(imgs, classifier, batch_size, resize, splits, device, boxes, valid, crop_size, sampling, on_device):
+    """``inception_score`` with boxes and / or the statistic on the device; batches as there."""
+    if boxes is not None and not resize:
+        raise ValueError("boxes are cropped inside the resize-to-299 launch: pass resize=True")
+    n = imgs.shape[0]
+    logits = None
+    preds = []
+    for i in range(0, n, batch_size):
+        x = imgs[i:i + batch_size]
+        if device is not None:
+            x = x.to(device)
+        if boxes is not None:
+            out = classifier(x.float(), boxes=boxes[i:i + batch_size].to(x.device),
+                             valid=None if valid is None else valid[i:i + batch_size].to(x.device), crop_size=crop_size,
+                             sampling=sampling, resize=True)
+        else:
+            if resize:
+                x = torch.nn.functional.interpolate(x.float(), size=(299, 299), mode="bilinear", align_corners=False)
+            out = classifier(x)
+        if on_device:
+            if logits is None:
+                logits = torch.empty(n, out.shape[1], device=out.device, dtype=torch.float32)
+            logits[i:i + out.shape[0]] = out
+        else:
+            preds.append(torch.softmax(out.double(), dim=1).cpu().numpy())
+    if on_device:
+        return inception_score_device(logits, splits)
+    return inception_score_from_probs(np.concatenate(preds, axis=0), splits)
+
+
+@torch.no_grad()
+def evaluate_image_model(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor]], classifier: Callable,
+                         crop: Optional[str] = None, max_n_samples: int = 8000, splits: int = 1, sampling: str = "reference",
+                         inplane_normalize: bool = False, inplane_parts=None) -> Dict[str, float]:
+    """The scores of an image model in one pass over ``batches`` -- ``compute_eval_metrics``
+    (experiments/shape_and_pose_net.py:666-755) with ``crop=None``, ``run_inference`` (:856-918) with ``crop="person"``.
+
+    Per batch, in eval mode under ``no_grad``: ``rec = model(timg, stickman)[0]`` and ``tr = model.transfer(app_img, stickman)``
+    (:693-703; ``app_img`` is ``batch["app_img"]`` where the batch brings one, else ``timg``; ``VunetOrg`` reconstructs from its
+    appearance input, as ``compute_ssim`` decides).  The SSIM is taken of the SAME ``rec`` -- the reference runs a second loader and a
+    second reconstruction for it (``compute_ssim``, :737-745); sums and the one division as in ``compute_ssim``.  Both image sets go
+    through ``classifier`` with the resize to 299 x 299 as its first launch; with ``crop="person"`` that launch also cuts every
+    image to the box of ``batch["keypoints"] * spatial_size`` (:880, :888-891; ``classifier`` an ``InceptionV3``: one fused launch,
+    any other callable: ``person_crop.crop_and_resize`` then ``inception_input``).  The logits stay on the device and the two
+    statistics are ``inception_score_device``: no image and no probability leaves the device.  An image without a valid keypoint
+    (``valid == 0``) is left out of both scores and counted in ``n_without_box``.  The loop ends as the reference's does:
+    before batch ``i`` where ``i * batch_size >= max_n_samples``.
+
+    -> {"ssim", "is_recon", "std_is_recon", "is_transfer", "std_is_transfer", "n", "n_without_box"}."""
+    from .. import person_crop
+    from ..models.inception import InceptionV3, inception_input
+    if crop not in (None, "person"):
+        raise ValueError(f"crop: None or 'person' expected, got {crop!r}")
+    person_crop._sampling(sampling)
+    fused = isinstance(classifier, InceptionV3)
+    was_training = model.training
+    model.eval()
+    total, count, n_seen, batch_size = None, 0, 0, None
+    rec_logits, tr_logits, valids = [], [], []
+    try:
+        for i, batch in enumerate(batches):
+            batch = _with_images(model, batch)
+            target = batch["pose_img"]
+            if batch_size is None:
+                batch_size = int(target.shape[0])
+            if i * batch_size >= max_n_samples:
+                break
+            size = int(target.shape[-1])
+            if "app_img" in batch and type(model).__name__ == "VunetOrg":   # as compute_ssim
+                timg = batch["app_img"]
+            else:
+                timg = _inplane_app(model, batch, inplane_parts) if inplane_normalize else target
+            app_img = batch.get("app_img", timg)
+            stickman = batch["stickman"]
+            rec = model(timg, stickman)[0]
+            tr = model.transfer(app_img, stickman)
+            vals = ssim(utils.scale_img(rec), utils.scale_img(target))
+            take = min(vals.numel(), max_n_samples - count)
+            if take > 0:
+                s = vals[:take].sum()
+                total = s if total is None else total + s
+                count += take
+            boxes = valid = None
+            if crop == "person":
+                if "keypoints" not in batch:
+                    raise KeyError('crop="person" cuts every image to the box of batch["keypoints"] * spatial_size: the batch has none')
+                kps = batch["keypoints"].to(rec.device).float() * float(model.spatial_size)   # :880
+                boxes, valid = person_crop.keypoint_boxes(kps)
+                valids.append(valid)
+            for img, sink in ((rec, rec_logits), (tr, tr_logits)):
+                img = img.detach().float()
+                if boxes is None:
+                    out = classifier(img, resize=True) if fused else classifier(inception_input(img))
+                elif fused:
+                    out = classifier(img, boxes=boxes, valid=valid, crop_size=size, sampling=sampling, resize=True)
+                else:
+                    out = classifier(inception_input(person_crop.crop_and_resize(img, boxes, size, valid, sampling)))
+                sink.append(out.float().clone())   # (an InceptionV3 returns a view into its arena)
+            n_seen += int(target.shape[0])
+    finally:
+        model.train(was_training)
+    if not rec_logits:
+        raise ValueError("evaluate: no batch")
+    rec_all, tr_all = torch.cat(rec_logits, dim=0), torch.cat(tr_logits, dim=0)
+    n_without_box = 0
+    if valids:
+        keep = torch.cat(valids, dim=0) != 0
+        n_without_box = int(keep.numel() - int(keep.sum()))
+        rec_all, tr_all = rec_all[keep], tr_all[keep]
+    if rec_all.shape[0] == 0:
+        raise ValueError("evaluate: no image with a valid keypoint")
+    is_rec, std_rec = inception_score_device(rec_all, splits)
+    is_tr, std_tr = inception_score_device(tr_all, splits)
+    return {"ssim": float(total / count) if count else float("nan"), "is_recon": is_rec, "std_is_recon": std_rec,
+            "is_transfer": is_tr, "std_is_transfer": std_tr, "n": n_seen, "n_without_box": n_without_box}

@@ -34,6 +34,16 @@ def scale_img(x):
     return torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
 
 
+def bounding_box_batch(kps_batch, img_batch, size_batch, spatial_size, sampling="reference"):
+    """lib/utils.py:530-558 with the reference's signature: every image of ``img_batch`` [N, Ch, H, W] cut to the bounding rectangle
+    of its valid keypoints (``kps_batch`` [N, J, 2 or 3] in pixels) and resized to ``spatial_size``.  ``size_batch`` is accepted and
+    unused, as there.  Two launches (person_crop.keypoint_boxes, person_crop.crop_and_resize); everything stays on the device.
+    An image without a valid keypoint -- where the reference's ``cv2.boundingRect`` of no points fails -- comes back as zeros."""
+    from .. import person_crop
+    boxes, valid = person_crop.keypoint_boxes(kps_batch.to(img_batch.device))
+    return person_crop.crop_and_resize(img_batch, boxes, spatial_size, valid, sampling)
+
+
 # ------------------------------------------------------------------------------------------------
 # pose -> "stickman" image (lib/utils.py:325-512 make_joint_img) on the GPU rasteriser
 # ------------------------------------------------------------------------------------------------

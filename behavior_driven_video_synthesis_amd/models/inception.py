@@ -168,7 +168,7 @@ class _Block(nn.Module):
 
 
 class _Step:
-    """One launch of a plan: ``fn`` in ("conv", "pool", "gap", "input"), its descriptor, arena offsets (floats; ``src`` None = the
+    """One launch of a plan: ``fn`` in ("conv", "pool", "gap", "input", "input_boxes"), its descriptor, arena offsets (floats; ``src`` None = the
     caller's tensor) and for a convolution the layer whose packed weights it reads."""
     __slots__ = ("fn", "desc", "src", "dst", "layer", "args", "label")
 
@@ -182,7 +182,8 @@ class Plan:
     the other, then a scratch region that the temporaries of each block share (a block's launches are in stream order, and its
     temporaries are dead when the next block starts)."""
 
-    def __init__(self, n: int, h: int, w: int, stem_pool: str = "max", resize_mode: Optional[str] = None, logits: bool = True):
+    def __init__(self, n: int, h: int, w: int, stem_pool: str = "max", resize_mode: Optional[str] = None, logits: bool = True,
+                 boxed: Optional[Tuple[int, int]] = None):
         if stem_pool not in ("max", "avg"):
             raise ValueError(f"stem_pool: 'max' or 'avg' expected, got {stem_pool!r}")
         self.n = int(n)
@@ -196,8 +197,14 @@ class Plan:
         src = None
         if resize_mode is not None:
             x0 = self._buf(3, SIZE, SIZE)
-            self.steps.append(_Step("input", None, None, x0, args=(n, int(h), int(w), INPUT_MODES[resize_mode]), label="input"))
+            if boxed is None:
+                self.steps.append(_Step("input", None, None, x0, args=(n, int(h), int(w), INPUT_MODES[resize_mode]), label="input"))
+            else:   # (crop size, sampling code): the person-box crop and the resize in one launch; boxes / valid come with the call
+                self.steps.append(_Step("input_boxes", None, None, x0, args=(n, int(h), int(w), int(boxed[0]), int(boxed[1]),
+                                                                             INPUT_MODES[resize_mode]), label="input_boxes"))
             src, h, w = x0, SIZE, SIZE
+        elif boxed is not None:
+            raise ValueError("a boxed plan crops inside the resize step: it needs a resize mode")
         if h < MIN_SIZE or w < MIN_SIZE:
             raise ValueError(f"Inception-v3 needs H, W >= {MIN_SIZE}, got {h} x {w}")
         cur = (src, 3, h, w)       # (buffer, channels, h, w)
@@ -443,20 +450,37 @@ class InceptionV3(nn.Module):
         return hit
 
     # ---- plans
-    def plan(self, n: int, h: int, w: int, resize_mode: Optional[str] = None) -> Plan:
-        return Plan(n, h, w, self.stem_pool, resize_mode)
+    def plan(self, n: int, h: int, w: int, resize_mode: Optional[str] = None, boxed: Optional[Tuple[int, int]] = None) -> Plan:
+        return Plan(n, h, w, self.stem_pool, resize_mode, boxed=boxed)
 
-    def _bound_plan(self, x, resize_mode):
+    def _bound_plan(self, x, resize_mode, boxed=None):
         n, _, h, w = x.shape
         key = (n, h, w, resize_mode, x.device.index, _stream().value)
+        if boxed is not None:   # a plan (and an arena) of its own: the plain plans keep their keys
+            key = key + ("boxes",) + tuple(boxed)
         rec = self._plans.get(key)
         if rec is None:
-            plan = self.plan(n, h, w, resize_mode)
+            plan = self.plan(n, h, w, resize_mode, boxed)
             arena = torch.empty(plan.arena_floats, device=x.device, dtype=torch.float32)
             rec = self._plans[key] = (plan, arena)
         return rec
 
-    def _run(self, x, resize_mode=None, upto_features=False, on_step=None):
+    def _boxed(self, x, resize_mode, boxes, valid, crop_size, sampling):
+        """The checked box arguments of a call: None without boxes, else ((crop size, sampling code), boxes, valid)."""
+        if boxes is None:
+            if valid is not None or crop_size is not None:
+                raise ValueError("valid / crop_size come with boxes")
+            return None
+        from .. import person_crop
+        if resize_mode is None:
+            raise ValueError("boxes are cropped inside the resize-to-299 launch: pass resize=True")
+        if crop_size is None or int(crop_size) < 2:
+            raise ValueError(f"boxes need crop_size >= 2 (the side the reference resizes the crop to), got {crop_size}")
+        boxes, valid = person_crop._boxes_device(x, boxes, valid)
+        return (int(crop_size), person_crop._sampling(sampling)), boxes, valid
+
+    def _run(self, x, resize_mode=None, upto_features=False, on_step=None, boxes=None, valid=None, crop_size=None,
+             sampling="reference"):
         if not (torch.is_tensor(x) and x.is_cuda):
             raise RuntimeError("InceptionV3 needs device tensors (hand-written gfx950 kernels; no CPU fallback)")
         if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
@@ -464,8 +488,9 @@ class InceptionV3(nn.Module):
         if any(p.device != x.device for p in (self.fc.weight, self.Conv2d_1a_3x3.conv.weight)):
             raise RuntimeError("InceptionV3 and its input are on different devices (model.cuda() first)")
         x = x.contiguous()
+        boxed = self._boxed(x, resize_mode, boxes, valid, crop_size, sampling)
         with torch.cuda.device(x.device):
-            plan, arena = self._bound_plan(x, resize_mode)
+            plan, arena = self._bound_plan(x, resize_mode, None if boxed is None else boxed[0])
             base, stream = arena.data_ptr(), _stream()
 
             def at(off):
@@ -482,8 +507,12 @@ class InceptionV3(nn.Module):
                     _call("vunet_pool2d", ctypes.byref(st.desc), at(st.src), at(st.dst), stream)
                 elif st.fn == "gap":
                     _call("vunet_global_avgpool", at(st.src), at(st.dst), *st.args, stream)
-                else:
+                elif st.fn == "input":
                     _call("vunet_inception_input", at(st.src), at(st.dst), *st.args, stream)
+                else:
+                    n_, h_, w_, size_, smp_, mode_ = st.args
+                    _call("vunet_inception_input_boxes", at(st.src), n_, h_, w_, _p(boxed[1]), _p(boxed[2]), size_, smp_, mode_,
+                          at(st.dst), stream)
                 if on_step is not None:
                     on_step(st, True)
         n = plan.n
@@ -493,12 +522,17 @@ class InceptionV3(nn.Module):
         return arena[plan.logits_off: plan.logits_off + n * N_CLASSES].view(n, N_CLASSES)
 
     @torch.no_grad()
-    def features(self, x):
-        return self._run(x, upto_features=True)
+    def features(self, x, boxes=None, valid=None, crop_size=None, sampling="reference", resize=False):
+        return self._run(x, "none" if resize else None, upto_features=True, boxes=boxes, valid=valid, crop_size=crop_size,
+                         sampling=sampling)
 
     @torch.no_grad()
-    def forward(self, x):
-        return self._run(x)
+    def forward(self, x, boxes=None, valid=None, crop_size=None, sampling="reference", resize=False):
+        """``resize``: the bilinear resize to 299 x 299 first (``nn.Upsample``, align_corners False: lib/metrics.py:385).  ``boxes``
+        [N, 4] int32 (+ ``valid``, ``crop_size``, ``sampling``: person_crop.py) with ``resize=True``: every image is cut to its box,
+        resized to ``crop_size`` and then to 299 in that same first launch -- bit-identical to
+        ``forward(inception_input(person_crop.crop_and_resize(x, boxes, crop_size, valid, sampling)))``."""
+        return self._run(x, "none" if resize else None, boxes=boxes, valid=valid, crop_size=crop_size, sampling=sampling)
 
 
 class FIDInceptionModel(InceptionV3):
@@ -512,8 +546,8 @@ class FIDInceptionModel(InceptionV3):
         super().__init__(state_dict, transform_input=False, stem_pool="avg", seed=seed)
 
     @torch.no_grad()
-    def forward(self, x):
-        return self._run(x, resize_mode="fid", upto_features=True)
+    def forward(self, x, boxes=None, valid=None, crop_size=None, sampling="reference"):
+        return self._run(x, resize_mode="fid", upto_features=True, boxes=boxes, valid=valid, crop_size=crop_size, sampling=sampling)
 
     features = forward
 

@@ -33,6 +33,14 @@
  *                         1  v (std_c / 0.5) + (mean_c - 0.5) / 0.5                (torchvision's transform_input)
  *                         2  (clamp((v + 1) / 2, 0, 1) - mean_c) / std_c            (FIDInceptionModel)
  *                       mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225).  Evaluated in float64 and rounded once.
+ * vunet_inception_score logits [N][K] fp32 -> scores [splits] float64 (csrc/inception_score.hip): lib/metrics.py:403-415 with
+ *                       scipy.stats.entropy(pk, qk), in float64.  Per row p = softmax by log-sum-exp (max, sum exp(l - max)).
+ *                       Split k takes the rows k (N / splits) .. (k + 1) (N / splits) - 1 (integer division; the tail rows belong
+ *                       to no split, as in the reference); q = the column mean of its rows; both vectors are renormalised to
+ *                       sum 1; KL_i = sum p log(p / q), a term with p == 0 contributing 0; scores[k] = exp(mean_i KL_i).  A split
+ *                       without rows (splits > N) scores NaN, the reference's mean of nothing.  `work`: caller-owned scratch of
+ *                       4 N + splits K doubles.  Four launches; every sum in a fixed order (strided partial sums, one tree: two
+ *                       stages).  splits <= 65535.
  *
  * VUNET_ERR_ARG: a NULL pointer (bias excepted), a size < 1, an inconsistent Ho / Wo, a slice outside its tensor, a packing
  * that is not padded as stated, a tensor of 2^31 elements or more, an unknown mode / tile.
@@ -75,6 +83,8 @@ int vunet_pool2d(const vunet_pool2d_desc* d, const float* x, float* y, void* str
 int vunet_global_avgpool(const float* x, float* y, int64_t NC, int32_t HW, void* stream);
 
 int vunet_inception_input(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t mode, void* stream);
+
+int vunet_inception_score(const float* logits, int32_t N, int32_t K, int32_t splits, double* work, double* scores, void* stream);
 
 #ifdef __cplusplus
 }
