@@ -75,10 +75,11 @@ def save_ckpt(directory: str, key: str, iteration: int, trainer, n_saved: int = 
     return path
 
 
-def save_metric_ckpt(directory: str, trainer, epoch: int, ssim: float, is_rec: float) -> Tuple[str, str]:
+def save_metric_ckpt(directory: str, trainer, epoch: int, ssim: float, is_rec: float, fid: Optional[float] = None) -> Tuple[str, str]:
     """The metric-tagged checkpoint of ``compute_eval_metrics`` (experiments/shape_and_pose_net.py:757-773): the model's state
     dict as ``<directory>/epoch_ckpts/model@e{epoch}@ssim={ssim}-is={is_rec}.pth`` and the optimiser's as ``opt@e...pth`` -- two
-    plain state dicts, not the ``{"model", "optimizer"}`` layout of ``save_ckpt``.  -> (model path, optimiser path)."""
+    plain state dicts, not the ``{"model", "optimizer"}`` layout of ``save_ckpt``.  With ``fid`` the names are those of
+    experiments/vunet.py:624-637, ``model@e{epoch}@ssim={ssim}-fid={fid}.pth`` / ``opt@...``.  -> (model path, optimiser path)."""
     save_dir = os.path.join(directory, "epoch_ckpts")
     os.makedirs(save_dir, exist_ok=True)
     sd = trainer.state_dict()
@@ -91,7 +92,7 @@ def save_metric_ckpt(directory: str, trainer, epoch: int, ssim: float, is_rec: f
         if isinstance(o, (list, tuple)):
             return type(o)(host(v) for v in o)
         return o
-    tag = f"e{epoch}@ssim={ssim}-is={is_rec}.pth"
+    tag = f"e{epoch}@ssim={ssim}-is={is_rec}.pth" if fid is None else f"e{epoch}@ssim={ssim}-fid={fid}.pth"
     model_path, opt_path = os.path.join(save_dir, "model@" + tag), os.path.join(save_dir, "opt@" + tag)
     torch.save(host(sd["model"]), model_path)
     torch.save(host(sd["optimizer"]), opt_path)

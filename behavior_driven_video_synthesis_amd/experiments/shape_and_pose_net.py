@@ -543,16 +543,19 @@ class ShapePoseNet:
 
     # ---- compute_eval_metrics (:666-755) / run_inference's scores (:856-918)
     def evaluate(self, batches, classifier, crop=None, max_n_samples: int = 8000, splits: int = 1, sampling: str = "reference",
-                 inplane_parts=None) -> dict:
+                 inplane_parts=None, *, fid_extractor=None, gt_features=None) -> dict:
         """SSIM and the Inception scores of reconstructions and transfers in one pass over ``batches``
         (lib.metrics.evaluate_image_model): ``crop=None`` is ``compute_eval_metrics``, ``crop="person"`` is ``run_inference`` -- every
         image cut to the box of ``batch["keypoints"] * spatial_size`` first.  ``classifier``: an ``InceptionV3`` (or any callable
         mapping a 299 x 299 batch to logits).  The model's ``training`` flag is restored.  ``experiments.checkpoint.save_metric_ckpt``
-        writes the metric-tagged checkpoint the reference saves beside these numbers (:757-773)."""
+        writes the metric-tagged checkpoint the reference saves beside these numbers (:757-773).  ``fid_extractor`` (a
+        ``FIDInceptionModel``; + ``gt_features``, the cached ground-truth features): the result also carries ``"fid"``, computed on
+        the device from the same reconstructions."""
         from ..lib.metrics import evaluate_image_model
         inplane_on = bool(self.config["data"].get("inplane_normalize", False)) and self.vunet.n_channels_x > 3
         return evaluate_image_model(self.vunet, batches, classifier, crop, max_n_samples, splits, sampling, inplane_on,
-                                    inplane_parts if inplane_parts is not None else self.inplane_parts)
+                                    inplane_parts if inplane_parts is not None else self.inplane_parts,
+                                    fid_extractor=fid_extractor, gt_features=gt_features)
 
     # ---- checkpoint layout of :471-494: {"model", "optimizer"} (the "reg_ckpt" file); the regressor and its optimiser
     # form the reference's second file ("regressor"), here the "regressor" entry of the same dict

@@ -142,13 +142,15 @@ class Vunet:
         return run_probe(regressor, encode, batches, n_epochs, lr, eps)
 
     def evaluate(self, batches, classifier, crop=None, max_n_samples: int = 8000, splits: int = 1, sampling: str = "reference",
-                 inplane_parts=None) -> dict:
+                 inplane_parts=None, *, fid_extractor=None, gt_features=None) -> dict:
         """As ``ShapePoseNet.evaluate``, over ``VunetOrg``: ``batch["app_img"]`` is its appearance input where the batch brings
-        one, as ``lib.metrics.compute_ssim`` decides."""
+        one, as ``lib.metrics.compute_ssim`` decides.  With ``fid_extractor`` the result carries the ``"fid"`` that
+        experiments/vunet.py:604-636 logs and names its metric checkpoints by (``checkpoint.save_metric_ckpt(..., fid=...)``)."""
         from ..lib.metrics import evaluate_image_model
         inplane_on = bool(self.config["data"].get("inplane_normalize", False)) and self.vunet.n_channels_x > 3
         return evaluate_image_model(self.vunet, batches, classifier, crop, max_n_samples, splits, sampling, inplane_on,
-                                    inplane_parts if inplane_parts is not None else self.inplane_parts)
+                                    inplane_parts if inplane_parts is not None else self.inplane_parts,
+                                    fid_extractor=fid_extractor, gt_features=gt_features)
 
     def state_dict(self):
         return {"model": self.vunet.state_dict(), "optimizer": self.optimizer.state_dict()}

@@ -18,6 +18,9 @@ on the host exactly as the reference computes them (numpy / scipy), pinned again
 features (tests/golden/g7_metrics.npz).  The Inception score's statistic also exists on the device (``inception_score_device``,
 ``inception_score(..., on_device=True)``: csrc/inception_score.hip), and ``evaluate_image_model`` is the one-pass scoring of an
 image model -- SSIM and both Inception scores, optionally on person-box crops (person_crop.py) -- behind ``ShapePoseNet.evaluate``.
+The FID statistic exists on the device too (``fid_from_features_device``, ``compute_fid(..., on_device=True)``,
+``evaluate_image_model(..., fid_extractor=...)``: fid_device.py, csrc/fid.hip -- float64 matrix-core products and a polar iteration
+in place of ``sqrtm``); the default route stays the host's.
 """
 from __future__ import annotations
 
@@ -142,15 +145,55 @@ def fid_from_features(gt_features: np.ndarray, gen_features: np.ndarray) -> floa
     return _calculate_fid(np.mean(gt, axis=0), np.cov(gt, rowvar=False), np.mean(gen, axis=0), np.cov(gen, rowvar=False))
 
 
+def fid_from_features_device(gt_features, gen_features, tol: float = 1e-14, max_iter: int = 100) -> float:
+    """``fid_from_features`` on the device (fid_device.py): feature sets [N >= 2, D], fp32 or float64 device tensors (host arrays are
+    uploaded); mean, covariance, traces and ``tr sqrtm(S1 S2)`` by float64 matrix products and a polar iteration, no ``sqrtm``."""
+    from ..fid_device import fid_device
+    return float(fid_device(gt_features, gen_features, tol, max_iter).fid)
+
+
+def _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_samples, inplane_normalize, inplane_parts) -> float:
+    """``compute_fid`` with the features gathered on the device: one clone per batch (an ``InceptionV3`` returns views into its
+    arena), no host copy, ``gt_features`` uploaded once."""
+    def _keep(f):
+        f = f.detach()
+        return (f if f.dtype == torch.float64 else f.float()).clone()
+    was_training = model.training
+    model.eval()
+    gts, gens, n = [], [], 0
+    try:
+        for batch in batches:
+            batch = _with_images(model, batch)
+            target = batch["pose_img"]
+            if "app_img" in batch and type(model).__name__ == "VunetOrg":
+                app = batch["app_img"]
+            else:
+                app = _inplane_app(model, batch, inplane_parts) if inplane_normalize else target
+            if gt_features is None:
+                gts.append(_keep(feature_extractor(target)))
+            gens.append(_keep(feature_extractor(model(app, batch["stickman"])[0])))
+            n += target.shape[0]
+            if n >= max_n_samples:
+                break
+    finally:
+        model.train(was_training)
+    gen = torch.cat(gens, dim=0)
+    return fid_from_features_device(gt_features if gt_features is not None else torch.cat(gts, dim=0), gen)
+
+
 @torch.no_grad()
 def compute_fid(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor]], feature_extractor: Callable,
                 gt_features: Optional[np.ndarray] = None, max_n_samples: int = 8000,
-                inplane_normalize: bool = False, inplane_parts=None) -> float:
+                inplane_normalize: bool = False, inplane_parts=None, on_device: bool = False) -> float:
     """lib/metrics.py:119-282 on an iterable of batches.  ``feature_extractor(images) -> [N, D]`` stands for the
     reference's ``FIDInceptionModel`` (``models.imagenet_pretrained.FIDInceptionModel`` with the user's torchvision weights, or any
     other callable); ground-truth features are
     computed from ``batch["pose_img"]`` unless ``gt_features`` (the reference's cached ``<dataset>-fid-features.npy``) is
-    given; generated features come from the reconstructions ``model(app, stickman)[0]`` (:243-258)."""
+    given; generated features come from the reconstructions ``model(app, stickman)[0]`` (:243-258).  ``on_device``: the features
+    of all batches stay in device buffers and the statistic is ``fid_from_features_device`` -- no per-batch host copy, no
+    ``np.cov``, no ``scipy.linalg.sqrtm``."""
+    if on_device:
+        return _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_samples, inplane_normalize, inplane_parts)
     was_training = model.training
     model.eval()
     gts, gens, n = [], [], 0
@@ -268,7 +311,8 @@ def _inception_score_boxed(imgs, classifier, batch_size, resize, splits, device,
 @torch.no_grad()
 def evaluate_image_model(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor]], classifier: Callable,
                          crop: Optional[str] = None, max_n_samples: int = 8000, splits: int = 1, sampling: str = "reference",
-                         inplane_normalize: bool = False, inplane_parts=None) -> Dict[str, float]:
+                         inplane_normalize: bool = False, inplane_parts=None, *, fid_extractor: Optional[Callable] = None,
+                         gt_features=None) -> Dict[str, float]:
     """The scores of an image model in one pass over ``batches`` -- ``compute_eval_metrics``
     (experiments/shape_and_pose_net.py:666-755) with ``crop=None``, ``run_inference`` (:856-918) with ``crop="person"``.
 
@@ -283,7 +327,12 @@ def evaluate_image_model(model: torch.nn.Module, batches: Iterable[Dict[str, tor
     (``valid == 0``) is left out of both scores and counted in ``n_without_box``.  The loop ends as the reference's does:
     before batch ``i`` where ``i * batch_size >= max_n_samples``.
 
-    -> {"ssim", "is_recon", "std_is_recon", "is_transfer", "std_is_transfer", "n", "n_without_box"}."""
+    ``fid_extractor`` (keyword only; a ``FIDInceptionModel`` or any callable images -> [n, D]): the same ``rec``, uncropped, also
+    goes through it, as ``compute_fid`` feeds it, and the result gains ``"fid"`` -- ``fid_from_features_device`` of the gathered
+    features against those of ``target`` (or against ``gt_features``, the reference's cached feature file, uploaded once): the
+    FID that experiments/vunet.py:604-636 logs beside the SSIM.  Without an extractor nothing changes.
+
+    -> {"ssim", "is_recon", "std_is_recon", "is_transfer", "std_is_transfer", "n", "n_without_box"} (+ "fid")."""
     from .. import person_crop
     from ..models.inception import InceptionV3, inception_input
     if crop not in (None, "person"):
@@ -294,6 +343,11 @@ def evaluate_image_model(model: torch.nn.Module, batches: Iterable[Dict[str, tor
     model.eval()
     total, count, n_seen, batch_size = None, 0, 0, None
     rec_logits, tr_logits, valids = [], [], []
+    fid_gt, fid_gen = [], []
+
+    def _keep(f):   # (an InceptionV3 returns a view into its arena)
+        f = f.detach()
+        return (f if f.dtype == torch.float64 else f.float()).clone()
     try:
         for i, batch in enumerate(batches):
             batch = _with_images(model, batch)
@@ -333,6 +387,10 @@ def evaluate_image_model(model: torch.nn.Module, batches: Iterable[Dict[str, tor
                 else:
                     out = classifier(inception_input(person_crop.crop_and_resize(img, boxes, size, valid, sampling)))
                 sink.append(out.float().clone())   # (an InceptionV3 returns a view into its arena)
+            if fid_extractor is not None:
+                if gt_features is None:
+                    fid_gt.append(_keep(fid_extractor(target)))
+                fid_gen.append(_keep(fid_extractor(rec)))
             n_seen += int(target.shape[0])
     finally:
         model.train(was_training)
@@ -348,5 +406,9 @@ def evaluate_image_model(model: torch.nn.Module, batches: Iterable[Dict[str, tor
         raise ValueError("evaluate: no image with a valid keypoint")
     is_rec, std_rec = inception_score_device(rec_all, splits)
     is_tr, std_tr = inception_score_device(tr_all, splits)
-    return {"ssim": float(total / count) if count else float("nan"), "is_recon": is_rec, "std_is_recon": std_rec,
-            "is_transfer": is_tr, "std_is_transfer": std_tr, "n": n_seen, "n_without_box": n_without_box}
+    res = {"ssim": float(total / count) if count else float("nan"), "is_recon": is_rec, "std_is_recon": std_rec,
+           "is_transfer": is_tr, "std_is_transfer": std_tr, "n": n_seen, "n_without_box": n_without_box}
+    if fid_extractor is not None:
+        res["fid"] = fid_from_features_device(gt_features if gt_features is not None else torch.cat(fid_gt, dim=0),
+                                              torch.cat(fid_gen, dim=0))
+    return res
