@@ -26,7 +26,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from .. import image_input, inplane, ops
+from .. import appearance_aug, image_input, inplane, ops
 from ..lib.losses import compute_kl_with_prior, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
 from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, p2_precision, vgg19
@@ -53,6 +53,15 @@ DEFAULT_CONFIG = {
                  "gan": {"enabled": False, "weight": 1.0, "pd_scales": 3, "grad_pen": False, "lambda_gp": 10,
                          "grad_weighting": False, "lr": 0.0002, "save_intervall": 10000}},
 }
+
+
+def _configured_aug(data: Dict):
+    """The ``appearance_aug.AppearanceAug`` of a ``data`` config section (``appearance_aug``: "deepfashion" | "market";
+    ``appearance_aug_crop``: Market's centre crop, 128 where absent), None where the key is absent."""
+    kind = data.get("appearance_aug")
+    if kind is None:
+        return None
+    return appearance_aug.AppearanceAug(kind, crop=data.get("appearance_aug_crop", 128), size=data["spatial_size"])
 
 
 class ShapePoseNet:
@@ -82,6 +91,9 @@ class ShapePoseNet:
                 raise ValueError(f"{self.inplane_parts!r} makes {3 * self.inplane_parts.n_parts} channels, the model takes {n_channels_x}")
             if self.device.type == "cuda":
                 self.inplane_parts.tables(self.device)
+        # ``data.appearance_aug`` ("deepfashion" | "market" | absent): the random appearance augmentation of a batch that brings
+        # ``pose_img_u8`` + ``pose_img_aug`` runs on the GPU (appearance_aug.batch_appearance); the draws stay with the caller
+        self.appearance_aug = _configured_aug(data)
         ops.enable_wgrad_streams(overlap)        # weight gradients beside the data-gradient chain (process-wide switch)
         self.vgg = vgg19(pretrained=True, weights_path=vgg_weights_path, width_div=vgg_width_div, seed=vgg_seed,
                          synthetic=vgg_synthetic).to(self.device)
@@ -390,6 +402,11 @@ class ShapePoseNet:
         tr = self.config["training"]
         # ``pose_img`` from raw frames where the batch brings ``pose_img_u8`` instead (three launches, recorded with the step)
         made = image_input.batch_images(batch, self.config["data"]["spatial_size"])
+        if made:
+            batch = {**batch, **made}
+        # ``pose_img_inplane`` from ``pose_img_u8`` + ``pose_img_aug`` (the random appearance augmentation: one launch, plus the
+        # resize's three where the window is not the output size; recorded with the step, the matrices one more static input)
+        made = appearance_aug.batch_appearance(batch, self.config["data"]["spatial_size"], self.appearance_aug)
         if made:
             batch = {**batch, **made}
         target_img = batch["pose_img"]

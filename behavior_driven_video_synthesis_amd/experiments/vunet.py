@@ -15,7 +15,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from .. import image_input, inplane, ops
+from .. import appearance_aug, image_input, inplane, ops
 from ..lib.losses import compute_kl_loss, vgg_loss
 from ..lib.utils import get_member, linear_var, n_parameters
 from ..models.imagenet_pretrained import PerceptualVGG, apply_config_precision, vgg19
@@ -56,6 +56,9 @@ class Vunet:
         self.inplane_parts = inplane.configured_parts(data) if n_channels_x > 3 else None
         if self.inplane_parts is not None and n_channels_x != 3 * self.inplane_parts.n_parts:
             raise ValueError(f"{self.inplane_parts!r} makes {3 * self.inplane_parts.n_parts} channels, the model takes {n_channels_x}")
+        # as ShapePoseNet: ``data.appearance_aug`` names the random appearance augmentation run on the GPU
+        self.appearance_aug = None if data.get("appearance_aug") is None else appearance_aug.AppearanceAug(
+            data["appearance_aug"], crop=data.get("appearance_aug_crop", 128), size=data["spatial_size"])
         ops.enable_wgrad_streams(overlap)
         self.vgg = vgg19(pretrained=True, weights_path=vgg_weights_path, width_div=vgg_width_div, seed=vgg_seed,
                          synthetic=vgg_synthetic).to(self.device)
@@ -95,6 +98,9 @@ class Vunet:
         self.optimizer.zero_grad()
         data = self.config["data"]
         made = image_input.batch_images(batch, data["spatial_size"])   # ``pose_img`` from ``pose_img_u8`` (+ ``pose_img_geom``)
+        if made:
+            batch = {**batch, **made}
+        made = appearance_aug.batch_appearance(batch, data["spatial_size"], self.appearance_aug)   # ``pose_img_inplane`` from ``pose_img_aug``
         if made:
             batch = {**batch, **made}
         app_img = batch.get("pose_img_inplane", batch["pose_img"])

@@ -209,7 +209,8 @@ def bounding_box(kps, frame_hw, relax: float = 0.1) -> np.ndarray:
 def to_device(batch: dict, device) -> dict:
     """``batch`` with its raw-frame inputs (``K_u8``, ``K_geom`` for K in ``pose_img``, ``app_img``) as device tensors, host
     geometry checked first -- what a step that is recorded into a hipGraph needs (its inputs are static device buffers).  The
-    batch itself where it brings none of them or they are on the device already."""
+    batch itself where it brings none of them or they are on the device already.  ``pose_img_aug`` / ``pose_img_hw`` (the
+    matrices and frame sizes of appearance_aug.batch_appearance) are staged alike."""
     out = None
     for key in KEYS:
         u8 = batch.get(key + "_u8")
@@ -226,7 +227,11 @@ def to_device(batch: dict, device) -> dict:
         if host_geom:
             n, hmax, wmax = (int(v) for v in out[key + "_u8"].shape[:3])
             out[key + "_geom"] = check_geom(geom, n, hmax, wmax).to(device, non_blocking=True)
-    return batch if out is None else out
+    batch = batch if out is None else out
+    if "pose_img_aug" in batch:   # the appearance augmentation's matrices and frame sizes (appearance_aug.batch_appearance)
+        from . import appearance_aug
+        batch = appearance_aug.to_device(batch, device)
+    return batch
 
 
 def batch_images(batch: dict, size: int) -> Dict[str, torch.Tensor]:
