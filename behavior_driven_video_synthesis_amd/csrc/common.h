@@ -27,6 +27,21 @@ __device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : (__expf(x
 __device__ __forceinline__ float elu_grad_f(float x) { return x > 0.f ? 1.f : __expf(x); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }   // (expf, not __expf: the sequence kernels)
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// 16 bytes touched once per kernel by one workgroup: streamed past the caches' retention (non-temporal)
+typedef float nt_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned nt_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 nt_load4(const float* p) {
+  const nt_f4 t = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(p));
+  return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ uint4 nt_load4(const uint16_t* p) {   // (eight bf16)
+  const nt_u4 t = __builtin_nontemporal_load(reinterpret_cast<const nt_u4*>(p));
+  return make_uint4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ void nt_store4(float* p, const float4& v) {
+  nt_f4 t = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(t, reinterpret_cast<nt_f4*>(p));
+}
 
 // input-side activation (+ optional dropout keep/scale) used as the conv prologue
 struct InAct {

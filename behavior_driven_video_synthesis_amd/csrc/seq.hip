@@ -30,18 +30,12 @@
 #include "common.h"
 #include "../../include/vunet_seq_train.h"
 #include "../../include/vunet_seq_tiled.h"
+#include "seq_linear_args.h"
 
 namespace {
 
-constexpr int SEQ_MAX_NB = 4;   // batch tiles of 16: B <= 64
-
-struct SeqLinearArgs {
-  const float* w[2];      // [M][K] row-major, M % 16 == 0, K % 32 == 0 (zero padded)
-  const float* x;         // [nets_in][Bp][ldx]
-  const float* bias[2];   // [M] (NULL: none)
-  float* y;               // [nets][Bp][M]
-  int M, K, Bp, ldx, act[2], shared_in;
-  int S;                  // > 1: K split over grid.y workgroups, y = [nets][S][Bp][M] RAW partial slabs (no bias, no activation)
+// seq_linear_args.h's argument block and, behind it, what the LSTM step and training add
+struct SeqLinearArgs : SeqLinearBaseArgs<float> {
   // LSTM form (template flag): the rows are gate-interleaved -- row 4 j + q is gate q (i, f, g, o) of hidden unit j -- so the
   // lane that holds rows 4 kq .. 4 kq + 3 of batch row n holds all four gates of one unit and finishes the cell in registers
   const float* c_in;      // [Bp][H]
@@ -57,33 +51,25 @@ struct SeqLinearArgs {
   int H, hoff, n, B;
 };
 
-__device__ __forceinline__ float seq_act(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.01f * v);   // nn.LeakyReLU() default slope 0.01 (lib/modules.py:244)
-  if (act == 2) return tanhf(v);              // the scale nets' head (lib/modules.py:252-253)
-  if (act == 3) return fmaxf(v, 0.f);         // nn.ReLU: the adversarial pose regressor (models/pose_behavior_rnn.py:47-62)
-  return v;
-}
-
 // The weight stream is the cost and a wave has few chunks (2 - 8), so what matters is bytes in flight: a group of U chunks
 // issues all of its loads (weights of RT tiles, the operand of NB batch tiles) before the first MFMA.  The scheduling barrier
 // keeps it that way: without it the scheduler interleaves loads and uses to save registers and keeps ~7 loads in flight.
-typedef float seq_f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 seq_w_load(const float* p) {
-  const seq_f4v t = __builtin_nontemporal_load(reinterpret_cast<const seq_f4v*>(p));
-  return make_float4(t.x, t.y, t.z, t.w);
-}
+// 16-row weight tiles per wave.  ONE: 32-row tiles halve the operand traffic per weight byte but leave half the CUs without a
+// workgroup at every layer size of the reference configuration.  (A constant, not a parameter; the loops over it stay written
+// out: without them the compiler merges the epilogue's stores and allocates registers differently in most forms.)
+constexpr int RT = 1;
 
 // LAY (include/vunet_seq_tiled.h): bit 0 -- the weights are tile-major images, bit 1 -- the operand is: a chunk is then 2 KB
 // contiguous, [half][lane] float4, and each of a wave's loads covers 1 KB contiguous.
-template <int NB, int RT, int U>
+template <int NB, int U>
 struct SeqGroupRegs {
   float4 wv[RT][U][2], xv[NB][U][2];
 };
 
 // the loads of a group of U chunks (c0, c0 + WAVES, ...): weights of RT tiles, the operand of NB batch tiles
-template <int NB, int RT, int U, int WAVES, int LAY>
+template <int NB, int U, int WAVES, int LAY>
 __device__ __forceinline__ void seq_group_load(const SeqLinearArgs& a, const float* __restrict__ w, const float* __restrict__ x, int c0,
-                                               SeqGroupRegs<NB, RT, U>& r) {
+                                               SeqGroupRegs<NB, U>& r) {
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -92,10 +78,10 @@ __device__ __forceinline__ void seq_group_load(const SeqLinearArgs& a, const flo
         const float* wp = w + (size_t)rt * 16 * a.K + 512 * (c0 + WAVES * u);
         r.wv[rt][u][0] = *reinterpret_cast<const float4*>(wp);
         r.wv[rt][u][1] = *reinterpret_cast<const float4*>(wp + 256);
-      } else if constexpr (LAY & 1) {   // (read once per pass by this one workgroup: streamed past the caches' retention, seq_w_load)
+      } else if constexpr (LAY & 1) {   // (read once per pass by this one workgroup: streamed past the caches' retention)
         const float* wp = w + (size_t)rt * 16 * a.K + 512 * (c0 + WAVES * u);
-        r.wv[rt][u][0] = seq_w_load(wp);
-        r.wv[rt][u][1] = seq_w_load(wp + 256);
+        r.wv[rt][u][0] = nt_load4(wp);
+        r.wv[rt][u][1] = nt_load4(wp + 256);
       } else {
         // (row-major weights: the parameters themselves when a flow trains -- the input-gradient chain and the update sweep read
         //  them again within the same block's 168 MB, from the Infinity Cache: default policy.  Non-temporal here: 7.21 -> 7.40 ms
@@ -136,8 +122,8 @@ __device__ __forceinline__ void seq_group_load(const SeqLinearArgs& a, const flo
 }
 
 // ... and its matrix steps: chunk by chunk, weight tile by weight tile, batch tile by batch tile, k ascending
-template <int NB, int RT, int U>
-__device__ __forceinline__ void seq_group_mfma(const SeqGroupRegs<NB, RT, U>& r, f32x4 (&acc)[RT][NB]) {
+template <int NB, int U>
+__device__ __forceinline__ void seq_group_mfma(const SeqGroupRegs<NB, U>& r, f32x4 (&acc)[RT][NB]) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -154,24 +140,22 @@ __device__ __forceinline__ void seq_group_mfma(const SeqGroupRegs<NB, RT, U>& r,
     }
 }
 
-template <int NB, int RT, int U, int WAVES, int LAY>
+template <int NB, int U, int WAVES, int LAY>
 __device__ __forceinline__ void seq_linear_group(const SeqLinearArgs& a, const float* __restrict__ w, const float* __restrict__ x, int c0,
                                                  f32x4 (&acc)[RT][NB]) {
-  SeqGroupRegs<NB, RT, U> r;
-  seq_group_load<NB, RT, U, WAVES, LAY>(a, w, x, c0, r);
+  SeqGroupRegs<NB, U> r;
+  seq_group_load<NB, U, WAVES, LAY>(a, w, x, c0, r);
   __builtin_amdgcn_sched_barrier(0);
-  seq_group_mfma<NB, RT, U>(r, acc);
+  seq_group_mfma<NB, U>(r, acc);
 }
 
 // grid (M / 16, S, nets), 64 WAVES threads.  Lane l of a wave: i = l & 15 (weight row / batch row), kq = l >> 4; in a K chunk of 32
 // it holds k = 8 kq .. 8 kq + 7 of its row -- the same k for the A (weights) and B (batch) operand of MFMA step j = 0..7.
 // D: lane holds batch row n = l & 15 of its tile, output rows 4 (l >> 4) + r of the weight tile.
-// RT (16-row weight tiles per wave): only 1 is instantiated -- 32-row tiles halve the operand traffic per weight byte but leave
-// half the CUs without a workgroup at every layer size of the reference configuration.
 // WAVES = 16 where K has >= 16 chunks, else 4.  Four waves with 16 chunks each and sixteen with 4 measured the same on the
 // 2048 x 2048 layers (12 us: the bound is what a CU pulls through its L1, not the number of round trips); sixteen are kept
 // because the batch tiles' epilogues then run on separate waves and the short layers request all their weights at once.
-template <int NB, int RT, int WAVES, bool LSTM = false, int LAY = 0>
+template <int NB, int WAVES, bool LSTM = false, int LAY = 0>
 __global__ __launch_bounds__(64 * WAVES) void seq_linear_kernel(SeqLinearArgs a) {
   __shared__ float4 red[WAVES][RT][NB][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -202,39 +186,39 @@ __global__ __launch_bounds__(64 * WAVES) void seq_linear_kernel(SeqLinearArgs a)
     // depth 2, any number of chunks (an odd count -- 34 chunks over four waves: 9, 9, 8, 8 -- keeps its last chunk in the ring)
     const int nw = c < nchunk ? (nchunk - c + WAVES - 1) / WAVES : 0;   // this wave's chunks
     if (nw > 0) {
-      SeqGroupRegs<NB, RT, 1> ra, rb;
-      seq_group_load<NB, RT, 1, WAVES, LAY>(a, w, x, c, ra);
+      SeqGroupRegs<NB, 1> ra, rb;
+      seq_group_load<NB, 1, WAVES, LAY>(a, w, x, c, ra);
       int k = 0;
       for (; k + 2 < nw; k += 2) {   // ra holds chunk k
-        seq_group_load<NB, RT, 1, WAVES, LAY>(a, w, x, c + WAVES * (k + 1), rb);
+        seq_group_load<NB, 1, WAVES, LAY>(a, w, x, c + WAVES * (k + 1), rb);
         __builtin_amdgcn_sched_barrier(0);
-        seq_group_mfma<NB, RT, 1>(ra, acc);
+        seq_group_mfma<NB, 1>(ra, acc);
         __builtin_amdgcn_sched_barrier(0);
-        seq_group_load<NB, RT, 1, WAVES, LAY>(a, w, x, c + WAVES * (k + 2), ra);
+        seq_group_load<NB, 1, WAVES, LAY>(a, w, x, c + WAVES * (k + 2), ra);
         __builtin_amdgcn_sched_barrier(0);
-        seq_group_mfma<NB, RT, 1>(rb, acc);
+        seq_group_mfma<NB, 1>(rb, acc);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (nw - k == 2) {
-        seq_group_load<NB, RT, 1, WAVES, LAY>(a, w, x, c + WAVES * (k + 1), rb);
+        seq_group_load<NB, 1, WAVES, LAY>(a, w, x, c + WAVES * (k + 1), rb);
         __builtin_amdgcn_sched_barrier(0);
-        seq_group_mfma<NB, RT, 1>(ra, acc);
+        seq_group_mfma<NB, 1>(ra, acc);
         __builtin_amdgcn_sched_barrier(0);
-        seq_group_mfma<NB, RT, 1>(rb, acc);
+        seq_group_mfma<NB, 1>(rb, acc);
       } else {
-        seq_group_mfma<NB, RT, 1>(ra, acc);
+        seq_group_mfma<NB, 1>(ra, acc);
       }
       c += WAVES * nw;
     }
   }
-  for (; c + WAVES * (UMAX - 1) < nchunk; c += WAVES * UMAX) seq_linear_group<NB, RT, UMAX, WAVES, LAY>(a, w, x, c, acc);
+  for (; c + WAVES * (UMAX - 1) < nchunk; c += WAVES * UMAX) seq_linear_group<NB, UMAX, WAVES, LAY>(a, w, x, c, acc);
   if constexpr (UMAX == 4)
     if (c + WAVES < nchunk) {
-      seq_linear_group<NB, RT, 2, WAVES, LAY>(a, w, x, c, acc);
+      seq_linear_group<NB, 2, WAVES, LAY>(a, w, x, c, acc);
       c += 2 * WAVES;
     }
   if constexpr (UMAX > 1)
-    for (; c < nchunk; c += WAVES) seq_linear_group<NB, RT, 1, WAVES, LAY>(a, w, x, c, acc);
+    for (; c < nchunk; c += WAVES) seq_linear_group<NB, 1, WAVES, LAY>(a, w, x, c, acc);
   // every wave's partial -> LDS; wave w < NB adds them in wave order for batch tile w and finishes that tile (the epilogues run
   // side by side: with tanh / the LSTM cell in them, one wave finishing four tiles was a 4 us tail)
 #pragma unroll
@@ -617,60 +601,16 @@ static int seq_linear_launch(const vunet_seq_linear_desc* d, int layout, const f
                              const float* bias0, const float* bias1, float* y, float* y2, void* stream) {
   if (!d || !w0 || !x || !y) return VUNET_ERR_ARG;
   if (layout < 0 || layout > 7 || layout == 1) return VUNET_ERR_UNSUPPORTED;   // (inference: 3 / 5 / 7; training: 2 / 4 / 6)
-  if (y2 && !(layout & 4)) return VUNET_ERR_ARG;
-  if ((layout & 4) && (d->S != 1 || d->M % 32)) return VUNET_ERR_ARG;
-  if (d->nets < 1 || d->nets > 2 || (d->nets == 2 && !w1)) return VUNET_ERR_ARG;
-  if (d->B < 1 || d->B > 16 * SEQ_MAX_NB || d->M < 16 || d->M % 16) return VUNET_ERR_ARG;
-  if (d->S < 1 || d->S > 8 || d->K < 32 || d->K % (32 * d->S) || d->ldx < d->K || d->ldx % 4) return VUNET_ERR_ARG;
-  if (d->act0 < 0 || d->act0 > 3 || d->act1 < 0 || d->act1 > 3) return VUNET_ERR_ARG;
-  SeqLinearArgs a;
-  a.w[0] = w0;
-  a.w[1] = w1;
-  a.x = x;
-  a.bias[0] = bias0;
-  a.bias[1] = bias1;
-  a.y = y;
-  a.M = d->M;
-  a.K = d->K;
-  a.Bp = (d->B + 15) / 16 * 16;
-  a.ldx = d->ldx;
-  a.act[0] = d->act0;
-  a.act[1] = d->act1;
-  a.shared_in = d->shared_in;
-  a.S = d->S;
-  a.c_in = nullptr; a.c_out = nullptr; a.xh_next = nullptr; a.h_out = nullptr; a.x_next = nullptr; a.gates_out = nullptr;
+  if ((y2 && !(layout & 4)) || !seq_linear_desc_ok(d, layout, w1)) return VUNET_ERR_ARG;
+  SeqLinearArgs a{};
+  seq_linear_fill(a, d, w0, w1, x, bias0, bias1, y);
   a.y2 = y2;
-  a.seq_stride = 0; a.H = a.hoff = a.n = a.B = 0;
-  // (RT = 2, a 32-row tile per workgroup, halves the operand traffic per weight byte but leaves half the CUs without a workgroup
-  // at every layer size of the reference configuration: not instantiated)
   const dim3 grid(d->M / 16, d->S, d->nets);
   hipStream_t st = (hipStream_t)stream;
-  // 16 waves where K gives each at least one chunk -- up to 32 batch rows.  With 3 - 4 batch tiles (the training batch of 64) a
-  // wave's operand loads are four times its weight loads and four waves with deeper groups are faster (flow training step at
-  // 64 rows: 7.77 -> 7.41 ms; at 16 rows the two forms measured the same, profiles/r05_seq_time.txt)
-  const bool wide = d->K / d->S >= 16 * 32 && d->B <= 32;
-#define SEQ_LINEAR_LAY(NB, LAY)                                                                     \
-  if (wide) VUNET_LAUNCH((seq_linear_kernel<NB, 1, 16, false, LAY>), grid, dim3(1024), 0, st, a);   \
-  else VUNET_LAUNCH((seq_linear_kernel<NB, 1, 4, false, LAY>), grid, dim3(256), 0, st, a);
-#define SEQ_LINEAR_CASE(NB)                        \
-  case NB:                                         \
-    if (layout == 0) { SEQ_LINEAR_LAY(NB, 0) }     \
-    else if (layout == 2) { SEQ_LINEAR_LAY(NB, 2) } \
-    else if (layout == 3) { SEQ_LINEAR_LAY(NB, 3) } \
-    else if (layout == 4) { SEQ_LINEAR_LAY(NB, 4) } \
-    else if (layout == 5) { SEQ_LINEAR_LAY(NB, 5) } \
-    else if (layout == 6) { SEQ_LINEAR_LAY(NB, 6) } \
-    else { SEQ_LINEAR_LAY(NB, 7) }                 \
-    break;
-  switch (a.Bp / 16) {
-    SEQ_LINEAR_CASE(1)
-    SEQ_LINEAR_CASE(2)
-    SEQ_LINEAR_CASE(3)
-    SEQ_LINEAR_CASE(4)
-    default: return VUNET_ERR_ARG;
-  }
-#undef SEQ_LINEAR_CASE
-#undef SEQ_LINEAR_LAY
+  const auto launch = [&](auto nb, auto waves, auto lay) {
+    VUNET_LAUNCH((seq_linear_kernel<nb(), waves(), false, lay()>), grid, dim3(64 * waves()), 0, st, a);
+  };
+  if (!seq_dispatch<0, 2, 3, 4, 5, 6, 7>(a.Bp / 16, seq_linear_wide(d->K / d->S, d->B), layout, launch)) return VUNET_ERR_ARG;
   return vunet_check_launch();
 }
 
@@ -731,18 +671,14 @@ static int seq_lstm_launch(const vunet_seq_lstm_desc* d, const float* w_perm, co
   if (!d || !w_perm || !xh || !bias_perm || !c_in || !c_out || c_in == c_out || !xh_next || xh_next == xh) return VUNET_ERR_ARG;
   if (d->B < 1 || d->B > 16 * SEQ_MAX_NB || d->H < 4 || d->H % 4 || d->n < 1 || d->hoff < d->n || d->ldx < d->hoff + d->H) return VUNET_ERR_ARG;
   if (d->ldx % 32) return VUNET_ERR_ARG;
-  SeqLinearArgs a;
+  SeqLinearArgs a{};
   a.w[0] = w_perm;
-  a.w[1] = nullptr;
   a.x = xh;
   a.bias[0] = bias_perm;
-  a.bias[1] = nullptr;
-  a.y = nullptr;
   a.M = 4 * d->H;
   a.K = d->ldx;
   a.Bp = (d->B + 15) / 16 * 16;
   a.ldx = d->ldx;
-  a.act[0] = a.act[1] = 0;
   a.shared_in = 1;
   a.S = 1;
   a.c_in = c_in;
@@ -750,7 +686,6 @@ static int seq_lstm_launch(const vunet_seq_lstm_desc* d, const float* w_perm, co
   a.xh_next = xh_next;
   a.h_out = h_out;
   a.x_next = x_next;
-  a.y2 = nullptr;
   a.gates_out = gates_out;
   a.ht_in = ht_in;
   a.ht_out = ht_out;
@@ -762,28 +697,16 @@ static int seq_lstm_launch(const vunet_seq_lstm_desc* d, const float* w_perm, co
   if ((ht_in || ht_out) && (!w_tiled || d->H % 32 || d->hoff % 32 || d->ldx != d->hoff + d->H || ht_in == ht_out)) return VUNET_ERR_ARG;
   const dim3 grid(a.M / 16, 1, 1);
   hipStream_t st = (hipStream_t)stream;
-  const bool wide = a.K >= 16 * 32 && d->B <= 32;   // (3 - 4 batch tiles: four waves, as vunet_seq_linear; 50-step roll-out at 64 rows 1.03 -> 0.93 ms)
+  const bool wide = seq_linear_wide(a.K, d->B);   // (3 - 4 batch tiles: four waves; 50-step roll-out at 64 rows 1.03 -> 0.93 ms)
   if (ht_in && !wide && a.Bp >= 48) {   // the h part of the operand from tiles: the four-wave form at 3 - 4 batch tiles
-    if (a.Bp == 48) VUNET_LAUNCH((seq_linear_kernel<3, 1, 4, true, 25>), grid, dim3(256), 0, st, a);
-    else VUNET_LAUNCH((seq_linear_kernel<4, 1, 4, true, 25>), grid, dim3(256), 0, st, a);
+    if (a.Bp == 48) VUNET_LAUNCH((seq_linear_kernel<3, 4, true, 25>), grid, dim3(256), 0, st, a);
+    else VUNET_LAUNCH((seq_linear_kernel<4, 4, true, 25>), grid, dim3(256), 0, st, a);
     return vunet_check_launch();
   }
-#define SEQ_LSTM_CASE(NB)                                                                                   \
-  case NB:                                                                                                  \
-    if (w_tiled) {                                                                                          \
-      if (wide) VUNET_LAUNCH((seq_linear_kernel<NB, 1, 16, true, 9>), grid, dim3(1024), 0, st, a);          \
-      else VUNET_LAUNCH((seq_linear_kernel<NB, 1, 4, true, 9>), grid, dim3(256), 0, st, a);                 \
-    } else if (wide) VUNET_LAUNCH((seq_linear_kernel<NB, 1, 16, true>), grid, dim3(1024), 0, st, a);        \
-    else VUNET_LAUNCH((seq_linear_kernel<NB, 1, 4, true>), grid, dim3(256), 0, st, a);                      \
-    break;
-  switch (a.Bp / 16) {
-    SEQ_LSTM_CASE(1)
-    SEQ_LSTM_CASE(2)
-    SEQ_LSTM_CASE(3)
-    SEQ_LSTM_CASE(4)
-    default: return VUNET_ERR_ARG;
-  }
-#undef SEQ_LSTM_CASE
+  const auto launch = [&](auto nb, auto waves, auto lay) {
+    VUNET_LAUNCH((seq_linear_kernel<nb(), waves(), true, lay()>), grid, dim3(64 * waves()), 0, st, a);
+  };
+  if (!seq_dispatch<0, 9>(a.Bp / 16, wide, w_tiled ? 9 : 0, launch)) return VUNET_ERR_ARG;
   return vunet_check_launch();
 }
 

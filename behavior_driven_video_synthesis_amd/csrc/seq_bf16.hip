@@ -13,39 +13,18 @@
 // of a wave holds batch row l & 15 and k = 8 (l >> 4) .. + 7 of a chunk there, which IS the B-operand map of the bf16 instruction.
 #include "common.h"
 #include "../../include/vunet_seq_bf16.h"
+#include "seq_linear_args.h"
 
 namespace {
 
-constexpr int SEQ16_MAX_NB = 4;   // batch tiles of 16: B <= 64
-
 typedef __bf16 seq_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned seq_u4v __attribute__((ext_vector_type(4)));
 
 union SeqFrag {
   uint4 u;
   seq_bf16x8 b;
 };
 
-struct SeqLinear16Args {
-  const uint16_t* w[2];   // bf16 tile images [M / 16][K / 32][64][8]
-  const float* x;         // [nets_in][Bp][ldx] rows, or xt tiles [nets_in][Bp / 16][K / 32][2][64][4]
-  const float* bias[2];   // [M] (NULL: none)
-  float* y;               // [nets][Bp][M] rows, the next layer's xt tiles, or (S > 1) [nets][S][Bp][M] raw partial slabs
-  int M, K, Bp, ldx, act[2], shared_in, S;
-};
-
-__device__ __forceinline__ float seq16_act(float v, int act) {   // (seq_act of csrc/seq.hip)
-  if (act == 1) return fmaxf(v, 0.01f * v);
-  if (act == 2) return tanhf(v);
-  if (act == 3) return fmaxf(v, 0.f);
-  return v;
-}
-
-// read once per pass by this one workgroup: streamed past the caches' retention
-__device__ __forceinline__ uint4 seq16_w_load(const uint16_t* p) {
-  const seq_u4v t = __builtin_nontemporal_load(reinterpret_cast<const seq_u4v*>(p));
-  return make_uint4(t.x, t.y, t.z, t.w);
-}
+using SeqLinear16Args = SeqLinearBaseArgs<uint16_t>;   // w: bf16 tile images [M / 16][K / 32][64][8]
 
 // x == t0 + t1 + t2: the upper 16 bits of the running remainder, three times (both subtractions are exact).  Values a, b are
 // elements 2 p, 2 p + 1 of the fragments: bf16 element j sits in bits 16 (j & 1) of word j / 2.
@@ -65,12 +44,13 @@ struct Seq16GroupRegs {
   float4 xv[NB][U][2];
 };
 
-// the loads of a group of U chunks (c0, c0 + WAVES, ...): one weight tile, the operand of NB batch tiles
+// the loads of a group of U chunks (c0, c0 + WAVES, ...): one weight tile (read once per pass by this one workgroup: streamed
+// past the caches' retention), the operand of NB batch tiles
 template <int NB, int U, int WAVES, int LAY>
 __device__ __forceinline__ void seq16_group_load(const SeqLinear16Args& a, const uint16_t* __restrict__ w, const float* __restrict__ x,
                                                  int c0, Seq16GroupRegs<NB, U>& r) {
 #pragma unroll
-  for (int u = 0; u < U; ++u) r.wv[u] = seq16_w_load(w + 512 * (size_t)(c0 + WAVES * u));
+  for (int u = 0; u < U; ++u) r.wv[u] = nt_load4(w + 512 * (size_t)(c0 + WAVES * u));
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -167,7 +147,7 @@ __global__ __launch_bounds__(64 * WAVES) void seq_linear_bf16w_kernel(SeqLinear1
   float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (bias) bv = *reinterpret_cast<const float4*>(bias + col);
   float4 t = add4(v, bv);
-  t = make_float4(seq16_act(t.x, act), seq16_act(t.y, act), seq16_act(t.z, act), seq16_act(t.w, act));
+  t = make_float4(seq_act(t.x, act), seq_act(t.y, act), seq_act(t.z, act), seq_act(t.w, act));
   if constexpr (LAY & 4) {
     // the next layer's operand tile: columns m0 + 4 kq .. + 3 of batch row i are chunk m0 / 32, slot 2 (m0 / 16 & 1) + kq / 2,
     // half kq & 1 there (include/vunet_seq_tiled.h)
@@ -217,48 +197,14 @@ extern "C" int vunet_seq_linear_bf16w(const vunet_seq_linear_desc* d, int32_t la
                                       const float* x, const float* bias0, const float* bias1, float* y, void* stream) {
   if (!d || !w0 || !x || !y) return VUNET_ERR_ARG;
   if (layout < 0 || layout > 7 || !(layout & VUNET_SEQ_TILED_W)) return VUNET_ERR_UNSUPPORTED;   // 1 / 3 / 5 / 7
-  if ((layout & 4) && (d->S != 1 || d->M % 32)) return VUNET_ERR_ARG;
-  if (d->nets < 1 || d->nets > 2 || (d->nets == 2 && !w1)) return VUNET_ERR_ARG;
-  if (d->B < 1 || d->B > 16 * SEQ16_MAX_NB || d->M < 16 || d->M % 16) return VUNET_ERR_ARG;
-  if (d->S < 1 || d->S > 8 || d->K < 32 || d->K % (32 * d->S) || d->ldx < d->K || d->ldx % 4) return VUNET_ERR_ARG;
-  if (d->act0 < 0 || d->act0 > 3 || d->act1 < 0 || d->act1 > 3) return VUNET_ERR_ARG;
-  SeqLinear16Args a;
-  a.w[0] = w0;
-  a.w[1] = w1;
-  a.x = x;
-  a.bias[0] = bias0;
-  a.bias[1] = bias1;
-  a.y = y;
-  a.M = d->M;
-  a.K = d->K;
-  a.Bp = (d->B + 15) / 16 * 16;
-  a.ldx = d->ldx;
-  a.act[0] = d->act0;
-  a.act[1] = d->act1;
-  a.shared_in = d->shared_in;
-  a.S = d->S;
+  if (!seq_linear_desc_ok(d, layout, w1)) return VUNET_ERR_ARG;
+  SeqLinear16Args a{};
+  seq_linear_fill(a, d, w0, w1, x, bias0, bias1, y);
   const dim3 grid(d->M / 16, d->S, d->nets);
   hipStream_t st = (hipStream_t)stream;
-  // 16 waves where K gives each at least one chunk, up to 32 batch rows; else four (the rule of the fp32 kernel)
-  const bool wide = d->K / d->S >= 16 * 32 && d->B <= 32;
-#define SEQ16_LAY(NB, LAY)                                                                     \
-  if (wide) VUNET_LAUNCH((seq_linear_bf16w_kernel<NB, 16, LAY>), grid, dim3(1024), 0, st, a);  \
-  else VUNET_LAUNCH((seq_linear_bf16w_kernel<NB, 4, LAY>), grid, dim3(256), 0, st, a);
-#define SEQ16_CASE(NB)                               \
-  case NB:                                           \
-    if (layout == 1) { SEQ16_LAY(NB, 0) }            \
-    else if (layout == 3) { SEQ16_LAY(NB, 2) }       \
-    else if (layout == 5) { SEQ16_LAY(NB, 4) }       \
-    else { SEQ16_LAY(NB, 6) }                        \
-    break;
-  switch (a.Bp / 16) {
-    SEQ16_CASE(1)
-    SEQ16_CASE(2)
-    SEQ16_CASE(3)
-    SEQ16_CASE(4)
-    default: return VUNET_ERR_ARG;
-  }
-#undef SEQ16_CASE
-#undef SEQ16_LAY
+  const auto launch = [&](auto nb, auto waves, auto lay) {
+    VUNET_LAUNCH((seq_linear_bf16w_kernel<nb(), waves(), lay()>), grid, dim3(64 * waves()), 0, st, a);
+  };
+  if (!seq_dispatch<0, 2, 4, 6>(a.Bp / 16, seq_linear_wide(d->K / d->S, d->B), layout & 6, launch)) return VUNET_ERR_ARG;
   return vunet_check_launch();
 }

@@ -28,17 +28,6 @@ namespace {
 
 __device__ __forceinline__ float comp4(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 
-// weights and moments are streamed: each byte is touched once per kernel by one workgroup
-typedef float seq_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 seq_nt_load(const float* p) {
-  const seq_f4 t = __builtin_nontemporal_load(reinterpret_cast<const seq_f4*>(p));
-  return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void seq_nt_store(float* p, const float4& v) {
-  seq_f4 t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<seq_f4*>(p));
-}
-
 // ------------------------------------------------------------------------------------------------ dX = dZ . W
 struct SeqDxArgs {
   const float* w[2];   // [M][K]
@@ -349,9 +338,9 @@ __global__ __launch_bounds__(256) void seq_dw_kernel(const vunet_seq_dw_layer* _
       off[u] = (size_t)(m0 + row) * L.K + k0 + 4 * c4;
       if constexpr (ADAM) {
         // (each of these bytes is touched once per step: keep them out of the L2 that holds the operand rows)
-        p[u] = seq_nt_load(L.w + off[u]);
-        m[u] = seq_nt_load(L.m + off[u]);
-        v[u] = seq_nt_load(L.v + off[u]);
+        p[u] = nt_load4(L.w + off[u]);
+        m[u] = nt_load4(L.m + off[u]);
+        v[u] = nt_load4(L.v + off[u]);
       }
       g[u] = *reinterpret_cast<const float4*>(&dws[dw_swo(row, 4 * c4)]);
       if (k0 + 4 * c4 + 3 >= L.kv) {   // (padding columns of the image: only where K is not the layer's own width)
@@ -369,9 +358,9 @@ __global__ __launch_bounds__(256) void seq_dw_kernel(const vunet_seq_dw_layer* _
         adam_update(h, g[u].y, p[u].y, m[u].y, v[u].y);
         adam_update(h, g[u].z, p[u].z, m[u].z, v[u].z);
         adam_update(h, g[u].w, p[u].w, m[u].w, v[u].w);
-        seq_nt_store(L.w + off[u], p[u]);
-        seq_nt_store(L.m + off[u], m[u]);
-        seq_nt_store(L.v + off[u], v[u]);
+        nt_store4(L.w + off[u], p[u]);
+        nt_store4(L.m + off[u], m[u]);
+        nt_store4(L.v + off[u], v[u]);
       } else {
         *reinterpret_cast<float4*>(L.g + off[u]) = g[u];
       }
@@ -473,15 +462,15 @@ __global__ __launch_bounds__(256) void seq_dwx_kernel(const vunet_seq_dw_layer* 
       }
       const size_t off = (size_t)(m0 + row) * L.K + k0 + 4 * c4;
       if constexpr (ADAM) {
-        float4 p = seq_nt_load(L.w + off), m = seq_nt_load(L.m + off), v = seq_nt_load(L.v + off);
+        float4 p = nt_load4(L.w + off), m = nt_load4(L.m + off), v = nt_load4(L.v + off);
         pold[it] = p;
         adam_update(h, g.x, p.x, m.x, v.x);
         adam_update(h, g.y, p.y, m.y, v.y);
         adam_update(h, g.z, p.z, m.z, v.z);
         adam_update(h, g.w, p.w, m.w, v.w);
-        seq_nt_store(L.w + off, p);
-        seq_nt_store(L.m + off, m);
-        seq_nt_store(L.v + off, v);
+        nt_store4(L.w + off, p);
+        nt_store4(L.m + off, m);
+        nt_store4(L.v + off, v);
       } else {
         pold[it] = L.dx_raw ? *reinterpret_cast<const float4*>(L.w + off) : make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4*>(L.g + off) = g;

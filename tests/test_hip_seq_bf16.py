@@ -96,6 +96,83 @@ def test_single_layer_is_the_fp32_accurate_product_with_rounded_weights(rows, op
     assert e16 <= max(3.0 * e32, 2e-6), (e16, e32)
 
 
+def _run_bf16w(ops, S, layout, B, M, K, ldx, var, x, w, bias, pad, split=1):
+    """One launch of vunet_seq_linear_bf16w on host-built images (``_image_index``; the operand by ``to_tiles``); returns y as
+    [nets][split][Bp][M] row-major (un-tiled by ``from_tiles`` with bit 4).  Padding rows of the operand hold ``pad``."""
+    import ctypes
+
+    from test_hip_seq_kernels import Outs, _d, from_tiles, to_tiles
+    nets, shared, acts, nobias = var
+    b_pad = (B + 15) // 16 * 16
+    xp = x.clone()
+    xp[:, B:] = pad
+    xop = torch.stack([to_tiles(xi[:, :K].contiguous()) for xi in xp]) if layout & 2 else xp
+    idx = torch.from_numpy(_image_index(M, K).reshape(-1))
+    wd = []
+    for n in range(nets):
+        img = torch.empty(M * K, dtype=torch.bfloat16)
+        img[idx] = w[n].bfloat16().reshape(-1)
+        wd.append(_d(img))
+    bd = [None if nobias == n else _d(bias[n]) for n in range(nets)]
+    o = Outs()
+    y = o.new(nets, split, b_pad, M)
+    d = S.SeqLinearDesc(B, M, K, ldx, acts[0], acts[1], nets, shared, split)
+    ops._call("vunet_seq_linear_bf16w", ctypes.byref(d), layout, ops._p(wd[0]), ops._p(wd[1] if nets > 1 else None), ops._p(_d(xop)),
+              ops._p(bd[0]), ops._p(bd[1] if nets > 1 else None), ops._p(y), ops._stream())
+    o.check()
+    y = y.cpu()
+    if layout & 4:
+        y = torch.stack([from_tiles(y[n].reshape(-1), b_pad, M) for n in range(nets)]).view(nets, 1, b_pad, M)
+    return y
+
+
+# B x K: 1, 5, 17 and 34 chunks -- one chunk, groups of 4 + 1, the 16-wave form with one wave holding two chunks, an uneven
+# split over four waves -- at 1 - 4 batch tiles; then the raw split-K slabs
+BF16W_CASES = [(b, k, 1) for k in (32, 160, 544, 1088) for b in (1, 17, 33, 64)] + [(b, k, s) for k, s in ((128, 2), (2048, 4))
+                                                                                       for b in (16, 64)]
+
+
+@pytest.mark.parametrize("B,K,split", BF16W_CASES)
+def test_linear_bf16w_every_layout_vs_float64(B, K, split):
+    """vunet_seq_linear_bf16w called directly.  M = 16 (layouts 1, 3) and 32 (1, 3, 5, 7); nets / shared_in / the four
+    activations / a NULL bias rotate as in tests/test_hip_seq_kernels.py.  Layouts 3, 5, 7 bit-equal to layout 1 after un-tiling;
+    rows < B bit-equal with the padding rows at 0 and at NaN; no unwritten output; against x.double() @ w.bfloat16().double().T
+    + b through the activation, error / max|y| at most the larger of 3 x the fp32 kernel's own (same inputs, against its float64
+    product) and 2e-6.  split > 1 (layouts 1, 3): RAW slabs -- the bias is given and tanh asked for, neither may be applied."""
+    from behavior_driven_video_synthesis_amd import ops, seq as S
+    from test_hip_seq_kernels import LINEAR_VARIANTS, NAN, _act64, _linear_operands, _run_linear, assert_same
+    case = BF16W_CASES.index((B, K, split))
+    kb = K // split
+    for mi, M in enumerate((16, 32)):
+        var = LINEAR_VARIANTS[(case * 2 + mi) % len(LINEAR_VARIANTS)] if split == 1 else ((1, 1, (2, 0), None), (2, 0, (2, 2), None))[mi]
+        nets, shared, acts, nobias = var
+        nin = 1 if (shared or nets == 1) else nets
+        x, w, bias, ldx = _linear_operands(7000 + 10 * case + mi, B, M, K, nets, nin)
+        y32, _ = _run_linear(ops, S, 0, B, M, K, ldx, var, x, w, bias, 0.0, split=split)
+        base = None
+        for layout in ((1, 3) if (M % 32 or split > 1) else (1, 3, 5, 7)):
+            y0 = _run_bf16w(ops, S, layout, B, M, K, ldx, var, x, w, bias, 0.0, split)
+            yn = _run_bf16w(ops, S, layout, B, M, K, ldx, var, x, w, bias, NAN, split)
+            tag = f"B {B} M {M} K {K} S {split} layout {layout} {var}"
+            assert not torch.isnan(y0).any(), f"{tag}: unwritten output"
+            assert_same(yn[:, :, :B], y0[:, :, :B], f"{tag}: rows < B depend on the padding rows")
+            if base is not None:
+                assert_same(y0, base, f"{tag}: differs from layout 1")
+                continue
+            base = y0
+            for n in range(nets):
+                for s in range(split):
+                    xi = x[n if nin > 1 else 0][:B, s * kb:(s + 1) * kb].double()
+                    b64 = torch.zeros(M, dtype=torch.float64) if (nobias == n or split > 1) else bias[n].double()
+                    act = 0 if split > 1 else acts[n]
+                    ref16 = _act64(xi @ w[n][:, s * kb:(s + 1) * kb].bfloat16().double().t() + b64, act)
+                    ref32 = _act64(xi @ w[n][:, s * kb:(s + 1) * kb].double().t() + b64, act)
+                    e16 = float((y0[n, s, :B].double() - ref16).abs().max() / ref16.abs().max())
+                    e32 = float((y32[n, s, :B].double() - ref32).abs().max() / ref32.abs().max())
+                    print(f"{tag} net {n} slab {s}: max err / max|y|  bf16 weights {e16:.2e}  fp32 kernel {e32:.2e}")
+                    assert e16 <= max(3.0 * e32, 2e-6), (tag, n, s, e16, e32)
+
+
 @pytest.mark.parametrize("bsz", [1, 16, 17, 48, 64, 100])
 def test_flow_vs_oracle_on_rounded_weights_over_batch_sizes(bsz):
     """Every batch-tile count of the kernel (1..4 tiles of 16 rows) and the chunking above 64 rows: forward, logdet, reverse."""
