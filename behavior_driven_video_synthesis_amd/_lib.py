@@ -6,7 +6,10 @@ product path raises.
 """
 from __future__ import annotations
 
+import ast
 import ctypes
+import functools
+import operator
 import os
 import re
 import subprocess
@@ -81,7 +84,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
+@functools.lru_cache(maxsize=None)
 def _header_text() -> str:
+    """include/*.h in one string, comments stripped (read once: the headers do not change under a running process)."""
     txt = "\n".join(open(h).read() for h in headers())
     return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
 
@@ -112,6 +117,96 @@ def declared_prototypes() -> dict:
                     types.append(_CTYPE[a.replace("const ", "").split(" ")[0]])
         protos[name] = types
     return protos
+
+
+# ---- descriptor structs and integer constants come from the same headers: Python holds no second copy of either
+def _members(cname: str, decl: str, structs: dict) -> list:
+    """The (name, ctype) fields of one member declaration (whitespace normalised) of struct ``cname``."""
+    dm = re.fullmatch(r"(?:const )?(\w+)\b ?(.+)", decl)
+    base, fields = dm.group(1) if dm else None, []
+    ctype = _CTYPE.get(base) or structs.get(base)
+    for part in dm.group(2).split(",") if dm else [""]:
+        pm = re.fullmatch(r"(\*?) ?([A-Za-z_]\w*)", part.strip())
+        if pm is None or (ctype is None and not (pm.group(1) and base == "void")):
+            raise ValueError(f"struct {cname}: unsupported declaration `{decl};`")
+        fields.append((pm.group(2), ctypes.c_void_p if pm.group(1) else ctype))
+    return fields
+
+
+def parse_structs(txt: str) -> dict:
+    """cname -> ctypes.Structure subclass for every ``typedef struct [tag] { ... } cname;`` of the comment-stripped header text,
+    in order.  A member is ``[const] T a, b;`` or ``[const] T *a, *b;``, T a fixed-width scalar, ``void`` (pointers only) or a struct
+    declared earlier; a pointer is a ``c_void_p``.  Anything else (an unknown type, a bitfield, an array, a union, a function
+    pointer) raises ValueError with the struct and the declaration: nothing is skipped."""
+    structs = {}
+    for m in re.finditer(r"\btypedef\s+struct\b\s*(\w*)\s*\{", txt):
+        end = txt.find("}", m.end())
+        tail = re.match(r"\}\s*(\w+)\s*;", txt[end:]) if end >= 0 else None
+        body = txt[m.end():end]
+        if tail is None or "{" in body:
+            raise ValueError(f"struct {m.group(1)}: braces inside the body (a union, an inner struct) or no closing `}} name;`")
+        cname = tail.group(1)
+        fields = [f for decl in body.split(";") if decl.strip() for f in _members(cname, " ".join(decl.split()), structs)]
+        structs[cname] = type(cname, (ctypes.Structure,), {"_fields_": fields})
+    return structs
+
+
+_TOKEN = r"0[xX][0-9a-fA-F]+|[1-9][0-9]*|0|[A-Za-z_]\w*|<<|[-+*()]"
+_BINOP = {ast.Add: operator.add, ast.Sub: operator.sub, ast.Mult: operator.mul, ast.LShift: operator.lshift}
+_FLOAT = r"[-+]?((\d+\.\d*|\.\d+)([eE][-+]?\d+)?|\d+[eE][-+]?\d+)[fFlL]?"
+
+
+def _eval_int(body: str, known: dict) -> int:
+    """A macro body of decimal / hex literals, names in ``known`` and ``+ - * << ( )`` (C and Python agree on their precedence)."""
+    def ev(n):
+        if isinstance(n, ast.Constant):
+            return n.value
+        if isinstance(n, ast.Name) and n.id in known:
+            return known[n.id]
+        if isinstance(n, ast.UnaryOp) and isinstance(n.op, (ast.USub, ast.UAdd)):
+            return -ev(n.operand) if isinstance(n.op, ast.USub) else ev(n.operand)
+        if isinstance(n, ast.BinOp) and type(n.op) in _BINOP:
+            return _BINOP[type(n.op)](ev(n.left), ev(n.right))
+        raise ValueError(ast.dump(n))
+    if not re.fullmatch(rf"(\s*({_TOKEN}))+\s*", body):
+        raise ValueError("a character outside the grammar")
+    return ev(ast.parse(" ".join(re.findall(_TOKEN, body)), mode="eval").body)   # (tokens re-joined: no Python-only spelling gets in)
+
+
+def parse_constants(txt: str) -> dict:
+    """name -> int for the object-like ``#define VUNET_*`` macros of the comment-stripped header text.  No constants, by rule:
+    macros of another namespace, function-like macros, empty bodies (the include guards) and a body that is one floating-point
+    literal.  Every other body must be an integer expression of literals and EARLIER macros (``_eval_int``), or this raises."""
+    consts = {}
+    for name, params, body in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(\(?)(.*)$", txt, flags=re.M):
+        body = body.strip()
+        if name.startswith("VUNET_") and not params and body and not re.fullmatch(_FLOAT, body):
+            try:
+                consts[name] = _eval_int(body, consts)
+            except (ValueError, SyntaxError) as e:
+                raise ValueError(f"#define {name} {body}: not an integer expression ({e})") from None
+    return consts
+
+
+@functools.lru_cache(maxsize=None)
+def structs() -> dict:
+    """cname -> ctypes.Structure subclass for every struct of include/*.h (parsed once; the dict is shared: read it only)."""
+    return parse_structs(_header_text())
+
+
+@functools.lru_cache(maxsize=None)
+def constants() -> dict:
+    """name -> value of every integer ``#define VUNET_*`` of include/*.h (parsed once; the dict is shared: read it only)."""
+    return parse_constants(_header_text())
+
+
+def struct(cname: str):
+    """The class of ``typedef struct ... cname;``.  Bind it at import, as ``const``'s values: no launch path looks either up."""
+    return structs()[cname]
+
+
+def const(name: str) -> int:
+    return constants()[name]
 
 
 _LIB = None

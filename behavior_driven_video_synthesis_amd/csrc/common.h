@@ -9,8 +9,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #include "../../include/vunet_hip.h"
 
-// ---- activation codes shared with include/vunet_hip.h
-enum { ACT_NONE = 0, ACT_ELU = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_LRELU = 4 };
+// ---- activation codes: the public ones of include/vunet_hip.h
+enum { ACT_NONE = VUNET_ACT_NONE, ACT_ELU = VUNET_ACT_ELU, ACT_RELU = VUNET_ACT_RELU, ACT_SIGMOID = VUNET_ACT_SIGMOID,
+       ACT_LRELU = VUNET_ACT_LRELU };
 
 // Stateless dropout hash: keep(idx) <=> hash(idx + seed) >= thresh.  The CPU side of the parity
 // tests reproduces this function bit for bit (tests/hip_parity_utils.py: dropout_keep_mask).

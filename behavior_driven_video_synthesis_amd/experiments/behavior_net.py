@@ -37,7 +37,7 @@ from ..models.flow.simple_flow import UnsupervisedTransformer2
 from ..models.pose_behavior_rnn import Regressor_fly, ResidualBehaviorNet
 from ..ops import _call, _p, _stream
 from ..optim import FusedAdam
-from ..seq_train import RegressorTrainEngine
+from ..seq_train import REG_C, REG_T, RegressorTrainEngine
 
 DEFAULT_CONFIG = {   # config/behavior_net.yaml
     "architecture": {"decoder_arch": "lstm", "linear_in_decoder": False, "dim_hidden_b": 1024, "flow_mid_channels_factor": 2,
@@ -164,8 +164,8 @@ class BehaviorNet:
         seq_len = seq_b.shape[1]
         out: Dict = {}
         if not self.only_flow:
-            if self.use_regressor and seq_len != 50:
-                raise ValueError(f"use_regressor needs seq_len == 50: the regressor's fc4 is Linear(50, 128) on a one-hot over the "
+            if self.use_regressor and seq_len != REG_T:
+                raise ValueError(f"use_regressor needs seq_len == {REG_T}: the regressor's fc4 is Linear({REG_T}, {REG_C}) on a one-hot over the "
                                  f"sequence (models/pose_behavior_rnn.py:55), got seq_len {seq_len}")
             p = self._cvae_step(seq_b, target, eps, reg_index, update)
             sc = p["scalars"]

@@ -24,9 +24,10 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _lib
 from .ops import _call, _p, _stream
 
-_DOT_WORK = 256      # VUNET_F64_DOT_WORK
+_DOT_WORK = _lib.const("VUNET_F64_DOT_WORK")
 
 
 class FIDResult(NamedTuple):

@@ -19,10 +19,11 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
+from . import _lib
 from .ops import _call, _p, _stream
 
-T2P, T3P, T4P, T5P = 2, 3, 4, 5          # VUNET_INPLANE_T2P .. T5P: the kind is the number of joints it reads
-MAX_IDS, MAX_PARTS = 5, 64               # VUNET_INPLANE_MAX_IDS, VUNET_INPLANE_MAX_PARTS
+T2P, T3P, T4P, T5P = (_lib.const("VUNET_INPLANE_" + k) for k in ("T2P", "T3P", "T4P", "T5P"))   # the kind is the number of joints it reads
+MAX_IDS, MAX_PARTS = _lib.const("VUNET_INPLANE_MAX_IDS"), _lib.const("VUNET_INPLANE_MAX_PARTS")
 BATCH_KEY = "inplane_keypoints"          # [N, J, 2] (x, y) pixel coordinates of batch["pose_img"]
 
 

@@ -15,10 +15,11 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import _lib
 from .ops import _call, _p, _stream
 
 FLOW_KEYS = ("flow_loss", "reference_nll_loss", "nlogdet_loss", "nll_loss")     # the kernel's output order
-KS_MAX_LDS_N = 32768            # VUNET_SEQ_KS_MAX_LDS_N: the longest column one workgroup sorts in LDS
+KS_MAX_LDS_N = _lib.const("VUNET_SEQ_KS_MAX_LDS_N")   # the longest column one workgroup sorts in LDS
 SETS = ("b", "mu", "pre", "prior_samples", "flow_samples", "gaussian_samples")
 P_METHODS = ("reference", "asymptotic", "exact")
 

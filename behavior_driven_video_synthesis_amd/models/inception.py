@@ -28,26 +28,20 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
-from .. import ops
+from .. import _lib, ops
 from ..ops import _call, _p, _stream
 
 BN_EPS = 1e-3
-SIZE = 299                      # VUNET_INCEPTION_SIZE
+SIZE = _lib.const("VUNET_INCEPTION_SIZE")
 MIN_SIZE = 75                   # the smallest input whose maps reach 1 x 1 at Mixed_7a
-KC, MT = 64, 64                 # VUNET_CONVG_KC / VUNET_CONVG_MT: the packing's K and M padding
+KC, MT = _lib.const("VUNET_CONVG_KC"), _lib.const("VUNET_CONVG_MT")   # the packing's K and M padding
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 INPUT_MODES = {"none": 0, "transform": 1, "fid": 2}
 N_FEATURES, N_CLASSES = 2048, 1000
 
 
-class ConvgDesc(ctypes.Structure):   # vunet_convg_desc
-    _fields_ = [(n, ctypes.c_int32) for n in ("N", "C", "H", "W", "M", "Ho", "Wo", "KH", "KW", "stride_h", "stride_w", "pad_h", "pad_w",
-                                              "x_ctot", "x_coff", "y_ctot", "y_coff", "relu", "Kpad", "Mpad", "tile")]
-
-
-class Pool2dDesc(ctypes.Structure):  # vunet_pool2d_desc
-    _fields_ = [(n, ctypes.c_int32) for n in ("N", "C", "H", "W", "Ho", "Wo", "stride", "pad", "mode", "x_ctot", "x_coff", "y_ctot",
-                                              "y_coff")]
+ConvgDesc = _lib.struct("vunet_convg_desc")
+Pool2dDesc = _lib.struct("vunet_pool2d_desc")
 
 
 def _pair(v) -> Tuple[int, int]:

@@ -18,11 +18,12 @@ from typing import Iterable, Optional, Tuple
 
 import torch
 
+from . import _lib
 from .behavior_eval import PoseStats
 from .ops import _call, _p, _stream
 
 # include/vunet_seq_nn.h
-QT_CODES, QT_POSES, CHUNK, MAX_H, MAX_TN = 16, 4, 128, 1024, 4096
+QT_CODES, QT_POSES, CHUNK, MAX_H, MAX_TN = (_lib.const("VUNET_NN_" + n) for n in ("QT_CODES", "QT_POSES", "CHUNK", "MAX_H", "MAX_TN"))
 
 
 def scratch_bytes(n: int, q: int) -> int:

@@ -22,43 +22,17 @@ import torch
 
 from . import _lib
 
-ACT_NONE, ACT_ELU, ACT_RELU, ACT_SIGMOID, ACT_LRELU = 0, 1, 2, 3, 4
+ACT_NONE, ACT_ELU, ACT_RELU, ACT_SIGMOID, ACT_LRELU = (_lib.const("VUNET_ACT_" + a) for a in ("NONE", "ELU", "RELU", "SIGMOID", "LRELU"))
 SEED2_OFFSET = 0x9E3779B9  # seed offset of the second source of a dual-source conv (csrc/conv_gather.hip)
 
-
-class ConvDesc(ctypes.Structure):
-    _fields_ = [("N", ctypes.c_int32), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32), ("Hs", ctypes.c_int32),
-                ("Ws", ctypes.c_int32), ("M", ctypes.c_int32), ("m_off", ctypes.c_int32), ("Mpad", ctypes.c_int32),
-                ("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32), ("KH", ctypes.c_int32), ("KW", ctypes.c_int32),
-                ("stride", ctypes.c_int32), ("pad", ctypes.c_int32), ("mode", ctypes.c_int32),
-                ("in_act", ctypes.c_int32), ("in_slope", ctypes.c_float), ("drop_p", ctypes.c_float),
-                ("drop_seed", ctypes.c_uint32), ("out_act", ctypes.c_int32), ("d2s", ctypes.c_int32),
-                ("aux_act", ctypes.c_int32), ("aux_slope", ctypes.c_float), ("aux_drop_p", ctypes.c_float),
-                ("aux_drop_seed", ctypes.c_uint32)]
-
-
-class WgradDesc(ctypes.Structure):
-    _fields_ = [("N", ctypes.c_int32), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32), ("Hs", ctypes.c_int32),
-                ("Ws", ctypes.c_int32), ("Cout", ctypes.c_int32), ("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32),
-                ("KH", ctypes.c_int32), ("KW", ctypes.c_int32), ("stride", ctypes.c_int32), ("pad", ctypes.c_int32),
-                ("in_act", ctypes.c_int32), ("in_slope", ctypes.c_float), ("drop_p", ctypes.c_float),
-                ("drop_seed", ctypes.c_uint32), ("nsplit", ctypes.c_int32), ("flags", ctypes.c_int32)]
-
-
-class WgradItem(ctypes.Structure):   # vunet_wgrad_item: one layer of a batched weight-gradient launch
-    _fields_ = [("d", WgradDesc)] + [(n, ctypes.c_void_p) for n in ("x1", "x2", "dy", "slabs", "dshift", "amax_x", "amax_x2",
-                                                                   "amax_dy")]
-
-
-class WnDesc(ctypes.Structure):
-    _fields_ = [("Cout", ctypes.c_int32), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32), ("KH", ctypes.c_int32),
-                ("KW", ctypes.c_int32), ("kind", ctypes.c_int32), ("split", ctypes.c_int32)]
-
-
-class WnBwdItem(ctypes.Structure):
-    _fields_ = ([(n, ctypes.c_void_p) for n in ("slabs", "dshift", "v", "g", "bias", "gamma", "invnorm", "dv", "dg", "dbias",
-                                                "dgamma", "dbeta", "workspace")] +
-                [("d", WnDesc), ("nsplit", ctypes.c_int32), ("accumulate", ctypes.c_int32)])
+# the descriptors of include/vunet_hip.h (WgradItem, WnItem and WnBwdItem are uploaded as device tables, byte for byte)
+ConvDesc = _lib.struct("vunet_conv_desc")
+WgradDesc = _lib.struct("vunet_wgrad_desc")
+WgradItem = _lib.struct("vunet_wgrad_item")
+WnDesc = _lib.struct("vunet_wn_desc")
+WnItem = _lib.struct("vunet_wn_item")
+WnBwdItem = _lib.struct("vunet_wn_bwd_item")
+P2Desc = _lib.struct("vunet_p2_desc")
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -206,8 +180,8 @@ def _scheme() -> int:
 
 
 _wants_split_cache = {}
-_TUNING_KEYS = {"split_force_nt": 0, "tiled_force_nt": 1, "force_small": 2, "blk_force_nt": 3, "parity_launches": 4, "blk_ws": 5, "wgrad_rowsplit": 6, "s2_fwd_f32": 7, "p2_form": 8,
-                "p2_terms": 9}
+_TUNING_KEYS = {k[len("VUNET_TUNE_"):].lower(): v for k, v in _lib.constants().items()
+                if k.startswith("VUNET_TUNE_") and k != "VUNET_TUNE_COUNT"}
 _tuning_values = {}
 
 
@@ -821,11 +795,6 @@ def remove_grad_hook(fn):
 # ------------------------------------------------------------------------------------------------
 # batched weight preparation: every layer of a model in two launches (vunet_weightnorm_fwd_multi)
 # ------------------------------------------------------------------------------------------------
-class WnItem(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("v", "g", "bias", "gamma", "beta", "wt_f", "wt_d", "scale", "shift",
-                                                "invnorm", "wx_f", "wx_d", "wmax")] + [("d", WnDesc)]
-
-
 _prepack_sets = {}      # id(model) -> dict(signature, table, max_cout, entries, keep)
 _active_prepack = {}    # id(module) -> (split, wt_f, wt_d, scale, shift, invnorm), only inside `prepacked(...)`
 
@@ -1932,10 +1901,6 @@ def adam_step_flat_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, beta1, beta2, e
 # (scale exponent, slots for the maximum).  The buffers are zero-filled ONCE and reused: no kernel writes the border.
 # ------------------------------------------------------------------------------------------------
 P2_META_INTS = 128
-
-
-class P2Desc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("N", "C", "H", "W", "M", "relu")]
 
 
 class Planes:

@@ -21,11 +21,12 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import _lib
 from .ops import _call, _p, _stream
 
-SAMPLING = {"reference": 0, "exact": 1}      # VUNET_CROP_REFERENCE / VUNET_CROP_EXACT
+SAMPLING = {"reference": _lib.const("VUNET_CROP_REFERENCE"), "exact": _lib.const("VUNET_CROP_EXACT")}
 INPUT_MODES = {"none": 0, "transform": 1, "fid": 2}
-INCEPTION_SIZE = 299                         # VUNET_INCEPTION_SIZE
+INCEPTION_SIZE = _lib.const("VUNET_INCEPTION_SIZE")
 
 
 def _sampling(sampling: str) -> int:

@@ -17,10 +17,11 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import _lib
 from .ops import _call, _p, _stream
 
-MAX_JOINTS = 32          # VUNET_POSE_MAX_JOINTS
-EULER_MAX_D, EULER_MAX_TD = 512, 7680     # VUNET_POSE_EULER_MAX_D, VUNET_POSE_EULER_MAX_TD: one sequence's angles sit in LDS
+MAX_JOINTS = _lib.const("VUNET_POSE_MAX_JOINTS")
+EULER_MAX_D, EULER_MAX_TD = _lib.const("VUNET_POSE_EULER_MAX_D"), _lib.const("VUNET_POSE_EULER_MAX_TD")   # one sequence's angles sit in LDS
 
 
 class KinematicTree:

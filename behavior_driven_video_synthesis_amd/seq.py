@@ -27,16 +27,11 @@ from .ops import _call, _p, _stream
 MAX_ROWS = 64   # batch rows per launch (four 16-row MFMA tiles); larger batches are processed in chunks
 
 
-class SeqLinearDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "M", "K", "ldx", "act0", "act1", "nets", "shared_in", "S")]
-
-
-class SeqCouplingDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "C", "c1", "ld_in", "ld_out", "Mp", "reverse", "affine_on_src", "S")]
-
-
-class SeqLstmDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "H", "ldx", "hoff", "n", "ldraw")] + [("seq_stride", ctypes.c_int64)]
+SeqLinearDesc = _lib.struct("vunet_seq_linear_desc")
+SeqCouplingDesc = _lib.struct("vunet_seq_coupling_desc")
+SeqLstmDesc = _lib.struct("vunet_seq_lstm_desc")
+# ``layout`` bits of the tiled launchers (include/vunet_seq_tiled.h): tile-major weight images, operand, output
+TILED_W, TILED_X, TILED_Y = _lib.const("VUNET_SEQ_TILED_W"), _lib.const("VUNET_SEQ_TILED_X"), _lib.const("VUNET_SEQ_TILED_Y")
 
 
 def _up(x: int, m: int) -> int:
@@ -92,8 +87,8 @@ def padded_vector(b: torch.Tensor, n_pad: int) -> torch.Tensor:
 
 def linear(desc: SeqLinearDesc, w: Sequence[torch.Tensor], x: torch.Tensor, bias: Sequence[Optional[torch.Tensor]], y: torch.Tensor,
            layout: int = 0, y_rowmajor: Optional[torch.Tensor] = None):
-    """``layout`` (include/vunet_seq_tiled.h): 1 = tile-major weight images, 2 = tile-major operand, 4 = tile-major output
-    (``y_rowmajor``: and a row-major copy)."""
+    """``layout``: an OR of ``TILED_W`` (tile-major weight images), ``TILED_X`` (tile-major operand) and ``TILED_Y`` (tile-major
+    output; ``y_rowmajor``: and a row-major copy)."""
     if layout:
         _call("vunet_seq_linear_tiled", ctypes.byref(desc), layout, _p(w[0]), _p(w[1] if len(w) > 1 else None), _p(x), _p(bias[0]),
               _p(bias[1] if len(bias) > 1 else None), _p(y), _p(y_rowmajor), _stream())
@@ -229,10 +224,10 @@ class MlpGroup:
                 d = SeqLinearDesc(rows, m_pad, k_pad, ldx if li == 0 else k_pad, act[0], act[1], self.nets, shared,
                                   self.head_split if li == last else 1)
                 if li == last:
-                    linear(d, self.w[li], tile_bufs[(li - 1) % 2], self.b[li], dst, layout=2)
+                    linear(d, self.w[li], tile_bufs[(li - 1) % 2], self.b[li], dst, layout=TILED_X)
                 else:
                     linear(d, self.w[li], src if li == 0 else tile_bufs[(li - 1) % 2], self.b[li], tile_bufs[li % 2],
-                           layout=4 | (2 if li > 0 else 0), y_rowmajor=dst)
+                           layout=TILED_Y | (TILED_X if li > 0 else 0), y_rowmajor=dst)
                 src, shared = dst, 0
             return src
         for li, (m_pad, k_pad) in enumerate(self.dims):
@@ -241,7 +236,7 @@ class MlpGroup:
             d = SeqLinearDesc(rows, m_pad, k_pad, ldx if li == 0 else k_pad, act[0], act[1], self.nets, shared,
                               self.head_split if li == last else 1)
             if self.tiled:   # layer 0 reads the row-major state rows; the heads' output is the coupling kernel's, row-major
-                linear(d, self.wt[li], src, self.b[li], dst, layout=1 | (2 if li > 0 else 0) | (4 if li < last else 0))
+                linear(d, self.wt[li], src, self.b[li], dst, layout=TILED_W | (TILED_X if li > 0 else 0) | (TILED_Y if li < last else 0))
             else:
                 linear(d, self.w[li], src, self.b[li], dst)
             src, shared = dst, 0

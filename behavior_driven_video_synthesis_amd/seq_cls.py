@@ -15,26 +15,18 @@ from typing import Dict, List
 import numpy as np
 import torch
 
+from . import _lib
 from .ops import _call, _p, _stream
 from .seq_train import SeqAdamHp
 
-NIN, KP, HID, G3 = 51, 64, 256, 768
-OFF_WHH = G3 * KP
-OFF_BIH = OFF_WHH + G3 * HID
-OFF_BHH = OFF_BIH + G3
-OFF_FCW = OFF_BHH + G3
-OFF_FCB = OFF_FCW + HID
-P = OFF_FCB + 4
-MAX_BS = 1024
+NIN, KP, HID, G3 = (_lib.const("VUNET_CLS_" + n) for n in ("NIN", "KP", "H", "G"))
+OFF_WHH, OFF_BIH, OFF_BHH, OFF_FCW, OFF_FCB = (_lib.const("VUNET_CLS_OFF_" + n) for n in ("WHH", "BIH", "BHH", "FCW", "FCB"))
+P = _lib.const("VUNET_CLS_P")            # floats of one classifier's parameter block
+MAX_BS = _lib.const("VUNET_CLS_MAX_BS")
 KINDS = ("prior", "cross", "flow")
 
 
-class GemmDesc(ctypes.Structure):
-    """vunet_seq_cls_gemm (include/vunet_seq_cls.h)."""
-    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("mask", ctypes.c_void_p)] + [(f, ctypes.c_int64) for f in (
-                    "a_net", "a_m", "a_k", "b_net", "b_k", "b_n", "c_net", "c_m", "c_n", "c_split", "bias_net", "mask_net", "mask_m")] + [
-                (f, ctypes.c_int32) for f in ("M", "N", "K", "nets", "split", "relu", "accumulate", "pad")]
+GemmDesc = _lib.struct("vunet_seq_cls_gemm")
 
 
 def _ptr(t: torch.Tensor, off: int = 0) -> int:

@@ -34,28 +34,12 @@ STALE_WEIGHTS = ("the {}'s parameters were modified between this pass's forward 
                  "before the step, or run the forward again")
 
 
-class SeqAdamHp(ctypes.Structure):
-    _fields_ = [("lr_dev", ctypes.c_void_p), ("step_dev", ctypes.c_void_p), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
-                ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float), ("resolved_dev", ctypes.c_void_p)]
-
-
-class SeqDxDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "M", "K", "nets", "S", "ldw")]
-
-
-class SeqCouplingBwdDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "C", "c1", "ld_g", "ld_in", "ld_out", "ld_full", "Mp", "S", "n_sl", "ld_sl", "c1s")]
-
-
-class SeqDwLayer(ctypes.Structure):
-    _fields_ = ([(n, ctypes.c_void_p) for n in ("w", "m", "v", "g", "bias", "bm", "bv", "bg", "dz", "x")]
-                + [(n, ctypes.c_int32) for n in ("M", "K", "ldz", "ldx", "tile0", "tiles_k", "kv", "nchunk", "chunk_z", "chunk_x")]
-                + [("dx_raw", ctypes.c_void_p)])
-
-
-class SeqActnormLayer(ctypes.Structure):
-    _fields_ = ([(n, ctypes.c_void_p) for n in ("scale", "loc", "sm", "sv", "lm", "lv", "gs", "gl", "gfull", "out")]
-                + [(n, ctypes.c_int32) for n in ("ld", "pad")])
+SeqAdamHp = _lib.struct("vunet_seq_adam_hp")
+SeqDxDesc = _lib.struct("vunet_seq_dx_desc")
+SeqCouplingBwdDesc = _lib.struct("vunet_seq_coupling_bwd_desc")
+SeqDwLayer = _lib.struct("vunet_seq_dw_layer")             # (uploaded as a device table, as SeqActnormLayer)
+SeqActnormLayer = _lib.struct("vunet_seq_actnorm_layer")
+SeqCellBwdDesc = _lib.struct("vunet_seq_cell_bwd_desc")
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -730,10 +714,6 @@ def flow_autograd(engine: FlowTrainEngine, x: torch.Tensor):
 # ================================================================================================
 # the behaviour cVAE (first stage of experiments/behavior_net.py: :591-660)
 # ================================================================================================
-class SeqCellBwdDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "H", "n", "n_sl", "ld_sl", "hoff_sl", "first", "pad")] + [("gl_stride", ctypes.c_int64)]
-
-
 from .seq import BehaviorEngine, SeqLinearDesc, SeqLstmDesc, ACT_NONE, linear   # noqa: E402
 
 
@@ -1003,6 +983,7 @@ def behavior_autograd(engine: BehaviorTrainEngine, x1, x2, length, start_frame, 
 # ================================================================================================
 ACT_RELU_SEQ = 3   # vunet_seq_linear's plain ReLU
 REG_STEPS = 5      # inner regressor steps per cVAE step (:628)
+REG_T, REG_C = _lib.const("VUNET_SEQ_REG_T"), _lib.const("VUNET_SEQ_REG_C")   # fc4 is Linear(50, 128) on the one-hot of a step
 
 
 class RegressorTrainEngine:
@@ -1026,7 +1007,7 @@ class RegressorTrainEngine:
         if n > 64:
             raise ValueError(f"the regressor's output is padded to 64 rows: at most 64 pose dimensions, got {n}")
         self.reg = reg
-        self.H, self.H4, self.K5, self.n = H, H // 4, H // 4 + 128, n
+        self.H, self.H4, self.K5, self.n = H, H // 4, H // 4 + REG_C, n
         dev = reg.fc1.weight.device
         self.adam = AdamState(dev, lr, betas, eps, 0.0)
         self._plans: Dict[int, dict] = {}
@@ -1055,7 +1036,7 @@ class RegressorTrainEngine:
         S = {"fc5": dx_split(64, K5, 1), "fc3": dx_split(H4, H2, 1), "fc2": dx_split(H2, H, 1), "fc1": dx_split(H, H, 1)}
         p = dict(b_pad=bp, S=S, idx=torch.zeros(REG_STEPS, dtype=torch.int32, device=dev), mu=z(bp, H), h1=z(bp, H), h2=z(bp, H2),
                  h3=z(bp, H4), cat=z(bp, K5), pred=z(bp, 64), tgt=z(bp, self.n), dpred=z(bp, 64), dz1=z(bp, H), dz2=z(bp, H2),
-                 dz3=z(bp, H4), dzc=z(bp, 128), reg=z(6), adv=z(rows, H),
+                 dz3=z(bp, H4), dzc=z(bp, REG_C), reg=z(6), adv=z(rows, H),
                  raw=z(max(S["fc5"] * bp * K5, S["fc3"] * bp * H2, S["fc2"] * bp * H, S["fc1"] * bp * H)))
         # the update sweep: fc1, fc2, fc3, fc5 in one launch (fc4 has its own kernel)
         entries, tile = [], 0

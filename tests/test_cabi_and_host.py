@@ -542,36 +542,145 @@ def test_bench_graph_guard_prints_the_eager_line_when_the_replay_never_returns(t
     assert r.returncode == 0 and r.stdout.strip() == '{"metric": "graph"}'
 
 
-def test_ctypes_descriptors_match_the_c_structs(tmp_path):
-    """The host builds the kernels' descriptors with ctypes and uploads tables of them byte for byte: every mirrored struct of
-    include/*.h must have the C compiler's size and field offsets (gcc here; the same LP64 layout hipcc uses)."""
-    import ctypes
+def _stripped_headers():
+    """(comment-stripped text of include/*.h, their file names), read here and not through ``_lib``."""
+    from behavior_driven_video_synthesis_amd import _lib
+    names = [os.path.basename(h) for h in _lib.headers()]
+    txt = "\n".join(open(os.path.join(ROOT, "include", n)).read() for n in names)
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S), names
+
+
+def _run_c(tmp_path, stem, includes, body):
+    """Compile ``int main`` with ``body`` against include/ (gcc; the same LP64 layout hipcc uses) and return its output lines."""
     import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    from behavior_driven_video_synthesis_amd import seq, seq_train
+    lines = ["#include <stdio.h>", "#include <stddef.h>"] + [f'#include "{n}"' for n in includes] + ["int main(void) {"] + body + ["  return 0;", "}"]
+    src = tmp_path / (stem + ".c")
+    src.write_text("\n".join(lines))
+    exe = tmp_path / stem
+    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    return subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().splitlines()
+
+
+def test_ctypes_descriptors_match_the_c_structs(tmp_path):
+    """The host builds the kernels' descriptors with ctypes and uploads tables of them byte for byte: every struct of
+    include/*.h, as ``_lib`` derives it from the header text, must have the C compiler's size and field offsets -- and ``_lib``
+    must have derived every one of them (the ``typedef struct``s are counted here independently)."""
+    import ctypes
+    from behavior_driven_video_synthesis_amd import _lib, seq, seq_train
+    txt, names = _stripped_headers()
+    structs = _lib.structs()
+    n = len(re.findall(r"\btypedef\s+struct\b", txt))
+    print(f"{n} structs in include/*.h, {len(structs)} derived")
+    assert len(structs) == n and n >= 19, (n, sorted(structs))
     pairs = {"vunet_seq_linear_desc": seq.SeqLinearDesc, "vunet_seq_coupling_desc": seq.SeqCouplingDesc, "vunet_seq_lstm_desc": seq.SeqLstmDesc,
              "vunet_seq_adam_hp": seq_train.SeqAdamHp, "vunet_seq_dx_desc": seq_train.SeqDxDesc,
              "vunet_seq_coupling_bwd_desc": seq_train.SeqCouplingBwdDesc, "vunet_seq_dw_layer": seq_train.SeqDwLayer,
              "vunet_seq_actnorm_layer": seq_train.SeqActnormLayer, "vunet_seq_cell_bwd_desc": seq_train.SeqCellBwdDesc}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vunet_hip.h"', '#include "vunet_seq_train.h"', '#include "vunet_seq_tiled.h"',
-             "int main(void) {"]
-    for cname, cls in pairs.items():
-        lines.append(f'  printf("{cname} %zu", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'  printf(" %zu", offsetof({cname}, {fname}));')
-        lines.append('  printf("\\n");')
-    lines += ["  return 0;", "}"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
-    for line in out.strip().splitlines():
+    for cname, cls in pairs.items():          # (the classes the engines use are the derived ones)
+        assert structs[cname] is cls, cname
+    body = []
+    for cname, cls in structs.items():
+        assert cls._fields_, cname
+        body.append(f'  printf("{cname} %zu", sizeof({cname}));')
+        body += [f'  printf(" %zu", offsetof({cname}, {fname}));' for fname, _ in cls._fields_]
+        body.append('  printf("\\n");')
+    out = _run_c(tmp_path, "layout", names, body)
+    assert [line.split()[0] for line in out] == list(structs)
+    for line in out:
         cname, size, *offs = line.split()
-        cls = pairs[cname]
+        cls = structs[cname]
         assert ctypes.sizeof(cls) == int(size), (cname, ctypes.sizeof(cls), size)
         assert [getattr(cls, f).offset for f, _ in cls._fields_] == [int(o) for o in offs], cname
+
+
+def test_header_constants_match_the_c_preprocessor(tmp_path):
+    """``_lib.constants()``: every integer ``#define VUNET_*`` of include/*.h with the value the C compiler gives it."""
+    from behavior_driven_video_synthesis_amd import _lib
+    txt, names = _stripped_headers()
+    consts = _lib.constants()
+    out = _run_c(tmp_path, "consts", names, [f'  printf("{k} %lld\\n", (long long)({k}));' for k in consts])
+    assert {line.split()[0]: int(line.split()[1]) for line in out} == consts
+    assert consts["VUNET_ERR_UNSUPPORTED"] == -3 and consts["VUNET_SKELETON_COORD_LIMIT"] == 1 << 20
+    assert consts["VUNET_CLS_P"] == 768 * 64 + 768 * 256 + 768 + 768 + 256 + 4 and consts["VUNET_TUNE_COUNT"] == 10
+    assert _lib.const("VUNET_CLS_P") == consts["VUNET_CLS_P"]
+    guards = set(re.findall(r"^\s*#\s*ifndef\s+(\w+)", txt, flags=re.M))
+    assert len(guards) == len(names) and not guards & set(consts), guards & set(consts)
+    # every object-like VUNET_ macro with a body is a constant: nothing but the guards is left out of today's headers
+    defined = set(re.findall(r"^\s*#\s*define\s+(VUNET_\w+)", txt, flags=re.M))
+    assert defined - guards == set(consts)
+    with pytest.raises(KeyError):
+        _lib.const("VUNET_HIP_H")
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    """A declaration the struct grammar does not cover, or a macro body that is no integer expression, raises and names the
+    culprit: nothing is skipped silently.  (In-memory header texts: no file is written.)"""
+    from behavior_driven_video_synthesis_amd import _lib
+    ok = _lib.parse_structs("typedef struct a_desc { int32_t n, m; const float *x, *y; float* z; int64_t s; } a_desc;\n"
+                            "typedef struct b_item { a_desc d; void* p; } b_item;")
+    assert [f for f, _ in ok["a_desc"]._fields_] == ["n", "m", "x", "y", "z", "s"] and ok["b_item"]._fields_[0] == ("d", ok["a_desc"])
+    for member, what in (("my_type_t v;", "an unknown field type"), ("uint32_t flags : 3;", "a bitfield"),
+                         ("union { int32_t i; float f; } u;", "a union"), ("int32_t (*fn)(int32_t);", "a function pointer"),
+                         ("float a[4];", "an array"), ("later_desc d;", "a struct declared later"), ("unsigned int n;", "a two-word type")):
+        with pytest.raises(ValueError, match="bad_desc") as e:
+            _lib.parse_structs("typedef struct bad_desc { int32_t n; " + member + " } bad_desc;\n"
+                               "typedef struct later_desc { int32_t n; } later_desc;")
+        assert member.split(";")[0].split("{")[0].strip() in str(e.value), (what, str(e.value))
+    for body, what in (("vunet_max(1, 2)", "a function call"), ('"text"', "a string"), ("8 / 2", "an operator outside + - * <<"),
+                       ("16u", "a suffixed literal"), ("VUNET_LATER + 1", "a later macro"), ("(1 << 4", "an open parenthesis")):
+        with pytest.raises(ValueError, match="VUNET_BAD"):
+            _lib.parse_constants("#define VUNET_OK_ONE 1\n#define VUNET_BAD " + body + "\n#define VUNET_LATER 2\n")
+    got = _lib.parse_constants("#ifndef VUNET_X_H\n#define VUNET_X_H\n#define VUNET_F(x) ((x) + 1)\n#define OTHER_LIB \"s\"\n"
+                               "#define VUNET_EPS 1e-3f\n#define VUNET_HALF 0.5\n#define VUNET_A (0x10 << 2) - -3 * (VUNET_B0 + 1)\n"
+                               .replace("#define VUNET_A", "#define VUNET_B0 2\n#define VUNET_A"))
+    assert got == {"VUNET_B0": 2, "VUNET_A": 73}    # the guard, the function-like, the foreign and the float macros are no constants
+
+
+def test_modules_bind_the_derived_structs_and_constants():
+    """The public names the engines, tests and tools use are the header-derived classes and values, bound at import."""
+    import ctypes
+    import importlib
+    from behavior_driven_video_synthesis_amd import _lib
+    pkg = "behavior_driven_video_synthesis_amd."
+    structs = {"ops": dict(ConvDesc="vunet_conv_desc", WgradDesc="vunet_wgrad_desc", WgradItem="vunet_wgrad_item", WnDesc="vunet_wn_desc",
+                           WnBwdItem="vunet_wn_bwd_item", WnItem="vunet_wn_item", P2Desc="vunet_p2_desc"),
+               "seq": dict(SeqLinearDesc="vunet_seq_linear_desc", SeqCouplingDesc="vunet_seq_coupling_desc", SeqLstmDesc="vunet_seq_lstm_desc"),
+               "seq_train": dict(SeqAdamHp="vunet_seq_adam_hp", SeqDxDesc="vunet_seq_dx_desc", SeqCouplingBwdDesc="vunet_seq_coupling_bwd_desc",
+                                 SeqDwLayer="vunet_seq_dw_layer", SeqActnormLayer="vunet_seq_actnorm_layer",
+                                 SeqCellBwdDesc="vunet_seq_cell_bwd_desc"),
+               "seq_cls": dict(GemmDesc="vunet_seq_cls_gemm"),
+               "models.inception": dict(ConvgDesc="vunet_convg_desc", Pool2dDesc="vunet_pool2d_desc")}
+    assert sum(len(v) for v in structs.values()) == 19
+    for mod, names in structs.items():
+        m = importlib.import_module(pkg + mod)
+        for name, cname in names.items():
+            assert getattr(m, name) is _lib.struct(cname), (mod, name)
+            assert issubclass(getattr(m, name), ctypes.Structure), (mod, name)
+    consts = {"ops": dict(ACT_NONE="VUNET_ACT_NONE", ACT_ELU="VUNET_ACT_ELU", ACT_RELU="VUNET_ACT_RELU", ACT_SIGMOID="VUNET_ACT_SIGMOID",
+                          ACT_LRELU="VUNET_ACT_LRELU"),
+              "seq": dict(TILED_W="VUNET_SEQ_TILED_W", TILED_X="VUNET_SEQ_TILED_X", TILED_Y="VUNET_SEQ_TILED_Y"),
+              "seq_train": dict(REG_T="VUNET_SEQ_REG_T", REG_C="VUNET_SEQ_REG_C"),
+              "seq_cls": dict(NIN="VUNET_CLS_NIN", KP="VUNET_CLS_KP", HID="VUNET_CLS_H", G3="VUNET_CLS_G", OFF_WHH="VUNET_CLS_OFF_WHH",
+                              OFF_BIH="VUNET_CLS_OFF_BIH", OFF_BHH="VUNET_CLS_OFF_BHH", OFF_FCW="VUNET_CLS_OFF_FCW",
+                              OFF_FCB="VUNET_CLS_OFF_FCB", P="VUNET_CLS_P", MAX_BS="VUNET_CLS_MAX_BS"),
+              "neighbours": dict(QT_CODES="VUNET_NN_QT_CODES", QT_POSES="VUNET_NN_QT_POSES", CHUNK="VUNET_NN_CHUNK", MAX_H="VUNET_NN_MAX_H",
+                                 MAX_TN="VUNET_NN_MAX_TN"),
+              "pose_angles": dict(MAX_JOINTS="VUNET_POSE_MAX_JOINTS", EULER_MAX_D="VUNET_POSE_EULER_MAX_D",
+                                  EULER_MAX_TD="VUNET_POSE_EULER_MAX_TD"),
+              "inplane": dict(T2P="VUNET_INPLANE_T2P", T3P="VUNET_INPLANE_T3P", T4P="VUNET_INPLANE_T4P", T5P="VUNET_INPLANE_T5P",
+                              MAX_IDS="VUNET_INPLANE_MAX_IDS", MAX_PARTS="VUNET_INPLANE_MAX_PARTS"),
+              "latent_diag": dict(KS_MAX_LDS_N="VUNET_SEQ_KS_MAX_LDS_N"),
+              "fid_device": dict(_DOT_WORK="VUNET_F64_DOT_WORK"),
+              "person_crop": dict(INCEPTION_SIZE="VUNET_INCEPTION_SIZE"),
+              "models.inception": dict(SIZE="VUNET_INCEPTION_SIZE", KC="VUNET_CONVG_KC", MT="VUNET_CONVG_MT")}
+    for mod, names in consts.items():
+        m = importlib.import_module(pkg + mod)
+        for name, macro in names.items():
+            assert getattr(m, name) == _lib.const(macro) and type(getattr(m, name)) is int, (mod, name)
+    from behavior_driven_video_synthesis_amd import ops, person_crop
+    assert person_crop.SAMPLING == {"reference": _lib.const("VUNET_CROP_REFERENCE"), "exact": _lib.const("VUNET_CROP_EXACT")}
+    assert ops._TUNING_KEYS == {"split_force_nt": 0, "tiled_force_nt": 1, "force_small": 2, "blk_force_nt": 3, "parity_launches": 4,
+                                "blk_ws": 5, "wgrad_rowsplit": 6, "s2_fwd_f32": 7, "p2_form": 8, "p2_terms": 9}
 
 
 def test_input_gradient_slab_rule(monkeypatch):
