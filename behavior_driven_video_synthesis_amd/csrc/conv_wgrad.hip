@@ -11,6 +11,7 @@
 // Partial results go to per-split slabs (deterministic; summed by vunet_weightnorm_bwd).
 // The per-channel sum of dy (gradient of the folded shift) falls out of the A fragments.
 #include "common.h"
+#include "conv_wgrad_route.h"
 
 struct WgradArgs {
   vunet_wgrad_desc d;
@@ -132,93 +133,62 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a_in) {
   }
 }
 
-// conv_wgrad_thin.hip: 3x3 layers with <= 4 output channels at full resolution (out_conv): fp32 FMA kernel
-bool vunet_wgrad_thin_applicable(const vunet_wgrad_desc* d);
-int vunet_wgrad_thin_nslabs(const vunet_wgrad_desc* d);
-int vunet_wgrad_thin_name(const vunet_wgrad_desc* d, char* name, int len);
-int vunet_wgrad_thin_launch(const vunet_wgrad_desc* d, const float* x1, const float* dy, float* slabs, float* dshift,
-                            hipStream_t st);
-
-// conv_wgrad_tiled.hip: LDS halo-tile kernel for the 3x3 / stride-1 layers that carry the FLOPs
-bool vunet_wgrad_tiled_applicable(const vunet_wgrad_desc* d);
-int vunet_wgrad_tiled_nslabs(const vunet_wgrad_desc* d);
-int vunet_wgrad_tiled_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy,
-                             float* slabs, float* dshift, hipStream_t st);
-
-// conv_wgrad_x6.hip: the same layers on the bf16 matrix cores (fp32-accurate split-bf16 operands)
-bool vunet_wgrad_x6_applicable(const vunet_wgrad_desc* d);
-int vunet_wgrad_x6_nslabs(const vunet_wgrad_desc* d);
-int vunet_wgrad_x6_name(const vunet_wgrad_desc* d, char* name, int len);
-int vunet_wgrad_x6_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy, float* slabs,
-                          float* dshift, hipStream_t st);
-// conv_wgrad_h2.hip: the same layers with two scaled fp16 terms / three products (d->flags bit 1)
-int vunet_wgrad_h2_name(const vunet_wgrad_desc* d, char* name, int len);
-int vunet_wgrad_h2_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy, float* slabs,
-                          float* dshift, const float* amax_x, const float* amax_x2, const float* amax_dy, hipStream_t st);
-
-// conv_wgrad_direct.hip: small maps, stride 2, 1x1 on the fp16 matrix cores (d->flags bit 1), operands straight from global
-bool vunet_wgrad_direct_applicable(const vunet_wgrad_desc* d);
-int vunet_wgrad_direct_nslabs(const vunet_wgrad_desc* d);
-int vunet_wgrad_direct_name(const vunet_wgrad_desc* d, char* name, int len);
-int vunet_wgrad_direct_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy, float* slabs,
-                              float* dshift, const float* amax_x, const float* amax_x2, const float* amax_dy, hipStream_t st);
-
-int vunet_wgrad_direct_form(const vunet_wgrad_desc* d);
-int vunet_wgrad_direct_launch_multi(const vunet_wgrad_item* items, const int* idx, int cnt, hipStream_t st);
-
-// ---- the routing decision of one weight gradient: wgrad_route() computes it, everything below reads it
-enum WgradFamily { WGRAD_X6, WGRAD_H2, WGRAD_DIRECT, WGRAD_THIN, WGRAD_TILED, WGRAD_GENERIC };
-
-struct WgradRoute {
-  int family;
-  int WM, WN, NTW;   // WGRAD_GENERIC: the instantiation of conv_wgrad_kernel
-  int nslabs;        // partial-result slabs the caller allocates (vunet_conv2d_wgrad_nsplit)
-};
-
+// ---- the plan: the first family that takes the problem fills it; everything below reads it
 static WgradRoute wgrad_route(const vunet_wgrad_desc* d) {
-  WgradRoute r = {WGRAD_GENERIC, 0, 0, 0, 0};
-  if (vunet_wgrad_x6_applicable(d)) {
-    r.family = (d->flags & 2) ? WGRAD_H2 : WGRAD_X6, r.nslabs = vunet_wgrad_x6_nslabs(d);
-  } else if (vunet_wgrad_direct_applicable(d)) {
-    r.family = WGRAD_DIRECT, r.nslabs = vunet_wgrad_direct_nslabs(d);
-  } else if (vunet_wgrad_thin_applicable(d)) {
-    r.family = WGRAD_THIN, r.nslabs = vunet_wgrad_thin_nslabs(d);
-  } else if (vunet_wgrad_tiled_applicable(d)) {
-    r.family = WGRAD_TILED, r.nslabs = vunet_wgrad_tiled_nslabs(d);
-  } else {
-    const int T = d->KH * d->KW, Ctot = d->C1 + d->C2;
-    r.WM = d->Cout > 64 ? 4 : (d->Cout > 32 ? 2 : 1);
-    if (T > 9 && r.WM == 4) r.WM = 2;
-    r.WN = 4 / r.WM;
-    r.NTW = T == 1 ? 1 : (T <= 9 ? (r.WM == 4 ? 9 : (r.WM == 2 ? 5 : 3)) : (r.WM == 2 ? 8 : 4));
-    const int nchunks = (int)(((int64_t)d->N * d->Ho * d->Wo + 31) / 32);
-    const int ciblocks = (Ctot + 31) / 32, coblocks = (d->Cout + 32 * r.WM - 1) / (32 * r.WM);
-    int S = 768 / (ciblocks * coblocks);
-    if (S > nchunks) S = nchunks;  // small maps: one 32-pixel chunk per workgroup rather than a serial chunk loop
-    // (capping S to bound the slab volume was measured slower: the serial chunk loop costs more than the reduce)
-    if (S < 1) S = 1;
-    if (S > 256) S = 256;
-    r.nslabs = S;
-  }
+  WgradRoute r = {};
+  if (vunet_wgrad_x6_plan(d, &r) || vunet_wgrad_direct_plan(d, &r) || vunet_wgrad_thin_plan(d, &r) || vunet_wgrad_tiled_plan(d, &r))
+    return r;
+  r.family = WGRAD_GENERIC;
+  const int T = d->KH * d->KW;
+  r.WM = d->Cout > 64 ? 4 : (d->Cout > 32 ? 2 : 1);
+  if (T > 9 && r.WM == 4) r.WM = 2;
+  r.WN = 4 / r.WM;
+  r.NTW = T == 1 ? 1 : (T <= 9 ? (r.WM == 4 ? 9 : (r.WM == 2 ? 5 : 3)) : (r.WM == 2 ? 8 : 4));
+  r.ntiles = (int)(((int64_t)d->N * d->Ho * d->Wo + 31) / 32);   // 32-pixel chunks
+  r.ciblocks = (d->C1 + d->C2 + 31) / 32, r.coblocks = (d->Cout + 32 * r.WM - 1) / (32 * r.WM);
+  int S = 768 / (r.ciblocks * r.coblocks);
+  if (S > r.ntiles) S = r.ntiles;  // small maps: one 32-pixel chunk per workgroup rather than a serial chunk loop
+  // (capping S to bound the slab volume was measured slower: the serial chunk loop costs more than the reduce)
+  if (S < 1) S = 1;
+  r.nslabs = S > 256 ? 256 : S;
   return r;
 }
 
+// character for character what the profiler keys and the tests hold
+int wgrad_route_name(const WgradRoute& r, char* name, int len) {
+  switch (r.family) {
+    case WGRAD_X6: return snprintf(name, len, "conv_wgrad_x6_kernel<%d>", r.MTW);
+    case WGRAD_H2: return snprintf(name, len, "conv_wgrad_h2_kernel<%d>", r.MTW);
+    case WGRAD_DIRECT:
+      if (r.s2_ncot) return snprintf(name, len, "conv_wgrad_s2_kernel");   // (bare: the same for its three instantiations)
+      return snprintf(name, len, "conv_wgrad_direct_kernel<%d, %s, %d>", r.S, r.W4 ? "true" : "false", r.T);
+    case WGRAD_THIN: return snprintf(name, len, "conv_wgrad_thin_kernel");
+    case WGRAD_TILED: return snprintf(name, len, "conv_wgrad_tiled_kernel<%d, %d, %d, %d>", r.MTW, r.TH, r.KS, r.ST);
+    default: return snprintf(name, len, "conv_wgrad_kernel<%d, %d, %d>", r.WM, r.WN, r.NTW);
+  }
+}
+
 // layers whose weight gradient runs on the direct kernel and is a short launch: batched (vunet_conv2d_wgrad_multi)
+static bool wgrad_route_batchable(const WgradRoute& r, const vunet_wgrad_desc* d) {
+  // (A/B: VUNET_WGRAD_BATCH_PIX moves the bound between "latency" and "work"; read once per process)
+  static const int64_t bound = [] { const char* e = getenv("VUNET_WGRAD_BATCH_PIX"); return e ? atoll(e) : WGRAD_BATCH_PIX; }();
+  return r.family == WGRAD_DIRECT && (int64_t)d->N * d->Ho * d->Wo <= bound;
+}
+
 extern "C" int vunet_conv2d_wgrad_batchable(const vunet_wgrad_desc* d) {
-  if (!d || wgrad_route(d).family != WGRAD_DIRECT) return 0;
-  // (A/B: VUNET_WGRAD_BATCH_PIX moves the bound between "latency" and "work")
-  static const int64_t bound = [] { const char* e = getenv("VUNET_WGRAD_BATCH_PIX"); return e ? atoll(e) : 16384ll; }();
-  return (int64_t)d->N * d->Ho * d->Wo <= bound ? 1 : 0;
+  return d && wgrad_route_batchable(wgrad_route(d), d) ? 1 : 0;
 }
 
 extern "C" int vunet_conv2d_wgrad_multi(const vunet_wgrad_item* items, int32_t n, void* stream) {
   if (n < 0 || (n > 0 && !items)) return VUNET_ERR_ARG;
   constexpr int MAXN = 256;
   if (n > MAXN) return VUNET_ERR_ARG;
+  WgradRoute routes[MAXN];
   int form[MAXN], idx[MAXN];
   for (int i = 0; i < n; ++i) {
-    if (!vunet_conv2d_wgrad_batchable(&items[i].d) || items[i].d.nsplit < 1) return VUNET_ERR_UNSUPPORTED;
-    form[i] = vunet_wgrad_direct_form(&items[i].d);
+    routes[i] = wgrad_route(&items[i].d);
+    if (!wgrad_route_batchable(routes[i], &items[i].d) || items[i].d.nsplit < 1) return VUNET_ERR_UNSUPPORTED;
+    form[i] = routes[i].form;
   }
   for (int i = 0; i < n; ++i) {
     if (form[i] < 0) continue;           // already launched with an earlier item of its form
@@ -226,45 +196,56 @@ extern "C" int vunet_conv2d_wgrad_multi(const vunet_wgrad_item* items, int32_t n
     const int f = form[i];
     for (int k = i; k < n; ++k)
       if (form[k] == f) { idx[cnt++] = k; form[k] = -1; }
-    const int rc = vunet_wgrad_direct_launch_multi(items, idx, cnt, (hipStream_t)stream);
+    const int rc = vunet_wgrad_direct_launch_multi(items, routes, idx, cnt, (hipStream_t)stream);
     if (rc != VUNET_OK) return rc;
   }
   return VUNET_OK;
 }
 
 extern "C" int vunet_conv2d_wgrad_wants_split(const vunet_wgrad_desc* d) {
-  return d && wgrad_route(d).family <= WGRAD_DIRECT ? 1 : 0;
+  return d && wgrad_route_wants_split(wgrad_route(d)) ? 1 : 0;
 }
 
 extern "C" int vunet_conv2d_wgrad_variant(const vunet_wgrad_desc* d, char* name, int32_t len) {
   if (!d || !name || len < 8) return VUNET_ERR_ARG;
-  const WgradRoute r = wgrad_route(d);
-  switch (r.family) {
-    case WGRAD_X6: vunet_wgrad_x6_name(d, name, len); break;
-    case WGRAD_H2: vunet_wgrad_h2_name(d, name, len); break;
-    case WGRAD_DIRECT: vunet_wgrad_direct_name(d, name, len); break;
-    case WGRAD_THIN: vunet_wgrad_thin_name(d, name, len); break;
-    case WGRAD_TILED:
-      if (d->stride == 2) snprintf(name, len, "conv_wgrad_tiled_kernel<2, 2, 3, 2>");
-      else snprintf(name, len, "conv_wgrad_tiled_kernel<%d, 4, %d, 1>", d->Cout >= 64 ? 2 : 1, d->KH);
-      break;
-    default: snprintf(name, len, "conv_wgrad_kernel<%d, %d, %d>", r.WM, r.WN, r.NTW);
-  }
+  wgrad_route_name(wgrad_route(d), name, len);
   return VUNET_OK;
 }
 
 extern "C" int vunet_conv2d_wgrad_nsplit(const vunet_wgrad_desc* d) { return d ? wgrad_route(d).nslabs : VUNET_ERR_ARG; }
 
 template <int WM, int WN, int NTW>
-static int launch_wgrad(const WgradArgs& wa, hipStream_t st) {
-  const int ciblocks = (wa.Ctot + 31) / 32, coblocks = (wa.d.Cout + 32 * WM - 1) / (32 * WM);
-  dim3 grid(wa.d.nsplit, ciblocks, coblocks), block(256);
+static int launch_wgrad(const WgradRoute& r, const WgradArgs& wa, hipStream_t st) {
+  dim3 grid(wa.d.nsplit, r.ciblocks, r.coblocks), block(256);
   const size_t lds = (size_t)(32 * WM + wa.T * 32) * 33 * sizeof(float);
   if (lds > 64 * 1024)
     hipFuncSetAttribute((const void*)conv_wgrad_kernel<WM, WN, NTW>, hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)lds);
   VUNET_LAUNCH((conv_wgrad_kernel<WM, WN, NTW>), grid, block, lds, st, wa);
   return vunet_check_launch();
+}
+
+static int wgrad_generic_launch(const WgradRoute& r, const vunet_wgrad_item& it, hipStream_t st) {
+  const vunet_wgrad_desc* d = &it.d;
+  WgradArgs wa;
+  wgrad_fill(wa, it);
+  wa.T = d->KH * d->KW;
+  wa.NP = d->N * d->Ho * d->Wo;
+  wa.nchunks = r.ntiles;
+  wa.HoWo = d->Ho * d->Wo;
+  wa.HsWs = d->Hs * d->Ws;
+  wa.cps = (wa.nchunks + d->nsplit - 1) / d->nsplit;
+  if (wa.T > 16) return VUNET_ERR_UNSUPPORTED;
+  switch (r.WM * 16 + r.NTW) {   // <WM, WN = 4 / WM, NTW> as wgrad_route picked them
+    case 4 * 16 + 1: return launch_wgrad<4, 1, 1>(r, wa, st);
+    case 2 * 16 + 1: return launch_wgrad<2, 2, 1>(r, wa, st);
+    case 1 * 16 + 1: return launch_wgrad<1, 4, 1>(r, wa, st);
+    case 4 * 16 + 9: return launch_wgrad<4, 1, 9>(r, wa, st);
+    case 2 * 16 + 5: return launch_wgrad<2, 2, 5>(r, wa, st);
+    case 1 * 16 + 3: return launch_wgrad<1, 4, 3>(r, wa, st);
+    case 2 * 16 + 8: return launch_wgrad<2, 2, 8>(r, wa, st);
+    default: return launch_wgrad<1, 4, 4>(r, wa, st);
+  }
 }
 
 extern "C" int vunet_conv2d_wgrad_a2(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy,
@@ -279,37 +260,14 @@ extern "C" int vunet_conv2d_wgrad_a2(const vunet_wgrad_desc* d, const float* x1,
   hipStream_t st = (hipStream_t)stream;
   const WgradRoute r = wgrad_route(d);
   if ((r.family == WGRAD_H2 || r.family == WGRAD_DIRECT) && (!amax_x || !amax_dy)) return VUNET_ERR_ARG;
+  const vunet_wgrad_item it = {*d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy};
   switch (r.family) {
-    case WGRAD_X6: return vunet_wgrad_x6_launch(d, x1, x2, dy, slabs, dshift, st);
-    case WGRAD_H2: return vunet_wgrad_h2_launch(d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy, st);
-    case WGRAD_DIRECT: return vunet_wgrad_direct_launch(d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy, st);
-    case WGRAD_THIN: return vunet_wgrad_thin_launch(d, x1, dy, slabs, dshift, st);
-    case WGRAD_TILED: return vunet_wgrad_tiled_launch(d, x1, x2, dy, slabs, dshift, st);
-    default: break;
-  }
-  WgradArgs wa;
-  wa.d = *d;
-  wa.x1 = x1; wa.x2 = x2; wa.dy = dy; wa.slabs = slabs; wa.dshift = dshift;
-  wa.T = d->KH * d->KW;
-  wa.Ctot = d->C1 + d->C2;
-  wa.Coutp = (d->Cout + 31) / 32 * 32;
-  wa.NP = d->N * d->Ho * d->Wo;
-  wa.nchunks = (int)(((int64_t)wa.NP + 31) / 32);
-  wa.HoWo = d->Ho * d->Wo;
-  wa.HsWs = d->Hs * d->Ws;
-  wa.cps = (wa.nchunks + d->nsplit - 1) / d->nsplit;
-  wa.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
-  wa.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
-  if (wa.T > 16) return VUNET_ERR_UNSUPPORTED;
-  switch (r.WM * 16 + r.NTW) {   // <WM, WN = 4 / WM, NTW> as wgrad_route picked them
-    case 4 * 16 + 1: return launch_wgrad<4, 1, 1>(wa, st);
-    case 2 * 16 + 1: return launch_wgrad<2, 2, 1>(wa, st);
-    case 1 * 16 + 1: return launch_wgrad<1, 4, 1>(wa, st);
-    case 4 * 16 + 9: return launch_wgrad<4, 1, 9>(wa, st);
-    case 2 * 16 + 5: return launch_wgrad<2, 2, 5>(wa, st);
-    case 1 * 16 + 3: return launch_wgrad<1, 4, 3>(wa, st);
-    case 2 * 16 + 8: return launch_wgrad<2, 2, 8>(wa, st);
-    default: return launch_wgrad<1, 4, 4>(wa, st);
+    case WGRAD_X6: return vunet_wgrad_x6_launch(r, it, st);
+    case WGRAD_H2: return vunet_wgrad_h2_launch(r, it, st);
+    case WGRAD_DIRECT: return vunet_wgrad_direct_launch(r, it, st);
+    case WGRAD_THIN: return vunet_wgrad_thin_launch(r, it, st);
+    case WGRAD_TILED: return vunet_wgrad_tiled_launch(r, it, st);
+    default: return wgrad_generic_launch(r, it, st);
   }
 }
 

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_wgrad_route.h"
 #include "split_h2.h"
 
 struct WgradDirectArgs {
@@ -562,17 +563,19 @@ __global__ __launch_bounds__(64 * NWAVE) void conv_wgrad_s2_kernel(const WgradDi
 
 // the LDS-staged form takes the stride-2 layers that are launched on their own (above the batching bound), with whole channel
 // tiles; VUNET_TUNE_WGRAD_ROWSPLIT = 3 keeps them on the direct kernel (A/B, tests)
-static bool s2_staged_ok(const vunet_wgrad_desc* d) {
-  if (g_vunet_tune[VUNET_TUNE_WGRAD_ROWSPLIT] == 3) return false;
-  if (!(d->flags & 2) || (d->flags & 1)) return false;
-  if (d->KH != 3 || d->KW != 3 || d->stride != 2 || d->pad != 1) return false;
-  if (d->Ws != 2 * d->Wo || d->Hs != 2 * d->Ho || d->Wo % 16) return false;
-  if (d->C1 % 32 || d->C2 % 32 || d->Cout % 32) return false;
+// -> its output-channel tiles (1, 2, 4: one instantiation each), 0: not taken
+static int s2_staged_ncot(const vunet_wgrad_desc* d) {
+  if (g_vunet_tune[VUNET_TUNE_WGRAD_ROWSPLIT] == 3) return 0;
+  if (!(d->flags & 2) || (d->flags & 1)) return 0;
+  if (d->KH != 3 || d->KW != 3 || d->stride != 2 || d->pad != 1) return 0;
+  if (d->Ws != 2 * d->Wo || d->Hs != 2 * d->Ho || d->Wo % 16) return 0;
+  if (d->C1 % 32 || d->C2 % 32 || d->Cout % 32) return 0;
   const int ncot = d->Cout / 32;
-  if (ncot != 1 && ncot != 2 && ncot != 4) return false;
+  if (ncot != 1 && ncot != 2 && ncot != 4) return 0;
   // (the batching bound of vunet_conv2d_wgrad_batchable, conv_wgrad.hip: layers at or below it share a launch on the direct kernel.
-  //  Both kernels accept any split count, so a bound moved by VUNET_WGRAD_BATCH_PIX only shifts which of the two runs a layer.)
-  return (int64_t)d->N * d->Ho * d->Wo > 16384;
+  //  The constant, not VUNET_WGRAD_BATCH_PIX: both kernels accept any split count, so a bound moved by the variable only shifts
+  //  which of the two runs a layer.)
+  return (int64_t)d->N * d->Ho * d->Wo > WGRAD_BATCH_PIX ? ncot : 0;
 }
 
 static int s2_staged_nslabs(const vunet_wgrad_desc* d) {
@@ -603,8 +606,30 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_direct_multi_kernel(const W
   wgrad_direct_body<S, W4, T>(a, local % b.gx[i], local / b.gx[i]);
 }
 
+// The kernels of this unit, in the order the code object has always held them (the launches below would instantiate them
+// in the order of their table; tools/device_asm_diff.sh compares whole files)
+#define WD_KERNEL(...) template __global__ void __VA_ARGS__
+WD_KERNEL(conv_wgrad_direct_multi_kernel<1, false, 1>(const WgradDirectBatch));
+WD_KERNEL(conv_wgrad_direct_multi_kernel<1, true, 9>(const WgradDirectBatch));
+WD_KERNEL(conv_wgrad_direct_multi_kernel<2, true, 9>(const WgradDirectBatch));
+WD_KERNEL(conv_wgrad_direct_multi_kernel<1, false, 9>(const WgradDirectBatch));
+WD_KERNEL(conv_wgrad_direct_multi_kernel<1, false, 3>(const WgradDirectBatch));
+WD_KERNEL(conv_wgrad_direct_multi_kernel<2, false, 9>(const WgradDirectBatch));
+WD_KERNEL(conv_wgrad_direct_multi_kernel<2, false, 3>(const WgradDirectBatch));
+WD_KERNEL(conv_wgrad_s2_kernel<3, 1, 1>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_s2_kernel<6, 1, 2>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_s2_kernel<6, 2, 4>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_direct_kernel<2, false, 3>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_direct_kernel<1, false, 3>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_direct_kernel<1, false, 1>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_direct_kernel<1, true, 9>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_direct_kernel<2, true, 9>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_direct_kernel<1, false, 9>(const WgradDirectArgs));
+WD_KERNEL(conv_wgrad_direct_kernel<2, false, 9>(const WgradDirectArgs));
+#undef WD_KERNEL
+
 // ---- host side ------------------------------------------------------------------------------------------------------
-// geometry class: 0 not covered; else (S, W4, T) packed
+// geometry class: 0 not covered; 1: 1x1; 2 / 3: 3x3 on 4-wide output maps at stride 1 / 2; 4 / 5: 3x3 on maps 8k wide
 static int direct_class(const vunet_wgrad_desc* d) {
   if (!(d->flags & 2) || (d->flags & 1)) return 0;   // the fp16 scheme only
   if (d->C1 <= 0 || d->Cout <= 0 || (d->C2 > 0 && d->C1 % 32 != 0)) return 0;
@@ -621,21 +646,6 @@ static int direct_class(const vunet_wgrad_desc* d) {
   return 0;
 }
 
-bool vunet_wgrad_direct_applicable(const vunet_wgrad_desc* d) { return direct_class(d) != 0; }
-
-static void direct_geometry(const vunet_wgrad_desc* d, WgradDirectArgs& a) {
-  const int cls = direct_class(d);
-  a.Ctot = d->C1 + d->C2;
-  a.Coutp = (d->Cout + 31) / 32 * 32;
-  a.ncot = a.Coutp / 32;
-  if (cls == 1) { a.opr = 0; a.opi = d->Hs * d->Ws / 8; }
-  else if (cls == 2 || cls == 3) { a.opr = 0; a.opi = d->Ho / 2; }
-  else { a.opr = d->Wo / 8; a.opi = d->Ho * a.opr; }
-  a.noct = d->N * a.opi;
-}
-
-// Pixel splits: about 2048 waves in all (eight per CU), every wave at least four K steps (eight octets) where the
-// problem has them; few splits for the tiny maps (a slab is written per split).
 // kernel-row split (three waves per (split, co tile), one kernel row each): every 3x3 layer on maps >= 8 wide.  Round 4 split
 // the stride-2 layers only; same-box A/B runs of the whole step at the end of round 5 (profiles/r05_rowsplit_ab.txt: five
 // alternating pairs on two boxes) put the stride-1 direct layers on it too: + 0.4 - 0.7 %.
@@ -647,119 +657,104 @@ static bool direct_rowsplit(int cls) {
   return cls == 5 || (knob != 4 && cls == 4);
 }
 
-int vunet_wgrad_direct_nslabs(const vunet_wgrad_desc* d) {
-  if (s2_staged_ok(d)) return s2_staged_nslabs(d);
-  WgradDirectArgs a;
-  direct_geometry(d, a);
-  const int ncit = (a.Ctot + 31) / 32;
-  int S = 2048 / (a.ncot * ncit * (direct_rowsplit(direct_class(d)) ? 3 : 1));
-  const int by_work = (a.noct + 7) / 8;
+// THE table from a form (class * 2 + kernel-row split) to its conv_wgrad_direct_kernel<S, W4, T>: f(DirectInst<S, W4, T>{});
+// false for a form without a kernel.  The plan's (S, W4, T), the single launch and the batch launch all go through it.
+template <int S_, bool W4_, int T_>
+struct DirectInst { static constexpr int S = S_; static constexpr bool W4 = W4_; static constexpr int T = T_; };
+template <class F>
+static bool direct_with_form(int form, F&& f) {
+  switch (form) {
+    case 2: f(DirectInst<1, false, 1>{}); return true;
+    case 4: f(DirectInst<1, true, 9>{}); return true;
+    case 6: f(DirectInst<2, true, 9>{}); return true;
+    case 8: f(DirectInst<1, false, 9>{}); return true;
+    case 9: f(DirectInst<1, false, 3>{}); return true;
+    case 10: f(DirectInst<2, false, 9>{}); return true;
+    case 11: f(DirectInst<2, false, 3>{}); return true;
+    default: return false;
+  }
+}
+
+bool vunet_wgrad_direct_plan(const vunet_wgrad_desc* d, WgradRoute* r) {
+  const int cls = direct_class(d);
+  if (!cls) return false;
+  r->family = WGRAD_DIRECT;
+  r->cls = cls;
+  r->rowsplit = direct_rowsplit(cls) ? 1 : 0;
+  r->form = cls * 2 + r->rowsplit;
+  direct_with_form(r->form, [&](auto k) { r->S = k.S; r->W4 = k.W4; r->T = k.T; });
+  r->s2_ncot = s2_staged_ncot(d);
+  r->ciblocks = (d->C1 + d->C2 + 31) / 32;
+  r->ncot = (d->Cout + 31) / 32;
+  if (cls == 1) { r->opr = 0; r->opi = d->Hs * d->Ws / 8; }
+  else if (cls == 2 || cls == 3) { r->opr = 0; r->opi = d->Ho / 2; }
+  else { r->opr = d->Wo / 8; r->opi = d->Ho * r->opr; }
+  r->noct = d->N * r->opi;
+  if (r->s2_ncot) {
+    r->nslabs = s2_staged_nslabs(d);
+    return true;
+  }
+  // Pixel splits: about 2048 waves in all (eight per CU), every wave at least four K steps (eight octets) where the
+  // problem has them; few splits for the tiny maps (a slab is written per split).
+  int S = 2048 / (r->ncot * r->ciblocks * (r->rowsplit ? 3 : 1));
+  const int by_work = (r->noct + 7) / 8;
   if (S > by_work) S = by_work;
   if (S < 1) S = 1;
   const int cap = d->KH == 1 ? 2048 : 512;   // (a 1x1 slab is one 4 KB tile: many splits cost nothing)
-  if (S > cap) S = cap;
-  return S;
-}
-
-int vunet_wgrad_direct_name(const vunet_wgrad_desc* d, char* name, int len) {
-  if (s2_staged_ok(d)) return snprintf(name, len, "conv_wgrad_s2_kernel");
-  const int cls = direct_class(d);
-  const int S = (cls == 3 || cls == 5) ? 2 : 1, W4 = (cls == 2 || cls == 3), T = cls == 1 ? 1 : (direct_rowsplit(cls) ? 3 : 9);
-  return snprintf(name, len, "conv_wgrad_direct_kernel<%d, %s, %d>", S, W4 ? "true" : "false", T);
+  r->nslabs = S > cap ? cap : S;
+  return true;
 }
 
 // the kernel's argument block and grid of one layer
-static void direct_fill(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy, float* slabs, float* dshift,
-                        const float* amax_x, const float* amax_x2, const float* amax_dy, WgradDirectArgs& a, int& gx, int& gy) {
-  a.d = *d;
-  a.x1 = x1; a.x2 = x2; a.dy = dy; a.slabs = slabs; a.dshift = dshift; a.amax_x = amax_x; a.amax_x2 = amax_x2; a.amax_dy = amax_dy;
-  direct_geometry(d, a);
-  a.ops = (a.noct + d->nsplit - 1) / d->nsplit;
+static void direct_fill(const WgradRoute& r, const vunet_wgrad_item& it, WgradDirectArgs& a, int& gx, int& gy) {
+  wgrad_fill(a, it);
+  a.amax_x = it.amax_x; a.amax_x2 = it.amax_x2; a.amax_dy = it.amax_dy;
+  a.ncot = r.ncot; a.noct = r.noct; a.opr = r.opr; a.opi = r.opi;
+  a.ops = (r.noct + it.d.nsplit - 1) / it.d.nsplit;
   a.ops = (a.ops + 1) & ~1;   // whole K steps of two octets
-  a.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
-  a.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
-  const int units = d->nsplit * a.ncot * (direct_rowsplit(direct_class(d)) ? 3 : 1);
+  const int units = it.d.nsplit * r.ncot * (r.rowsplit ? 3 : 1);
   gx = (units + 3) / 4;
-  gy = (a.Ctot + 31) / 32;
+  gy = r.ciblocks;
 }
 
-// form of a layer's kernel: class * 2 + (kernel-row split)
-static int direct_form(const vunet_wgrad_desc* d) {
-  const int cls = direct_class(d);
-  return cls ? cls * 2 + (direct_rowsplit(cls) ? 1 : 0) : 0;
-}
-
-template <int S, bool W4, int T>
-static void direct_launch_batch(const WgradDirectBatch& b, hipStream_t st) {
-  VUNET_LAUNCH((conv_wgrad_direct_multi_kernel<S, W4, T>), dim3((unsigned)b.start[b.n]), dim3(256), 0, st, b);
-}
-
-// items[i] for i in idx[0..cnt): all of one form
-int vunet_wgrad_direct_launch_multi(const vunet_wgrad_item* items, const int* idx, int cnt, hipStream_t st) {
-  if (cnt < 1) return VUNET_OK;
-  const int form = direct_form(&items[idx[0]].d);
-  if (!form) return VUNET_ERR_UNSUPPORTED;
+int vunet_wgrad_direct_launch_multi(const vunet_wgrad_item* items, const WgradRoute* routes, const int* idx, int cnt, hipStream_t st) {
   for (int at = 0; at < cnt; at += WD_MULTI) {
     WgradDirectBatch b;
     b.n = cnt - at < WD_MULTI ? cnt - at : WD_MULTI;
     b.start[0] = 0;
     for (int k = 0; k < b.n; ++k) {
       const vunet_wgrad_item& it = items[idx[at + k]];
-      if (direct_form(&it.d) != form) return VUNET_ERR_ARG;
       if (!it.x1 || !it.dy || !it.slabs || !it.dshift || !it.amax_x || !it.amax_dy || (it.d.C2 > 0 && !it.x2)) return VUNET_ERR_ARG;
       int gx, gy;
-      direct_fill(&it.d, it.x1, it.x2, it.dy, it.slabs, it.dshift, it.amax_x, it.amax_x2, it.amax_dy, b.it[k], gx, gy);
+      direct_fill(routes[idx[at + k]], it, b.it[k], gx, gy);
       b.gx[k] = gx;
       b.start[k + 1] = b.start[k] + gx * gy;
     }
     for (int k = b.n; k < WD_MULTI; ++k) { b.it[k] = b.it[0]; b.gx[k] = 1; b.start[k + 1] = b.start[b.n]; }
-    switch (form) {
-      case 2: direct_launch_batch<1, false, 1>(b, st); break;
-      case 4: direct_launch_batch<1, true, 9>(b, st); break;
-      case 6: direct_launch_batch<2, true, 9>(b, st); break;
-      case 8: direct_launch_batch<1, false, 9>(b, st); break;
-      case 9: direct_launch_batch<1, false, 3>(b, st); break;
-      case 10: direct_launch_batch<2, false, 9>(b, st); break;
-      case 11: direct_launch_batch<2, false, 3>(b, st); break;
-      default: return VUNET_ERR_UNSUPPORTED;
-    }
+    const bool known = direct_with_form(routes[idx[at]].form, [&](auto k) {
+      VUNET_LAUNCH((conv_wgrad_direct_multi_kernel<k.S, k.W4, k.T>), dim3((unsigned)b.start[b.n]), dim3(256), 0, st, b);
+    });
+    if (!known) return VUNET_ERR_UNSUPPORTED;
     const int rc = vunet_check_launch();
     if (rc != VUNET_OK) return rc;
   }
   return VUNET_OK;
 }
 
-int vunet_wgrad_direct_form(const vunet_wgrad_desc* d) { return direct_form(d); }
-
-int vunet_wgrad_direct_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy, float* slabs,
-                              float* dshift, const float* amax_x, const float* amax_x2, const float* amax_dy, hipStream_t st) {
-  const int cls = direct_class(d);
-  if (!cls) return VUNET_ERR_UNSUPPORTED;
+int vunet_wgrad_direct_launch(const WgradRoute& r, const vunet_wgrad_item& it, hipStream_t st) {
   WgradDirectArgs a;
   int gx, gy;
-  direct_fill(d, x1, x2, dy, slabs, dshift, amax_x, amax_x2, amax_dy, a, gx, gy);
-  if (s2_staged_ok(d)) {
-    const int ncot = d->Cout / 32;
-    dim3 grid((unsigned)d->nsplit, (unsigned)((d->C1 + d->C2) / 32));
-    const size_t lds = (size_t)S2Lds::XBYTES + (size_t)ncot * S2Lds::DYCOT;
-    if (ncot == 1) VUNET_LAUNCH((conv_wgrad_s2_kernel<3, 1, 1>), grid, dim3(192), lds, st, a);
-    else if (ncot == 2) VUNET_LAUNCH((conv_wgrad_s2_kernel<6, 1, 2>), grid, dim3(384), lds, st, a);
+  direct_fill(r, it, a, gx, gy);
+  if (r.s2_ncot) {
+    dim3 grid((unsigned)it.d.nsplit, (unsigned)r.ciblocks);
+    const size_t lds = (size_t)S2Lds::XBYTES + (size_t)r.s2_ncot * S2Lds::DYCOT;
+    if (r.s2_ncot == 1) VUNET_LAUNCH((conv_wgrad_s2_kernel<3, 1, 1>), grid, dim3(192), lds, st, a);
+    else if (r.s2_ncot == 2) VUNET_LAUNCH((conv_wgrad_s2_kernel<6, 1, 2>), grid, dim3(384), lds, st, a);
     else VUNET_LAUNCH((conv_wgrad_s2_kernel<6, 2, 4>), grid, dim3(384), lds, st, a);
     return vunet_check_launch();
   }
-  const bool rs = direct_rowsplit(cls);
-  dim3 grid((unsigned)gx, (unsigned)gy), block(256);
-  if (rs) {
-    if (cls == 5) VUNET_LAUNCH((conv_wgrad_direct_kernel<2, false, 3>), grid, block, 0, st, a);
-    else VUNET_LAUNCH((conv_wgrad_direct_kernel<1, false, 3>), grid, block, 0, st, a);
-    return vunet_check_launch();
-  }
-  switch (cls) {
-    case 1: VUNET_LAUNCH((conv_wgrad_direct_kernel<1, false, 1>), grid, block, 0, st, a); break;
-    case 2: VUNET_LAUNCH((conv_wgrad_direct_kernel<1, true, 9>), grid, block, 0, st, a); break;
-    case 3: VUNET_LAUNCH((conv_wgrad_direct_kernel<2, true, 9>), grid, block, 0, st, a); break;
-    case 4: VUNET_LAUNCH((conv_wgrad_direct_kernel<1, false, 9>), grid, block, 0, st, a); break;
-    default: VUNET_LAUNCH((conv_wgrad_direct_kernel<2, false, 9>), grid, block, 0, st, a); break;
-  }
-  return vunet_check_launch();
+  const bool known = direct_with_form(r.form, [&](auto k) {
+    VUNET_LAUNCH((conv_wgrad_direct_kernel<k.S, k.W4, k.T>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, a);
+  });
+  return known ? vunet_check_launch() : VUNET_ERR_UNSUPPORTED;
 }

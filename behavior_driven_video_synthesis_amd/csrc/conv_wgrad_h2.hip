@@ -46,6 +46,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_wgrad_route.h"
 #include "split_h2.h"
 
 typedef h2_f16x8 wg_bf16x8;   // (the fragment type of this file: eight fp16)
@@ -542,34 +543,13 @@ __global__ __launch_bounds__(256 * WG_GROUPS, 1) void conv_wgrad_h2_kernel(const
 }
 
 // ---- host side ----------------------------------------------------------------------------
-static void h2_geometry(const vunet_wgrad_desc* d, int& MTW, int& ntiles, int& ciblocks, int& coblocks) {
-  MTW = d->Cout % 64 == 0 ? 2 : 1;
-  ntiles = d->N * (d->Ho / 4) * (d->Wo / 32);
-  ciblocks = (d->C1 + d->C2) / 32;
-  coblocks = (d->Cout + 32 * MTW - 1) / (32 * MTW);
-}
-
-int vunet_wgrad_h2_name(const vunet_wgrad_desc* d, char* name, int len) {
-  return snprintf(name, len, "conv_wgrad_h2_kernel<%d>", d->Cout % 64 == 0 ? 2 : 1);
-}
-
-// same applicability and split count as the three-term kernel (vunet_wgrad_x6_applicable / _nslabs)
-int vunet_wgrad_h2_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy, float* slabs,
-                          float* dshift, const float* amax_x, const float* amax_x2, const float* amax_dy, hipStream_t st) {
+// planned by vunet_wgrad_x6_plan (conv_wgrad_x6.hip): the same applicability, half the workgroup target
+int vunet_wgrad_h2_launch(const WgradRoute& r, const vunet_wgrad_item& it, hipStream_t st) {
   WgradH2Args a;
-  a.d = *d;
-  a.x1 = x1; a.x2 = x2; a.dy = dy; a.slabs = slabs; a.dshift = dshift;
-  a.amax_x = amax_x; a.amax_x2 = amax_x2; a.amax_dy = amax_dy;
-  int MTW, ciblocks, coblocks;
-  h2_geometry(d, MTW, a.ntiles, ciblocks, coblocks);
-  a.Ctot = d->C1 + d->C2;
-  a.Coutp = (d->Cout + 31) / 32 * 32;
-  a.tiles_per_img_w = d->Wo / 32;
-  a.tiles_per_img = (d->Ho / 4) * a.tiles_per_img_w;
-  a.tps = (a.ntiles + d->nsplit - 1) / d->nsplit;
-  a.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
-  a.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
-  dim3 grid(d->nsplit, ciblocks, coblocks);
+  wgrad_fill(a, it);
+  wgrad_fill_tiles(a, r);
+  a.amax_x = it.amax_x; a.amax_x2 = it.amax_x2; a.amax_dy = it.amax_dy;
+  dim3 grid(it.d.nsplit, r.ciblocks, r.coblocks);
   // per group: two planes (30 KiB) + the edge planes (6 KiB) [+ the raw fp32 tile and its halo columns, 25.5 KiB, for the
   // form that stages by LDS-DMA]; the fold through LDS reuses 16 KiB per group of it
   constexpr size_t staged = (size_t)2 * (6 * 32 * 5 + 1) * 16 + (size_t)2 * 6 * 4 * 32 * 4;
@@ -582,7 +562,7 @@ int vunet_wgrad_h2_launch(const vunet_wgrad_desc* d, const float* x1, const floa
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) == hipSuccess);
   }();
   if (!attr_ok) return VUNET_ERR_LAUNCH;
-  if (MTW == 1) VUNET_LAUNCH((conv_wgrad_h2_kernel<1>), grid, dim3(256 * WG_GROUPS), lds1, st, a);
+  if (r.MTW == 1) VUNET_LAUNCH((conv_wgrad_h2_kernel<1>), grid, dim3(256 * WG_GROUPS), lds1, st, a);
   else VUNET_LAUNCH((conv_wgrad_h2_kernel<2>), grid, dim3(256 * WG_GROUPS), lds2, st, a);
   return vunet_check_launch();
 }

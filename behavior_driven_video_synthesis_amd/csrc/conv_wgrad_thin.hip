@@ -9,6 +9,7 @@
 // of the 4 dy values, 3 taps x Cout FMAs -- and accumulates over the tiles of its split.  Partial sums go to the slabs
 // vunet_weightnorm_bwd* reduces ([split][Coutp][T * Ctot], k order (tap, ci)); the per-channel sums of dy ride along.
 #include "common.h"
+#include "conv_wgrad_route.h"
 
 struct WgradThinArgs {
   vunet_wgrad_desc d;
@@ -164,34 +165,29 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(const WgradThinArg
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-bool vunet_wgrad_thin_applicable(const vunet_wgrad_desc* d) {
-  return d->Cout >= 1 && d->Cout <= 4 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->C2 == 0 &&
-         d->C1 >= 8 && d->C1 <= 64 && d->Ho == d->Hs && d->Wo == d->Ws && d->Hs % 8 == 0 && d->Ws % 32 == 0 &&
-         (long)d->N * d->Hs * d->Ws >= 64 * 1024;
+bool vunet_wgrad_thin_plan(const vunet_wgrad_desc* d, WgradRoute* r) {
+  if (!(d->Cout >= 1 && d->Cout <= 4 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->C2 == 0 &&
+        d->C1 >= 8 && d->C1 <= 64 && d->Ho == d->Hs && d->Wo == d->Ws && d->Hs % 8 == 0 && d->Ws % 32 == 0 &&
+        (long)d->N * d->Hs * d->Ws >= 64 * 1024))
+    return false;
+  r->family = WGRAD_THIN;
+  r->ntiles = d->N * (d->Hs / 8) * (d->Ws / 32);
+  r->nslabs = r->ntiles < 512 ? r->ntiles : 512;   // two workgroups per CU; each walks ntiles / 512 tiles
+  return true;
 }
 
-static int thin_tiles(const vunet_wgrad_desc* d) { return d->N * (d->Hs / 8) * (d->Ws / 32); }
-
-int vunet_wgrad_thin_nslabs(const vunet_wgrad_desc* d) {
-  const int t = thin_tiles(d);
-  return t < 512 ? t : 512;   // two workgroups per CU; each walks ntiles / 512 tiles
-}
-
-int vunet_wgrad_thin_name(const vunet_wgrad_desc* d, char* name, int len) {
-  return snprintf(name, len, "conv_wgrad_thin_kernel");
-}
-
-int vunet_wgrad_thin_launch(const vunet_wgrad_desc* d, const float* x1, const float* dy, float* slabs, float* dshift,
-                            hipStream_t st) {
+// (one source, no channel padding of the input: the block has no x2 / in2 / Ctot and is filled here)
+int vunet_wgrad_thin_launch(const WgradRoute& r, const vunet_wgrad_item& it, hipStream_t st) {
+  const vunet_wgrad_desc* d = &it.d;
   WgradThinArgs a;
   a.d = *d;
-  a.x1 = x1; a.dy = dy; a.slabs = slabs; a.dshift = dshift;
+  a.x1 = it.x1; a.dy = it.dy; a.slabs = it.slabs; a.dshift = it.dshift;
   a.Coutp = (d->Cout + 31) / 32 * 32;
   a.tiles_w = d->Ws / 32;
   a.tiles_per_img = (d->Hs / 8) * a.tiles_w;
-  a.ntiles = thin_tiles(d);
+  a.ntiles = r.ntiles;
   a.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
-  if (d->nsplit != vunet_wgrad_thin_nslabs(d)) return VUNET_ERR_ARG;
+  if (d->nsplit != r.nslabs) return VUNET_ERR_ARG;
   const int CP = 10 * 35 + 1;
   const size_t lds = ((size_t)((d->C1 * CP + 3) & ~3) + 4 * 256) * sizeof(float);
   if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)conv_wgrad_thin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,

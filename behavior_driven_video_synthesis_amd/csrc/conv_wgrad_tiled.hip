@@ -12,6 +12,7 @@
 // (m-tile, pixel-row) space; waves that share an m-tile write separate slabs, which
 // vunet_weightnorm_bwd sums in a fixed order (deterministic, no atomics).
 #include "common.h"
+#include "conv_wgrad_route.h"
 
 struct WgradTiledArgs {
   vunet_wgrad_desc d;
@@ -197,31 +198,25 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tiled_kernel(const WgradTil
 }
 
 // ---- host side ----------------------------------------------------------------------------
-bool vunet_wgrad_tiled_applicable(const vunet_wgrad_desc* d) {
+bool vunet_wgrad_tiled_plan(const vunet_wgrad_desc* d, WgradRoute* r) {
   const bool k3 = d->KH == 3 && d->KW == 3 && d->pad == 1, k1 = d->KH == 1 && d->KW == 1 && d->pad == 0;
   const bool chans = ((d->C1 % 32 == 0 && d->C2 % 32 == 0) || (d->C2 == 0 && d->C1 < 32)) &&
                      (d->Cout % 32 == 0 || d->Cout < 32);
-  if (d->stride == 2)  // Downsample convs: 2 x 32 output tiles, two m-tiles per workgroup
-    return k3 && chans && d->Cout >= 64 && d->Hs == 2 * d->Ho && d->Ws == 2 * d->Wo && d->Wo % 32 == 0 && d->Ho % 2 == 0;
-  return (k3 || k1) && chans && d->stride == 1 && d->Ws % 32 == 0 && d->Hs % 4 == 0 && d->Ho == d->Hs && d->Wo == d->Ws;
-}
-
-static void tiled_geometry(const vunet_wgrad_desc* d, int& MTW, int& TH, int& ntiles, int& ciblocks, int& coblocks) {
-  MTW = d->Cout >= 64 ? 2 : 1;
-  TH = d->stride == 2 ? 2 : 4;
-  ntiles = d->N * (d->Ho / TH) * (d->Wo / 32);
-  ciblocks = (d->C1 + d->C2 + 31) / 32;
-  coblocks = (d->Cout + 32 * MTW - 1) / (32 * MTW);
-}
-
-int vunet_wgrad_tiled_nslabs(const vunet_wgrad_desc* d) {
-  int MTW, TH, ntiles, ciblocks, coblocks;
-  tiled_geometry(d, MTW, TH, ntiles, ciblocks, coblocks);
-  int S = 1024 / (ciblocks * coblocks);  // ~4 workgroups per CU over the whole grid
-  if (S > ntiles / 2) S = ntiles / 2;
-  if (S < 1) S = 1;
-  if (S > 512) S = 512;
-  return S;
+  if (d->stride == 2) {  // Downsample convs: 2 x 32 output tiles, two m-tiles per workgroup
+    if (!(k3 && chans && d->Cout >= 64 && d->Hs == 2 * d->Ho && d->Ws == 2 * d->Wo && d->Wo % 32 == 0 && d->Ho % 2 == 0)) return false;
+  } else if (!((k3 || k1) && chans && d->stride == 1 && d->Ws % 32 == 0 && d->Hs % 4 == 0 && d->Ho == d->Hs && d->Wo == d->Ws)) {
+    return false;
+  }
+  r->family = WGRAD_TILED;
+  r->MTW = d->Cout >= 64 ? 2 : 1;
+  r->TH = d->stride == 2 ? 2 : 4;
+  r->KS = d->KH;
+  r->ST = d->stride;
+  r->ntiles = d->N * (d->Ho / r->TH) * (d->Wo / 32);
+  r->ciblocks = (d->C1 + d->C2 + 31) / 32;
+  r->coblocks = (d->Cout + 32 * r->MTW - 1) / (32 * r->MTW);
+  r->nslabs = wgrad_tile_nslabs(*r, 1024);  // ~4 workgroups per CU over the whole grid
+  return true;
 }
 
 template <int MTW, int TH, int KS, int ST>
@@ -234,24 +229,14 @@ static int launch_wgrad_tiled(const WgradTiledArgs& a, dim3 grid, hipStream_t st
   return vunet_check_launch();
 }
 
-int vunet_wgrad_tiled_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy,
-                             float* slabs, float* dshift, hipStream_t st) {
+int vunet_wgrad_tiled_launch(const WgradRoute& r, const vunet_wgrad_item& it, hipStream_t st) {
   WgradTiledArgs a;
-  a.d = *d;
-  a.x1 = x1; a.x2 = x2; a.dy = dy; a.slabs = slabs; a.dshift = dshift;
-  int MTW, TH, ciblocks, coblocks;
-  tiled_geometry(d, MTW, TH, a.ntiles, ciblocks, coblocks);
-  a.S = d->nsplit;
-  a.HW = d->Hs * d->Ws;
-  a.Ctot = d->C1 + d->C2;
-  a.Coutp = (d->Cout + 31) / 32 * 32;
-  a.tiles_per_img_w = d->Wo / 32;
-  a.tiles_per_img = (d->Ho / TH) * a.tiles_per_img_w;
-  a.tps = (a.ntiles + a.S - 1) / a.S;
-  a.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
-  a.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
-  dim3 grid(a.S, ciblocks, coblocks);
-  if (d->stride == 2) return launch_wgrad_tiled<2, 2, 3, 2>(a, grid, st);
-  if (d->KH == 3) return MTW == 1 ? launch_wgrad_tiled<1, 4, 3, 1>(a, grid, st) : launch_wgrad_tiled<2, 4, 3, 1>(a, grid, st);
-  return MTW == 1 ? launch_wgrad_tiled<1, 4, 1, 1>(a, grid, st) : launch_wgrad_tiled<2, 4, 1, 1>(a, grid, st);
+  wgrad_fill(a, it);
+  wgrad_fill_tiles(a, r);
+  a.S = it.d.nsplit;
+  a.HW = it.d.Hs * it.d.Ws;
+  dim3 grid(a.S, r.ciblocks, r.coblocks);
+  if (r.ST == 2) return launch_wgrad_tiled<2, 2, 3, 2>(a, grid, st);   // (the plan's only stride-2 instantiation)
+  if (r.KS == 3) return r.MTW == 1 ? launch_wgrad_tiled<1, 4, 3, 1>(a, grid, st) : launch_wgrad_tiled<2, 4, 3, 1>(a, grid, st);
+  return r.MTW == 1 ? launch_wgrad_tiled<1, 4, 1, 1>(a, grid, st) : launch_wgrad_tiled<2, 4, 1, 1>(a, grid, st);
 }

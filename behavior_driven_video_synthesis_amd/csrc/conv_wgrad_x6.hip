@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_wgrad_route.h"
 
 typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
@@ -341,8 +342,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x6_kernel(const WgradX6Args
 }
 
 // ---- host side ----------------------------------------------------------------------------
-bool vunet_wgrad_x6_applicable(const vunet_wgrad_desc* d) {
-  static const bool on = [] {
+static bool x6_applicable(const vunet_wgrad_desc* d) {
+  static const bool on = [] {   // (read once per process)
     const char* e = getenv("VUNET_CONV_PRECISION");
     return !(e && (e[0] == 'f' || e[0] == 'F'));
   }();
@@ -351,49 +352,32 @@ bool vunet_wgrad_x6_applicable(const vunet_wgrad_desc* d) {
          d->Ws % 32 == 0 && d->Hs % 4 == 0 && d->C1 > 0 && d->C1 % 32 == 0 && d->C2 % 32 == 0 && d->Cout % 32 == 0;
 }
 
-static void x6_geometry(const vunet_wgrad_desc* d, int& MTW, int& ntiles, int& ciblocks, int& coblocks) {
-  MTW = d->Cout % 64 == 0 ? 2 : 1;
-  ntiles = d->N * (d->Ho / 4) * (d->Wo / 32);
-  ciblocks = (d->C1 + d->C2) / 32;
-  coblocks = (d->Cout + 32 * MTW - 1) / (32 * MTW);
-}
-
-int vunet_wgrad_x6_nslabs(const vunet_wgrad_desc* d) {
-  int MTW, ntiles, ciblocks, coblocks;
-  x6_geometry(d, MTW, ntiles, ciblocks, coblocks);
+// fills WGRAD_X6 or, for d->flags bit 1, WGRAD_H2 (conv_wgrad_h2.hip has no rule of its own)
+bool vunet_wgrad_x6_plan(const vunet_wgrad_desc* d, WgradRoute* r) {
+  if (!x6_applicable(d)) return false;
+  const bool h2 = d->flags & 2;
+  r->family = h2 ? WGRAD_H2 : WGRAD_X6;
+  r->MTW = d->Cout % 64 == 0 ? 2 : 1;
+  r->TH = 4;
+  r->ntiles = d->N * (d->Ho / 4) * (d->Wo / 32);
+  r->ciblocks = (d->C1 + d->C2) / 32;
+  r->coblocks = (d->Cout + 32 * r->MTW - 1) / (32 * r->MTW);
   // 512 workgroups = exactly the two resident per CU, one round: measured best with the fp16 kernel (r02: 1024 -> 512:
   // conv_wgrad_h2_kernel<2> 2.08 -> 1.87 ms per step, half the slab volume for the reduce; 768 and 256 are worse)
-  static const int target = [] { const char* e = getenv("VUNET_WGRAD_SPLIT_WGS"); return e ? atoi(e) : 512; }();   // tuning
+  static const int target = [] { const char* e = getenv("VUNET_WGRAD_SPLIT_WGS"); return e ? atoi(e) : 512; }();   // tuning, read once
   // (fp16 scheme, round 4: a workgroup is 512 threads -- two groups in antiphase, conv_wgrad_h2.hip -- so ONE workgroup per
   // CU is resident: half the workgroups, each walking twice the tiles, half the slab volume again)
-  int S = ((d->flags & 2) ? target / 2 : target) / (ciblocks * coblocks);
-  if (S > ntiles / 2) S = ntiles / 2;
-  if (S < 1) S = 1;
-  if (S > 512) S = 512;
-  return S;
+  r->nslabs = wgrad_tile_nslabs(*r, h2 ? target / 2 : target);
+  return true;
 }
 
-int vunet_wgrad_x6_name(const vunet_wgrad_desc* d, char* name, int len) {
-  return snprintf(name, len, "conv_wgrad_x6_kernel<%d>", d->Cout % 64 == 0 ? 2 : 1);
-}
-
-int vunet_wgrad_x6_launch(const vunet_wgrad_desc* d, const float* x1, const float* x2, const float* dy, float* slabs,
-                          float* dshift, hipStream_t st) {
+int vunet_wgrad_x6_launch(const WgradRoute& r, const vunet_wgrad_item& it, hipStream_t st) {
   WgradX6Args a;
-  a.d = *d;
-  a.x1 = x1; a.x2 = x2; a.dy = dy; a.slabs = slabs; a.dshift = dshift;
-  int MTW, ciblocks, coblocks;
-  x6_geometry(d, MTW, a.ntiles, ciblocks, coblocks);
-  a.Ctot = d->C1 + d->C2;
-  a.Coutp = (d->Cout + 31) / 32 * 32;
-  a.tiles_per_img_w = d->Wo / 32;
-  a.tiles_per_img = (d->Ho / 4) * a.tiles_per_img_w;
-  a.tps = (a.ntiles + d->nsplit - 1) / d->nsplit;
-  a.in1 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed);
-  a.in2 = make_inact(d->in_act, d->in_slope, d->drop_p, d->drop_seed + 0x9E3779B9u);
-  dim3 grid(d->nsplit, ciblocks, coblocks);
+  wgrad_fill(a, it);
+  wgrad_fill_tiles(a, r);
+  dim3 grid(it.d.nsplit, r.ciblocks, r.coblocks);
   constexpr size_t lds = (size_t)3 * (6 * 32 * 5 + 1) * 16;
-  if (MTW == 1) VUNET_LAUNCH((conv_wgrad_x6_kernel<1>), grid, dim3(256), lds, st, a);
+  if (r.MTW == 1) VUNET_LAUNCH((conv_wgrad_x6_kernel<1>), grid, dim3(256), lds, st, a);
   else VUNET_LAUNCH((conv_wgrad_x6_kernel<2>), grid, dim3(256), lds, st, a);
   return vunet_check_launch();
 }

@@ -39,6 +39,62 @@ def assert_close(actual, expected, rtol=1e-4, atol=1e-4, name=""):
                              f"{(err > tol).mean() * 100:.3f}% outside rtol={rtol} atol={atol}")
 
 
+def run_wgrad(ops, x1, x2, dy, k, stride, pad, in_act, drop, seed, flags):
+    """One weight gradient through the C ABI: ask the library for the kernel's name and the slab count, launch
+    vunet_conv2d_wgrad into NaN-filled slabs, reduce them with vunet_weightnorm_bwd (kind 1: plain dW) -> (dw, db, name).
+    The tensor maxima are handed over for flags == 2 (the fp16 scheme) only."""
+    import ctypes
+    n, c1, hs, ws = x1.shape
+    c2 = 0 if x2 is None else x2.shape[1]
+    cout, ho, wo = dy.shape[1:]
+    ctot, ktot = c1 + c2, k * k * (c1 + c2)
+    wd = ops.WgradDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, Cout=cout, Ho=ho, Wo=wo, KH=k, KW=k, stride=stride, pad=pad,
+                       in_act=in_act, in_slope=0.0, drop_p=drop, drop_seed=seed, nsplit=1, flags=flags)
+    buf = ctypes.create_string_buffer(96)
+    ops._call("vunet_conv2d_wgrad_variant", ctypes.byref(wd), buf, 96)
+    ns = ops._lib.lib().vunet_conv2d_wgrad_nsplit(ctypes.byref(wd))
+    assert ns >= 1
+    wd.nsplit = ns
+    cp = ops._r32(cout)
+    slabs = torch.full((ns * cp * ktot + ns * cp,), float("nan"), device="cuda")
+    dshift = slabs[ns * cp * ktot:]
+    amx = ops.absmax_partials(x1, x2) if flags == 2 else None
+    amd = ops.absmax_partials(dy) if flags == 2 else None
+    ops._call("vunet_conv2d_wgrad", ctypes.byref(wd), ops._p(x1), ops._p(x2), ops._p(dy), ops._p(slabs),
+              ops._p(dshift), ops._p(amx), ops._p(amd), ops._stream())
+    dw = torch.empty(cout, ctot, k, k, device="cuda")
+    db = torch.empty(cout, device="cuda")
+    v = torch.zeros(cout, ctot, k, k, device="cuda")
+    work = torch.empty(cout * (ktot + 1), device="cuda")
+    wn = ops.WnDesc(cout, c1, c2, k, k, 1, 0)
+    ops._call("vunet_weightnorm_bwd", ctypes.byref(wn), ops._p(slabs), ops._p(dshift), ns, ops._p(v), None, None,
+              None, None, ops._p(dw), None, ops._p(db), None, None, ops._p(work), 0, ops._stream())
+    torch.cuda.synchronize()
+    return dw, db, buf.value.decode()
+
+
+def wgrad_ref_fp64(ops, x1, x2, dy, k, stride, pad, in_act, drop, seed):
+    """float64 reference of run_wgrad on the CPU: the prologue (ELU, the dropout keep-mask of each source), then autograd of
+    conv2d with respect to the weight -> (dW, db = dy summed per channel)."""
+    import torch.nn.functional as F
+    xs = []
+    for i, x in enumerate((x1, x2)):
+        if x is None:
+            continue
+        t = x.double().cpu()
+        if in_act == ops.ACT_ELU:
+            t = F.elu(t)
+        if drop > 0:
+            s = seed if i == 0 else (seed + ops.SEED2_OFFSET) & 0xFFFFFFFF
+            t = t * dropout_keep_mask(tuple(x.shape), drop, s).double() * float(torch.tensor(1.0 / (1.0 - drop),
+                                                                                             dtype=torch.float32))
+        xs.append(t)
+    xin = torch.cat(xs, dim=1)
+    wz = torch.zeros(dy.shape[1], xin.shape[1], k, k, dtype=torch.float64, requires_grad=True)
+    (F.conv2d(xin, wz, stride=stride, padding=pad) * dy.double().cpu()).sum().backward()
+    return wz.grad, dy.double().cpu().sum(dim=(0, 2, 3))
+
+
 def psnr(a: torch.Tensor, b: torch.Tensor, peak: float = 2.0) -> float:
     mse = float(((a.double().cpu() - b.double().cpu()) ** 2).mean())
     return float("inf") if mse == 0 else 10.0 * np.log10(peak * peak / mse)

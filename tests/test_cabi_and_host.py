@@ -238,7 +238,7 @@ def test_routing_table_recorded_from_the_parent_replays():
     cases = list(rs.unpack(lines[1:]))
     assert len(cases) >= 2000
     q = rs.Queries()
-    conv_seen, wgrad_seen = set(), set()
+    conv_seen, wgrad_seen, wgrad_names = set(), set(), set()
     for line in cases:
         assert rs.replay(q, line) == line
         f = line.split("|")
@@ -246,8 +246,43 @@ def test_routing_table_recorded_from_the_parent_replays():
             conv_seen.update(rs.conv_family(x.rsplit(" ", 2)[0].split(":", 1)[1]) for x in f[3:6])
             if f[1] == "0": conv_seen.add("unsupported")
         else:
+            wgrad_names.add(f[1].split(":", 1)[1])
             wgrad_seen.add(rs.wgrad_family(f[1].split(":", 1)[1]))
     assert conv_seen == set(rs.CONV_FAMILIES) and wgrad_seen == set(rs.WGRAD_FAMILIES)
+    # instantiations, not only families: every name the full default weight-gradient sweep reaches (recorded from that sweep
+    # on the commit before the plan, not read off the router)
+    assert wgrad_names == {
+        "conv_wgrad_x6_kernel<1>", "conv_wgrad_x6_kernel<2>", "conv_wgrad_h2_kernel<1>", "conv_wgrad_h2_kernel<2>",
+        "conv_wgrad_direct_kernel<1, false, 1>", "conv_wgrad_direct_kernel<1, false, 3>", "conv_wgrad_direct_kernel<1, true, 9>",
+        "conv_wgrad_direct_kernel<2, false, 3>", "conv_wgrad_direct_kernel<2, true, 9>", "conv_wgrad_s2_kernel",
+        "conv_wgrad_thin_kernel", "conv_wgrad_tiled_kernel<1, 4, 1, 1>", "conv_wgrad_tiled_kernel<1, 4, 3, 1>",
+        "conv_wgrad_tiled_kernel<2, 2, 3, 2>", "conv_wgrad_tiled_kernel<2, 4, 1, 1>", "conv_wgrad_tiled_kernel<2, 4, 3, 1>",
+        "conv_wgrad_kernel<1, 4, 1>", "conv_wgrad_kernel<1, 4, 3>", "conv_wgrad_kernel<1, 4, 4>", "conv_wgrad_kernel<2, 2, 1>",
+        "conv_wgrad_kernel<2, 2, 5>", "conv_wgrad_kernel<2, 2, 8>", "conv_wgrad_kernel<4, 1, 1>", "conv_wgrad_kernel<4, 1, 9>"}
+
+
+def test_row_split_off_names_of_the_direct_weight_gradient():
+    """conv_wgrad_direct_kernel<1, false, 9> and <2, false, 9> are reached only with the tuning key wgrad_rowsplit = 1, so the
+    table above cannot hold them: the answers (variant | nsplit | wants_split | batchable) as recorded before the plan."""
+    import importlib.util
+    from behavior_driven_video_synthesis_amd import ops
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("route_sweep_under_test", os.path.join(root, "tools", "route_sweep.py"))
+    rs = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rs)
+    q = rs.Queries()
+    recorded = {1: "0:conv_wgrad_direct_kernel<1, false, 9>|8|1|1", 2: "0:conv_wgrad_direct_kernel<2, false, 9>|2|1|1"}
+    default = {1: "0:conv_wgrad_direct_kernel<1, false, 3>|8|1|1", 2: "0:conv_wgrad_direct_kernel<2, false, 3>|2|1|1"}
+    for stride in (1, 2):
+        d = dict(N=2, C1=32, C2=0, Hs=16, Ws=16, Cout=32, Ho=16 // stride, Wo=16 // stride, KH=3, KW=3, stride=stride, pad=1,
+                 in_act=1, drop_p=0.0, flags=2)
+        ops.set_tuning("wgrad_rowsplit", 1)
+        try:
+            off = q.wgrad(d)[0]
+        finally:
+            ops.set_tuning("wgrad_rowsplit", 0)
+        assert off == recorded[stride]
+        assert q.wgrad(d)[0] == default[stride]
 
 
 def test_p2_dispatch_and_the_vgg19_program_are_host_logic():

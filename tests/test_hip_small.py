@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from hip_parity_utils import assert_close, dropout_keep_mask
+from hip_parity_utils import assert_close, dropout_keep_mask, run_wgrad, wgrad_ref_fp64
 
 pytestmark = pytest.mark.gpu
 
@@ -217,58 +217,20 @@ def test_direct_weight_gradient_vs_fp64(case, rowsplit):
     x2 = torch.randn(n, c2, hs, ws, generator=g_).cuda() if c2 else None
     dy = torch.randn(n, cout, ho, wo, generator=g_).cuda()
     seed = 0xFACE
-    ctot, ktot = c1 + c2, k * k * (c1 + c2)
 
     def run(flags):
-        wd = ops.WgradDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, Cout=cout, Ho=ho, Wo=wo, KH=k, KW=k, stride=stride, pad=pad,
-                           in_act=in_act, in_slope=0.0, drop_p=drop, drop_seed=seed, nsplit=1, flags=flags)
-        buf = ctypes.create_string_buffer(96)
-        ops._call("vunet_conv2d_wgrad_variant", ctypes.byref(wd), buf, 96)
-        ns = ops._lib.lib().vunet_conv2d_wgrad_nsplit(ctypes.byref(wd))
-        assert ns >= 1
-        wd.nsplit = ns
-        cp = ops._r32(cout)
-        slabs = torch.full((ns * cp * ktot + ns * cp,), float("nan"), device="cuda")
-        dshift = slabs[ns * cp * ktot:]
-        amx = ops.absmax_partials(x1, x2) if flags == 2 else None
-        amd = ops.absmax_partials(dy) if flags == 2 else None
-        ops._call("vunet_conv2d_wgrad", ctypes.byref(wd), ops._p(x1), ops._p(x2), ops._p(dy), ops._p(slabs),
-                  ops._p(dshift), ops._p(amx), ops._p(amd), ops._stream())
-        dw = torch.empty(cout, ctot, k, k, device="cuda")
-        db = torch.empty(cout, device="cuda")
-        v = torch.zeros(cout, ctot, k, k, device="cuda")
-        work = torch.empty(cout * (ktot + 1), device="cuda")
-        wn = ops.WnDesc(cout, c1, c2, k, k, 1, 0)
-        ops._call("vunet_weightnorm_bwd", ctypes.byref(wn), ops._p(slabs), ops._p(dshift), ns, ops._p(v), None, None,
-                  None, None, ops._p(dw), None, ops._p(db), None, None, ops._p(work), 0, ops._stream())
-        torch.cuda.synchronize()
-        return dw, db, buf.value.decode()
+        return run_wgrad(ops, x1, x2, dy, k, stride, pad, in_act, drop, seed, flags)
 
     dwh, dbh, name = run(2)
     dw3, db3, name3 = run(1)
     assert name.startswith("conv_wgrad_direct_kernel"), name
     assert not name3.startswith("conv_wgrad_direct_kernel"), name3
-    xs = []
-    for i, x in enumerate((x1, x2)):
-        if x is None:
-            continue
-        t = x.double().cpu()
-        if in_act == ops.ACT_ELU:
-            t = F.elu(t)
-        if drop > 0:
-            s = seed if i == 0 else (seed + ops.SEED2_OFFSET) & 0xFFFFFFFF
-            t = t * dropout_keep_mask(tuple(x.shape), drop, s).double() * float(torch.tensor(1.0 / (1.0 - drop),
-                                                                                             dtype=torch.float32))
-        xs.append(t)
-    wz = torch.zeros(cout, ctot, k, k, dtype=torch.float64, requires_grad=True)
-    (F.conv2d(torch.cat(xs, dim=1), wz, stride=stride, padding=pad) * dy.double().cpu()).sum().backward()
-    ref = wz.grad
+    ref, refb = wgrad_ref_fp64(ops, x1, x2, dy, k, stride, pad, in_act, drop, seed)
     sc = float(ref.abs().max())
     eh = float((dwh.double().cpu() - ref).abs().max())
     e3 = float((dw3.double().cpu() - ref).abs().max())
     assert eh <= 3e-6 * sc, (eh, sc)
     assert eh <= 5.0 * e3 + 4e-7 * sc, (eh, e3, sc)
-    refb = dy.double().cpu().sum(dim=(0, 2, 3))
     assert float((dbh.double().cpu() - refb).abs().max()) <= 1e-5 * max(float(refb.abs().max()), 1.0)
 
 
@@ -295,51 +257,86 @@ def test_staged_stride2_weight_gradient_vs_fp64_and_the_direct_kernel(case):
     x2 = torch.randn(n, c2, hs, ws, generator=g_).cuda() if c2 else None
     dy = torch.randn(n, cout, ho, wo, generator=g_).cuda()
     seed = 0xFACE
-    ctot, ktot = c1 + c2, 9 * (c1 + c2)
 
     def run(knob):
         ops.set_tuning("wgrad_rowsplit", knob)
-        wd = ops.WgradDesc(N=n, C1=c1, C2=c2, Hs=hs, Ws=ws, Cout=cout, Ho=ho, Wo=wo, KH=k, KW=k, stride=stride, pad=pad,
-                           in_act=in_act, in_slope=0.0, drop_p=drop, drop_seed=seed, nsplit=1, flags=2)
-        buf = ctypes.create_string_buffer(96)
-        ops._call("vunet_conv2d_wgrad_variant", ctypes.byref(wd), buf, 96)
-        ns = ops._lib.lib().vunet_conv2d_wgrad_nsplit(ctypes.byref(wd))
-        wd.nsplit = ns
-        cp = ops._r32(cout)
-        slabs = torch.full((ns * cp * ktot + ns * cp,), float("nan"), device="cuda")
-        dshift = slabs[ns * cp * ktot:]
-        ops._call("vunet_conv2d_wgrad", ctypes.byref(wd), ops._p(x1), ops._p(x2), ops._p(dy), ops._p(slabs), ops._p(dshift),
-                  ops._p(ops.absmax_partials(x1, x2)), ops._p(ops.absmax_partials(dy)), ops._stream())
-        dw, db = torch.empty(cout, ctot, k, k, device="cuda"), torch.empty(cout, device="cuda")
-        v, work = torch.zeros(cout, ctot, k, k, device="cuda"), torch.empty(cout * (ktot + 1), device="cuda")
-        wn = ops.WnDesc(cout, c1, c2, k, k, 1, 0)
-        ops._call("vunet_weightnorm_bwd", ctypes.byref(wn), ops._p(slabs), ops._p(dshift), ns, ops._p(v), None, None, None, None,
-                  ops._p(dw), None, ops._p(db), None, None, ops._p(work), 0, ops._stream())
-        torch.cuda.synchronize()
-        return dw, db, buf.value.decode()
+        return run_wgrad(ops, x1, x2, dy, k, stride, pad, in_act, drop, seed, 2)
     dws, dbs, name_s = run(0)
     dwd, dbd, name_d = run(3)
     assert name_s == "conv_wgrad_s2_kernel" and name_d.startswith("conv_wgrad_direct_kernel<2"), (name_s, name_d)
-    xs = []
-    for i, x in enumerate((x1, x2)):
-        if x is None:
-            continue
-        t = x.double().cpu()
-        if in_act == ops.ACT_ELU:
-            t = F.elu(t)
-        if drop > 0:
-            sd = seed if i == 0 else (seed + ops.SEED2_OFFSET) & 0xFFFFFFFF
-            t = t * dropout_keep_mask(tuple(x.shape), drop, sd).double() * float(torch.tensor(1.0 / (1.0 - drop), dtype=torch.float32))
-        xs.append(t)
-    wz = torch.zeros(cout, ctot, k, k, dtype=torch.float64, requires_grad=True)
-    (F.conv2d(torch.cat(xs, dim=1), wz, stride=2, padding=1) * dy.double().cpu()).sum().backward()
-    ref = wz.grad
+    ref, refb = wgrad_ref_fp64(ops, x1, x2, dy, k, stride, pad, in_act, drop, seed)
     sc = float(ref.abs().max())
     es, ed = float((dws.double().cpu() - ref).abs().max()), float((dwd.double().cpu() - ref).abs().max())
     assert es <= 3e-6 * sc, (es, sc)
     assert es <= 3.0 * ed + 4e-7 * sc, (es, ed, sc)
-    refb = dy.double().cpu().sum(dim=(0, 2, 3))
     assert float((dbs.double().cpu() - refb).abs().max()) <= 1e-5 * max(float(refb.abs().max()), 1.0)
+
+
+# (kernel name, flags, wgrad_rowsplit, n, c1, cout, hs, ws, k, stride): one case per kernel the weight gradient can launch, each
+# on the smallest shape its instantiation accepts.  flags: 0 the bf16 scheme, 1 the fp32-input kernels, 2 the fp16 scheme.
+_GENERIC = [("conv_wgrad_kernel<%s>" % inst, 1, 0, 2, 32, cout, 12, 12, k, 1)    # a 12 x 12 map: no family above takes it
+            for k, cout, inst in ((1, 16, "1, 4, 1"), (1, 48, "2, 2, 1"), (1, 96, "4, 1, 1"), (3, 16, "1, 4, 3"),
+                                  (3, 48, "2, 2, 5"), (3, 96, "4, 1, 9"), (4, 16, "1, 4, 4"), (4, 48, "2, 2, 8"))]
+WGRAD_EVERY = [
+    ("conv_wgrad_x6_kernel<1>", 0, 0, 2, 32, 32, 8, 32, 3, 1),
+    ("conv_wgrad_x6_kernel<2>", 0, 0, 2, 32, 64, 8, 32, 3, 1),
+    ("conv_wgrad_h2_kernel<1>", 2, 0, 2, 32, 32, 8, 32, 3, 1),
+    ("conv_wgrad_h2_kernel<2>", 2, 0, 2, 32, 64, 8, 32, 3, 1),
+    ("conv_wgrad_direct_kernel<1, false, 1>", 2, 0, 2, 32, 32, 8, 8, 1, 1),
+    ("conv_wgrad_direct_kernel<1, true, 9>", 2, 0, 2, 32, 32, 4, 4, 3, 1),
+    ("conv_wgrad_direct_kernel<2, true, 9>", 2, 0, 2, 32, 32, 8, 8, 3, 2),
+    ("conv_wgrad_direct_kernel<1, false, 3>", 2, 0, 2, 32, 32, 16, 16, 3, 1),
+    ("conv_wgrad_direct_kernel<2, false, 3>", 2, 0, 2, 32, 32, 16, 16, 3, 2),
+    ("conv_wgrad_direct_kernel<1, false, 9>", 2, 1, 2, 32, 32, 16, 16, 3, 1),
+    ("conv_wgrad_direct_kernel<2, false, 9>", 2, 1, 2, 32, 32, 16, 16, 3, 2),
+    # the LDS-staged stride-2 kernel's three instantiations (1, 2, 4 output-channel tiles) report one name; N Ho Wo = 18432
+    ("conv_wgrad_s2_kernel", 2, 0, 2, 32, 32, 192, 192, 3, 2),
+    ("conv_wgrad_s2_kernel", 2, 0, 2, 32, 64, 192, 192, 3, 2),
+    ("conv_wgrad_s2_kernel", 2, 0, 2, 32, 128, 192, 192, 3, 2),
+    ("conv_wgrad_tiled_kernel<1, 4, 3, 1>", 1, 0, 2, 32, 32, 8, 32, 3, 1),
+    ("conv_wgrad_tiled_kernel<2, 4, 3, 1>", 1, 0, 2, 32, 64, 8, 32, 3, 1),
+    ("conv_wgrad_tiled_kernel<1, 4, 1, 1>", 1, 0, 2, 32, 32, 8, 32, 1, 1),
+    ("conv_wgrad_tiled_kernel<2, 4, 1, 1>", 1, 0, 2, 32, 64, 8, 32, 1, 1),
+    ("conv_wgrad_tiled_kernel<2, 2, 3, 2>", 1, 0, 2, 32, 64, 4, 64, 3, 2),
+    # (the thin kernel asks for N Hs Ws >= 65536: 256 images of its 8 x 32 tile)
+    ("conv_wgrad_thin_kernel", 1, 0, 256, 32, 3, 8, 32, 3, 1),
+] + _GENERIC
+
+
+@pytest.mark.parametrize("case", WGRAD_EVERY, ids=lambda c: "%s-cout%d" % (c[0], c[5]))
+def test_every_weight_gradient_instantiation_vs_float64(case):
+    """Every kernel vunet_conv2d_wgrad can launch, by the name vunet_conv2d_wgrad_variant reports for it: dW against the
+    float64 conv2d gradient, db against dy summed per channel.  Bounds: the existing ones of each family."""
+    ops = _ops()
+    want, flags, rowsplit, n, c1, cout, hs, ws, k, stride = case
+    ops.set_tuning("wgrad_rowsplit", rowsplit)
+    pad = 0 if k == 1 else 1
+    ho, wo = (hs + 2 * pad - k) // stride + 1, (ws + 2 * pad - k) // stride + 1
+    g_ = torch.Generator().manual_seed(hash(case[1:]) & 0xFFFF)
+    x1 = torch.randn(n, c1, hs, ws, generator=g_).cuda()
+    dy = torch.randn(n, cout, ho, wo, generator=g_).cuda()
+    try:
+        dw, db, name = run_wgrad(ops, x1, None, dy, k, stride, pad, ops.ACT_ELU, 0.0, 0, flags)
+    finally:
+        ops.set_tuning("wgrad_rowsplit", 0)
+    assert name == want
+    ref, refb = wgrad_ref_fp64(ops, x1, None, dy, k, stride, pad, ops.ACT_ELU, 0.0, 0)
+    err, sc = float((dw.double().cpu() - ref).abs().max()), float(ref.abs().max())
+    errb, scb = float((db.double().cpu() - refb).abs().max()), float(refb.abs().max())
+    print(f"{name}: max|dW - ref| = {err:.3e} of {sc:.3e}, max|db - ref| = {errb:.3e} of {scb:.3e}")
+    if name.startswith(("conv_wgrad_direct", "conv_wgrad_s2")):
+        # tests/test_hip_small.py:232 and :234 (test_direct_weight_gradient_vs_fp64), :270 and :272 (the staged kernel's test)
+        assert err <= 3e-6 * sc, (err, sc)
+        assert errb <= 1e-5 * max(scb, 1.0), (errb, scb)
+    elif name.startswith(("conv_wgrad_x6", "conv_wgrad_h2")):
+        # tests/test_hip_x6.py:338 and :340 (test_x6_weight_gradient_vs_fp64: dW, then dshift)
+        assert err <= 3e-6 * sc, (err, sc)
+        assert_close(db, refb.float(), rtol=1e-5, atol=1e-5 * scb, name="dshift")
+    else:
+        # the fp32 families (tiled, thin, generic): tests/test_hip_primitives.py:129 (test_normconv_vs_oracle, whose shapes
+        # run the tiled and the generic kernel: the parameter gradients' rtol=1e-3, atol=2e-4)
+        assert_close(dw, ref.float(), rtol=1e-3, atol=2e-4, name="dw")
+        assert_close(db, refb.float(), rtol=1e-3, atol=2e-4, name="db")
 
 
 def test_batched_weight_gradient_launch_equals_one_launch_per_layer():

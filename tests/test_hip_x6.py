@@ -21,7 +21,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from hip_parity_utils import assert_close, dropout_keep_mask
+from hip_parity_utils import assert_close, dropout_keep_mask, run_wgrad, wgrad_ref_fp64
 
 pytestmark = pytest.mark.gpu
 
@@ -323,59 +323,20 @@ def test_x6_weight_gradient_vs_fp64(n, c1, c2, cout, h, w, in_act, drop, wide, s
     x2 = (torch.randn(n, c2, h, w, generator=g_) * col).cuda() if c2 else None
     dy = (torch.randn(n, cout, h, w, generator=g_) * col).cuda()
     seed = 0xBEEF
-    ctot, ktot = c1 + c2, 9 * (c1 + c2)
 
     def run(flags):
-        wd = ops.WgradDesc(N=n, C1=c1, C2=c2, Hs=h, Ws=w, Cout=cout, Ho=h, Wo=w, KH=3, KW=3, stride=1, pad=1,
-                           in_act=in_act, in_slope=0.0, drop_p=drop, drop_seed=seed, nsplit=1, flags=flags)
-        buf = ctypes.create_string_buffer(96)
-        ops._call("vunet_conv2d_wgrad_variant", ctypes.byref(wd), buf, 96)
-        ns = ops._lib.lib().vunet_conv2d_wgrad_nsplit(ctypes.byref(wd))
-        assert ns >= 1
-        wd.nsplit = ns
-        cp = ops._r32(cout)
-        slabs = torch.full((ns * cp * ktot + ns * cp,), float("nan"), device="cuda")
-        dshift = slabs[ns * cp * ktot:]
-        amx = ops.absmax_partials(x1, x2) if flags == 2 else None
-        amd = ops.absmax_partials(dy) if flags == 2 else None
-        ops._call("vunet_conv2d_wgrad", ctypes.byref(wd), ops._p(x1), ops._p(x2), ops._p(dy), ops._p(slabs),
-                  ops._p(dshift), ops._p(amx), ops._p(amd), ops._stream())
-        dw = torch.empty(cout, ctot, 3, 3, device="cuda")
-        db = torch.empty(cout, device="cuda")
-        v = torch.zeros(cout, ctot, 3, 3, device="cuda")
-        work = torch.empty(cout * (ktot + 1), device="cuda")
-        wn = ops.WnDesc(cout, c1, c2, 3, 3, 1, 0)
-        ops._call("vunet_weightnorm_bwd", ctypes.byref(wn), ops._p(slabs), ops._p(dshift), ns, ops._p(v), None, None,
-                  None, None, ops._p(dw), None, ops._p(db), None, None, ops._p(work), 0, ops._stream())
-        torch.cuda.synchronize()
-        return dw, db, buf.value.decode()
+        return run_wgrad(ops, x1, x2, dy, 3, 1, 1, in_act, drop, seed, flags)
 
     dw6, db6, name6 = run(2 if scheme == "h2" else 0)
     dw3, db3, name3 = run(1)
     assert name6.startswith("conv_wgrad_%s_kernel" % scheme) and not name3.startswith("conv_wgrad_%s_kernel" % scheme), (name6, name3)
     # fp64 reference: the same prologue as the forward, then autograd of the convolution w.r.t. the weight
-    xs = []
-    for i, x in enumerate((x1, x2)):
-        if x is None:
-            continue
-        t = x.double().cpu()
-        if in_act == ops.ACT_ELU:
-            t = F.elu(t)
-        if drop > 0:
-            s = seed if i == 0 else (seed + ops.SEED2_OFFSET) & 0xFFFFFFFF
-            t = t * dropout_keep_mask(tuple(x.shape), drop, s).double() * float(torch.tensor(1.0 / (1.0 - drop),
-                                                                                             dtype=torch.float32))
-        xs.append(t)
-    xin = torch.cat(xs, dim=1)
-    wz = torch.zeros(cout, ctot, 3, 3, dtype=torch.float64, requires_grad=True)
-    (F.conv2d(xin, wz, padding=1) * dy.double().cpu()).sum().backward()
-    ref = wz.grad
+    ref, refb = wgrad_ref_fp64(ops, x1, x2, dy, 3, 1, 1, in_act, drop, seed)
     scale_ = float(ref.abs().max())
     e6 = float((dw6.double().cpu() - ref).abs().max())
     e3 = float((dw3.double().cpu() - ref).abs().max())
     assert e6 <= 3e-6 * scale_, (e6, scale_)
     assert e6 <= 5.0 * e3 + 4e-7 * scale_, (e6, e3, scale_)
-    refb = dy.double().cpu().sum(dim=(0, 2, 3))
     assert_close(db6, refb.float(), rtol=1e-5, atol=1e-5 * float(refb.abs().max()), name="dshift")
 
 
