@@ -295,7 +295,7 @@ class ShapePoseNet:
             steps_before = [[b.step for b in o.buckets] for o in opts]
             err = out = None
             try:
-                with torch.cuda.graph(graph, stream=self._graph_stream):
+                with ops._graph_recording(graph, self._graph_stream):
                     self.optimizer.zero_grad()
                     with ops.prepacked(*self._packed_models()):
                         out = self._step(static, it, None, None)

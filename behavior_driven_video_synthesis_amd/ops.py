@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import gc
 import os
 from collections import namedtuple
 from dataclasses import dataclass
@@ -48,6 +49,27 @@ def _stream():
     if _raw_stream is not None:
         return ctypes.c_void_p(_raw_stream(torch.cuda.current_device()))
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+@contextlib.contextmanager
+def _collector_off():
+    """No collector run inside the block; afterwards the collector is as it was, also when the body raises."""
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
+@contextlib.contextmanager
+def _graph_recording(graph, stream):
+    """``torch.cuda.graph(graph, stream=stream)`` with no collector run while the stream records: a finaliser that frees device
+    memory or destroys another graph (an engine of a model that went out of scope) is not a recordable operation and aborts
+    the process."""
+    with _collector_off(), torch.cuda.graph(graph, stream=stream):
+        yield
 
 
 def _dev(*ts):

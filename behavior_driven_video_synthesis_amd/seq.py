@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-import gc
 import os
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -22,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .ops import _call, _p, _stream
+from .ops import _call, _graph_recording, _p, _stream
 
 MAX_ROWS = 64   # batch rows per launch (four 16-row MFMA tiles); larger batches are processed in chunks
 
@@ -322,6 +321,19 @@ class _GraphCache:
         self.on_evict = None    # weakref.WeakMethod called with the key of a recording that is dropped (its buffers go too)
         self._warmed: set = set()   # run_step's keys that were issued eagerly once: the next call records
 
+    def _record(self, key, issue):
+        """Record ``issue`` on the cache's side stream and keep the recording as ``key``'s (at the cap the oldest one goes)."""
+        torch.cuda.synchronize()
+        if self._stream is None:
+            self._stream = torch.cuda.Stream()
+        g = torch.cuda.CUDAGraph()
+        with _graph_recording(g, self._stream):
+            issue()
+        if len(self.graphs) >= self.MAX_GRAPHS:
+            self.drop(next(iter(self.graphs)))
+        self.graphs[key] = g
+        return g
+
     def run(self, key, issue):
         if not self.enabled or torch.cuda.is_current_stream_capturing():   # (inside someone else's capture: become part of it)
             issue()
@@ -329,25 +341,8 @@ class _GraphCache:
         g = self.graphs.get(key)
         if g is None:
             issue()                      # once eagerly: first-launch work (module load, function attributes) stays outside
-            torch.cuda.synchronize()
-            if self._stream is None:
-                self._stream = torch.cuda.Stream()
-            g = torch.cuda.CUDAGraph()
-            # no collector run while the stream records: a finaliser that frees device memory or destroys another graph
-            # (an engine of a model that went out of scope) is not a recordable operation and aborts the process
-            was_on = gc.isenabled()
-            gc.disable()
-            try:
-                with torch.cuda.graph(g, stream=self._stream):
-                    issue()
-            finally:
-                if was_on:
-                    gc.enable()
-            if len(self.graphs) >= self.MAX_GRAPHS:
-                self.drop(next(iter(self.graphs)))      # the oldest recording
-            self.graphs[key] = g
+            g = self._record(key, issue)
         g.replay()
-
 
     def run_step(self, key, issue):
         """``run`` for a launch sequence with side effects (an optimisation step): every call executes it exactly once -- the
@@ -360,22 +355,7 @@ class _GraphCache:
             self._warmed.add(key)
             issue()
             return "eager"
-        torch.cuda.synchronize()
-        if self._stream is None:
-            self._stream = torch.cuda.Stream()
-        g = torch.cuda.CUDAGraph()
-        was_on = gc.isenabled()
-        gc.disable()
-        try:
-            with torch.cuda.graph(g, stream=self._stream):
-                issue()
-        finally:
-            if was_on:
-                gc.enable()
-        if len(self.graphs) >= self.MAX_GRAPHS:
-            self.drop(next(iter(self.graphs)))
-        self.graphs[key] = g
-        g.replay()
+        self._record(key, issue).replay()
         return "captured"
 
     def clear(self):
@@ -512,50 +492,40 @@ class FlowEngine:
                        map_=None if last else self.blocks[i - 1]["bwd"], scale=blk["scale"], loc=blk["loc"], on_src=1)
             cur = 1 - cur
 
-    def _issue_forward(self, rows: int, p: dict):
-        """ActNorm, half 0, swap + half 1, shuffle per block (models/flow/blocks.py:540-551, :296-309)."""
-        st, cur = p["state"], 0
-        n = len(self.blocks)
-        ld_acc = p["logdet"]
-        ld_acc.zero_()
-        self._step(rows, p["x_in"], self.C, st[0], self.ld, 0, scale=self.blocks[0]["scale"], loc=self.blocks[0]["loc"], logdet=ld_acc)
-        for i in range(n):
-            blk = self.blocks[i]
-            h0, h1 = blk["halves"]
-            part = h0.run(rows, st[cur], self.ld, p["part"])
-            self._step(rows, st[cur], self.ld, st[1 - cur], self.ld, 0, half=h0, st=part, map_=self.swap, logdet=ld_acc)
-            cur = 1 - cur
-            part = h1.run(rows, st[cur], self.ld, p["part"])
-            last = i == n - 1
-            nxt = None if last else self.blocks[i + 1]
-            self._step(rows, st[cur], self.ld, p["x_out"] if last else st[1 - cur], self.C if last else self.ld, 0, half=h1, st=part,
-                       map_=blk["fwd"], scale=None if last else nxt["scale"], loc=None if last else nxt["loc"], on_src=0, logdet=ld_acc)
-            cur = 1 - cur
+    def _issue_forward(self, rows: int, p: dict, s0=None, s1=None, y=None, tile_bufs=None, init: bool = False):
+        """ActNorm, half 0, swap + half 1, shuffle per block (models/flow/blocks.py:540-551, :296-309).  Block i goes from
+        ``s0[i]`` over ``s1[i]`` to ``s0[i + 1]`` and its halves' MLPs write ``y[i][0]`` / ``y[i][1]`` (``tile_bufs``:
+        ``MlpGroup.run``'s).  The default is inference's: every block on the plan's two states (the ping-pong index is back at 0
+        after each block) and every MLP through its two ``part`` buffers; training keeps each block's.
 
-    def _issue_forward_init(self, rows: int, p: dict):
-        """The forward pass of a flow whose ActNorm layers still await their data-dependent initialisation
-        (lib/modules.py:303-305): each block's statistics come from the batch as it reaches that block, so the affine
-        step cannot ride on the previous block's last launch.  Issued eagerly, once."""
-        st, cur = p["state"], 0
+        ``init``: the pass of a flow whose ActNorm layers still await their data-dependent initialisation
+        (lib/modules.py:303-305).  Each block's statistics come from the batch as it reaches that block, so the affine step
+        cannot ride on the previous block's last launch: it runs in place after the block's ``vunet_seq_actnorm_init``.  Issued
+        eagerly, once."""
+        n = len(self.blocks)
+        if s0 is None:
+            s0, s1, y = [p["state"][0]] * n, [p["state"][1]] * n, [[p["part"]] * 2] * n
         ld_acc = p["logdet"]
         ld_acc.zero_()
-        self._step(rows, p["x_in"], self.C, st[0], self.ld, 0)
-        n = len(self.blocks)
-        for i, (blk, mod) in enumerate(zip(self.blocks, self.flow.sub_layers)):
-            norm = mod.norm_layer
-            if norm.initialized.item() == 0:
-                _call("vunet_seq_actnorm_init", _p(st[cur]), self.ld, rows, self.C, _p(norm.loc.data), _p(norm.scale.data), _stream())
-                norm.initialized.fill_(1)
-            self._step(rows, st[cur], self.ld, st[cur], self.ld, 0, scale=blk["scale"], loc=blk["loc"], logdet=ld_acc)
+        if init:
+            self._step(rows, p["x_in"], self.C, s0[0], self.ld, 0)
+        else:
+            self._step(rows, p["x_in"], self.C, s0[0], self.ld, 0, scale=self.blocks[0]["scale"], loc=self.blocks[0]["loc"], logdet=ld_acc)
+        for i, blk in enumerate(self.blocks):
+            if init:
+                norm = self.flow.sub_layers[i].norm_layer
+                if norm.initialized.item() == 0:
+                    _call("vunet_seq_actnorm_init", _p(s0[i]), self.ld, rows, self.C, _p(norm.loc.data), _p(norm.scale.data), _stream())
+                    norm.initialized.fill_(1)
+                self._step(rows, s0[i], self.ld, s0[i], self.ld, 0, scale=blk["scale"], loc=blk["loc"], logdet=ld_acc)
             h0, h1 = blk["halves"]
-            part = h0.run(rows, st[cur], self.ld, p["part"])
-            self._step(rows, st[cur], self.ld, st[1 - cur], self.ld, 0, half=h0, st=part, map_=self.swap, logdet=ld_acc)
-            cur = 1 - cur
-            part = h1.run(rows, st[cur], self.ld, p["part"])
+            part = h0.run(rows, s0[i], self.ld, y[i][0], tile_bufs=tile_bufs)
+            self._step(rows, s0[i], self.ld, s1[i], self.ld, 0, half=h0, st=part, map_=self.swap, logdet=ld_acc)
+            part = h1.run(rows, s1[i], self.ld, y[i][1], tile_bufs=tile_bufs)
             last = i == n - 1
-            self._step(rows, st[cur], self.ld, p["x_out"] if last else st[1 - cur], self.C if last else self.ld, 0, half=h1, st=part,
-                       map_=blk["fwd"], logdet=ld_acc)
-            cur = 1 - cur
+            nxt = None if last or init else self.blocks[i + 1]     # the next block's ActNorm rides on this launch
+            self._step(rows, s1[i], self.ld, p["x_out"] if last else s0[i + 1], self.C if last else self.ld, 0, half=h1, st=part,
+                       map_=blk["fwd"], scale=nxt["scale"] if nxt else None, loc=nxt["loc"] if nxt else None, logdet=ld_acc)
 
     def _run(self, x: torch.Tensor, reverse: bool):
         _need_device(x)
@@ -570,7 +540,7 @@ class FlowEngine:
                 raise ValueError("ActNorm's data-dependent initialisation needs one batch of 2..64 rows")
             p = self._plan(x2.shape[0])
             p["x_in"].copy_(x2)
-            self._issue_forward_init(x2.shape[0], p)
+            self._issue_forward(x2.shape[0], p, init=True)
             return p["x_out"].clone(), p["logdet"][:x2.shape[0]].clone()
         x2 = x.reshape(x.shape[0], -1)
         if x2.shape[1] != self.C:
@@ -614,6 +584,9 @@ class BehaviorEngine:
         self._plans: Dict[int, dict] = {}
         self.graph = _GraphCache()
         self.graph.on_evict = weakref.WeakMethod(self._drop_io)   # (no cycle: the engine's recordings are freed by refcount)
+        # h handed from LSTM step to LSTM step as tiles too (vunet_seq_lstm_gates_tiled_h; batches of more than 32 rows);
+        # "0": the step reads its whole operand from the row-major rows (bit-identical)
+        self.tile_h = os.environ.get("VUNET_SEQ_LSTM_TILED_H", "1") != "0"
 
     def _drop_io(self, key):
         """A recording and the input / output buffers its launches point at live and die together."""
@@ -715,23 +688,31 @@ class BehaviorEngine:
                      xraw=torch.zeros(b_pad, self.ldraw, device=dev),
                      pre=torch.zeros(b_pad, self.H, device=dev), b_in=torch.zeros(rows, self.H, device=dev),
                      heads=torch.zeros(2 * b_pad * self.H, device=dev), io={})
-            # more than 32 rows: h also goes from step to step as tiles (include/vunet_seq_tiled.h: vunet_seq_lstm_gates_tiled_h)
-            tile_h = (os.environ.get("VUNET_SEQ_LSTM_TILED_H", "1") != "0" and b_pad >= 48 and self.H % 32 == 0
-                      and self.hoff % 32 == 0 and self.ldx == self.hoff + self.H)
-            p["ht"] = [torch.zeros(b_pad * self.H, device=dev) for _ in range(2)] if tile_h else None
+            p["ht"] = [torch.zeros(b_pad * self.H, device=dev) for _ in range(2)] if self._h_as_tiles(b_pad) else None
             self._plans[rows] = p
         return p
 
-    def _lstm_step(self, d, wt, bias, p, t, h_out, x_next):
-        """Step t of a roll-out on the plan's ping-pong buffers (t even: 0 -> 1)."""
-        cur, nxt = t % 2, 1 - t % 2
+    def _h_as_tiles(self, b_pad: int) -> bool:
+        """More than 32 rows: h also goes from step to step as tiles (include/vunet_seq_tiled.h), through the plan's two ``ht``."""
+        return self.tile_h and b_pad >= 48 and self.H % 32 == 0 and self.hoff % 32 == 0
+
+    @staticmethod
+    def _ht(p, t):
+        """(tiled h read, tiled h written) by step t of a roll-out, (None, None) where h travels in the rows alone; step 0
+        reads its h from the rows either way."""
         ht = p["ht"]
-        if ht is not None:
-            _call("vunet_seq_lstm_gates_tiled_h", ctypes.byref(d), _p(wt), _p(p["xh"][cur]), _p(ht[cur]) if t else None, _p(bias),
-                  _p(p["c"][cur]), _p(p["c"][nxt]), _p(p["xh"][nxt]), _p(ht[nxt]), h_out, x_next, None, _stream())
+        return (None, None) if ht is None else (ht[t & 1] if t else None, ht[(t + 1) & 1])
+
+    def _lstm_step(self, d, wt, bias, xh_in, xh_out, c_in, c_out, ht_in, ht_out, h_out, x_next, gates):
+        """One LSTM step: operand row ``xh_in`` = [x | 0 | h] and cell ``c_in`` -> ``c_out`` and, in ``xh_out``, the h part of the
+        next step's operand (its x part: the row at ``x_next``, a raw pointer or None).  ``ht_in`` / ``ht_out``: ``_ht``'s.
+        ``h_out``: a copy of h; ``gates``: the gate activations, kept for the backward pass (tensors or None)."""
+        if ht_out is not None:
+            _call("vunet_seq_lstm_gates_tiled_h", ctypes.byref(d), _p(wt), _p(xh_in), _p(ht_in), _p(bias), _p(c_in), _p(c_out), _p(xh_out),
+                  _p(ht_out), _p(h_out), x_next, _p(gates), _stream())
         else:
-            _call("vunet_seq_lstm_gates_tiled", ctypes.byref(d), _p(wt), _p(p["xh"][cur]), _p(bias), _p(p["c"][cur]), _p(p["c"][nxt]),
-                  _p(p["xh"][nxt]), h_out, x_next, None, _stream())
+            _call("vunet_seq_lstm_gates_tiled", ctypes.byref(d), _p(wt), _p(xh_in), _p(bias), _p(c_in), _p(c_out), _p(xh_out), _p(h_out),
+                  x_next, _p(gates), _stream())
 
     def _issue_decode(self, rows, p, x_pose, t_in, start_frame, length, xs, cs):
         dec = self.net.decoder
@@ -741,8 +722,8 @@ class BehaviorEngine:
               self.hoff, _p(p["c"][0]), rows, n, self.H, _stream())
         d = SeqLstmDesc(rows, self.H, self.ldx, self.hoff, n, self.ldraw, length * n)
         for t in range(length):
-            nxt = 1 - t % 2
-            self._lstm_step(d, self.dec_wt, self.dec_b, p, t, None, None)
+            cur, nxt = t % 2, 1 - t % 2
+            self._lstm_step(d, self.dec_wt, self.dec_b, p["xh"][cur], p["xh"][nxt], p["c"][cur], p["c"][nxt], *self._ht(p, t), None, None, None)
             _call("vunet_seq_decoder_out", ctypes.byref(d), _p(p["xh"][nxt]), _p(dec.n_out.weight.detach()), _p(dec.n_out.bias.detach()),
                   _p(p["xraw"]), ctypes.c_void_p(xs.data_ptr() + t * n * esz), ctypes.c_void_p(cs.data_ptr() + t * n * esz), _stream())
 
@@ -781,7 +762,9 @@ class BehaviorEngine:
         d = SeqLstmDesc(rows, self.H, self.ldx, self.hoff, n, self.ldraw, t_in * n)
         for t in range(t_in):   # one launch per time step: gate product, cell update and the next input row
             x_next = ctypes.c_void_p(seq.data_ptr() + (t + 1) * n * esz) if t + 1 < t_in else None
-            self._lstm_step(d, self.enc_wt, self.enc_b, p, t, _p(p["pre"]) if t == t_in - 1 else None, x_next)
+            cur, nxt = t % 2, 1 - t % 2
+            self._lstm_step(d, self.enc_wt, self.enc_b, p["xh"][cur], p["xh"][nxt], p["c"][cur], p["c"][nxt], *self._ht(p, t),
+                            p["pre"] if t == t_in - 1 else None, x_next, None)
         if self.heads is not None:
             w, bias = self.heads
             dl = SeqLinearDesc(rows, self.H, self.H, self.H, ACT_NONE, ACT_NONE, 2, 1, 1)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _call, _p, _stream
+from .ops import _call, _graph_recording, _p, _stream
 from .seq_train import SeqAdamHp
 
 NIN, KP, HID, G3 = (_lib.const("VUNET_CLS_" + n) for n in ("NIN", "KP", "H", "G"))
@@ -248,7 +248,7 @@ class StudyEngine:
             g = torch.cuda.CUDAGraph()
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.graph(g, stream=s):
+            with _graph_recording(g, s):
                 self._iteration(final)
             torch.cuda.current_stream().wait_stream(s)
             self.graphs[final] = g

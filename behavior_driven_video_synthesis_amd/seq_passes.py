@@ -66,3 +66,16 @@ class PassPool:
         lease = PassLease(key, self.acquire(key))
         lease._finalizer = weakref.finalize(lease, self.release, key, lease.slot)
         return lease
+
+
+class KeepsPasses:
+    """For an engine that holds its pool as ``_passes``: the engine's ``max_passes`` attribute."""
+
+    @property
+    def max_passes(self) -> int:
+        """How many forward passes of one shape may be alive (under autograd) at the same time, each in a plan of its own."""
+        return self._passes.max_passes
+
+    @max_passes.setter
+    def max_passes(self, n: int):
+        self._passes.max_passes = int(n)

@@ -25,7 +25,7 @@ from . import _lib
 from .ops import _call, _p, _stream
 from .seq import (ACT_LRELU, BF16_INFERENCE_ONLY, FlowEngine, SeqCouplingDesc, _need_device, _up, _versions, padded_vector,  # noqa: F401
                   weight_image)
-from .seq_passes import PassPool
+from .seq_passes import KeepsPasses, PassPool
 
 LRELU_SLOPE = 0.01   # nn.LeakyReLU() default (lib/modules.py:244)
 
@@ -235,7 +235,7 @@ class TrainLayer:
                           tiles_k=self.kp // 64, kv=self.kp if kv is None else kv, nchunk=nchunk, chunk_z=0, chunk_x=0, dx_raw=dx_raw)
 
 
-class FlowTrainEngine(FlowEngine):
+class FlowTrainEngine(KeepsPasses, FlowEngine):
     """``UnconditionalFlow2`` forward with every intermediate kept, ``FlowLoss``, the backward pass and Adam, for one batch of
     <= 64 rows (``config/behavior_net.yaml``: batch_size 64).  Widths are padded to 64 (the tiles of the backward kernels); a
     parameter whose shape already fits -- every layer of the reference configuration -- is read and updated in place."""
@@ -249,7 +249,8 @@ class FlowTrainEngine(FlowEngine):
         self._adam_args = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.adam: Optional[AdamState] = None
         # autograd's passes in flight (seq_passes).  The flow stage runs one pass per iteration (experiments/behavior_net.py:707-710):
-        # by default one pass at a time, a second forward REPLACES the first one's activations; ``max_passes`` > 1 keeps several
+        # by default one pass at a time: a forward takes the one plan whether or not an earlier pass is alive, and that pass's
+        # backward raises; ``max_passes`` > 1 keeps several, each in a plan of its own
         self._passes = PassPool(1, "the flow")
         # the update sweep beside the next half's chain on a second stream: measured slower (8.1 vs 7.75 ms per step: the sweep's
         # 5120 workgroups hold every CU, the chain's 1024-thread workgroups wait for room) -- off unless asked for
@@ -306,16 +307,6 @@ class FlowTrainEngine(FlowEngine):
     def _all_layers(self):
         return [lay for blk in self.layers for half in blk for net in half for lay in net]
 
-    @property
-    def max_passes(self) -> int:
-        """How many forward passes of one batch size may be alive (under autograd) at the same time, each in a plan of its own.
-        1, the default: a forward takes the one plan whether or not an earlier pass is alive, and that pass's backward raises."""
-        return self._passes.max_passes
-
-    @max_passes.setter
-    def max_passes(self, n: int):
-        self._passes.max_passes = int(n)
-
     # ---- buffers
     def _plan(self, rows: int, slot: int = 0) -> dict:
         """Slot 0 is the fused step's plan (``train_step``: its recorded graph points into it) and the first autograd pass's;
@@ -363,21 +354,8 @@ class FlowTrainEngine(FlowEngine):
 
     # ---- forward, everything kept
     def _issue_train_forward(self, rows: int, p: dict):
-        """As ``FlowEngine._issue_forward`` (models/flow/blocks.py:540-551, :296-309), into buffers that stay alive."""
-        n = len(self.blocks)
-        ld_acc = p["logdet"]
-        ld_acc.zero_()
-        self._step(rows, p["x_in"], self.C, p["s0"][0], self.ld, 0, scale=self.blocks[0]["scale"], loc=self.blocks[0]["loc"], logdet=ld_acc)
-        for i, blk in enumerate(self.blocks):
-            h0, h1 = blk["halves"]
-            tb = p["yt"] if self.tile_activations else None
-            part = h0.run(rows, p["s0"][i], self.ld, p["y"][i][0], tile_bufs=tb)
-            self._step(rows, p["s0"][i], self.ld, p["s1"][i], self.ld, 0, half=h0, st=part, map_=self.swap, logdet=ld_acc)
-            part = h1.run(rows, p["s1"][i], self.ld, p["y"][i][1], tile_bufs=tb)
-            last = i == n - 1
-            nxt = None if last else self.blocks[i + 1]
-            self._step(rows, p["s1"][i], self.ld, p["x_out"] if last else p["s0"][i + 1], self.C if last else self.ld, 0, half=h1, st=part,
-                       map_=blk["fwd"], scale=None if last else nxt["scale"], loc=None if last else nxt["loc"], on_src=0, logdet=ld_acc)
+        """``FlowEngine._issue_forward`` into buffers that stay alive: every block's two states and every MLP layer's output."""
+        self._issue_forward(rows, p, p["s0"], p["s1"], p["y"], tile_bufs=p["yt"] if self.tile_activations else None)
 
     # ---- backward
     def _coupling_bwd(self, rows, p, gbase, ld_g, gslabs, inv_map, scale, in_state, half, heads, gfull, gout, ld_out, dzh):
@@ -457,28 +435,40 @@ class FlowTrainEngine(FlowEngine):
 
     def _issue_train_backward(self, rows: int, p: dict, gz: torch.Tensor, ld_gz: int, tables: dict, hp: Optional[SeqAdamHp]):
         """``gz``: d loss / d z [rows.., ld_gz]; ``p['dld']``: d loss / d logdet.  Per block, last first: the step that ends the
-        block (coupling half 1 + shuffle + the next block's ActNorm), its MLP chain, the update of that half's eight layers;
-        the same for half 0; finally block 0's ActNorm and the ActNorm gradients of all blocks."""
-        n = len(self.blocks)
+        block (coupling half 1 + shuffle + the next block's ActNorm), then that half's MLP -- its input-gradient chain and the
+        update of its eight layers, or with ``fused_dx`` both in ONE pass over W per layer (``vunet_seq_dwx`` updates the layer and
+        leaves its input gradient as raw slabs: no ``vunet_seq_dx``, the chain does not read W a second time); the same for half 0;
+        finally block 0's ActNorm and the ActNorm gradients of all blocks."""
+        n, b_pad = len(self.blocks), p["b_pad"]
         hpp = ctypes.byref(hp) if hp is not None else None
-        if self.fused_dx:
-            return self._issue_train_backward_fused(rows, p, gz, ld_gz, tables, hpp)
-        dw = tables["dw"]
-        gbase, ld_g, gsl = gz, ld_gz, None
-        rng = iter(dw["ranges"])
+        side = self._side() if self.two_streams and not self.fused_dx else None      # (the fused form has no sweep to set aside)
         main = torch.cuda.current_stream()
-        side = self._side() if self.two_streams else None
 
-        def sweep(first, cnt):
-            """The update of one half's eight layers.  Nothing downstream of it in this pass reads what it writes (W, the
-            moments) and the chain never touches the dZ / activation buffers it reads again: it runs on the side stream
-            beside the next half's input-gradient chain, which alone leaves most of the HBM bandwidth idle."""
+        def chain_then_sweep(bi, hi, half):
+            """The update of one half's eight layers after its chain.  Nothing downstream of it in this pass reads what it
+            writes (W, the moments) and the chain never touches the dZ / activation buffers it reads again: with ``two_streams``
+            it runs on the side stream beside the next half's input-gradient chain, which alone leaves most of the HBM
+            bandwidth idle."""
+            dw = tables["dw"]
+            self._mlp_bwd(rows, p, half, p["y"][bi][hi], p["dz"][bi][hi], p["raw_in"][hi])
+            first, cnt = dw["ranges"][2 * (n - 1 - bi) + 1 - hi]     # (the table's order: block, last first; half 1, then 0)
             if side is None:
                 _call("vunet_seq_dw", _p(dw["table"]), dw["n"], first, cnt, rows, hpp, _stream())
                 return
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 _call("vunet_seq_dw", _p(dw["table"]), dw["n"], first, cnt, rows, hpp, _stream())
+
+        def update_with_dx(bi, hi, half):
+            dwx = tables["dwx"]
+            for li in reversed(range(len(half.dims))):
+                first, cnt = dwx["ranges"][(bi, hi, li)]
+                _call("vunet_seq_dwx", _p(dwx["table"]), dwx["n"], first, cnt, rows, hpp, _stream())
+                if li > 0:
+                    _call("vunet_seq_dz_finish", _p(p["raw"]), _p(p["y"][bi][hi][li - 1]), _p(p["dz"][bi][hi][li - 1]), half.nets,
+                          p["S"][li], b_pad, half.dims[li][1], LRELU_SLOPE, _stream())
+        mlp = update_with_dx if self.fused_dx else chain_then_sweep
+        gbase, ld_g, gsl = gz, ld_gz, None
         for i in reversed(range(n)):
             blk = self.blocks[i]
             h0, h1 = blk["halves"]
@@ -487,50 +477,18 @@ class FlowTrainEngine(FlowEngine):
             # half 1: out[c] = A_next(v[fwd[c]]), v = couple_1(S1_i)
             self._coupling_bwd(rows, p, gbase, ld_g, gsl, blk["bwd"], None if last else nxt["scale"], p["s1"][i], h1, p["y"][i][1][-1],
                                None if last else p["gfull"][i + 1], p["g1"], self.ld, p["dz"][i][1][-1])
-            self._mlp_bwd(rows, p, h1, p["y"][i][1], p["dz"][i][1], p["raw_in"][1])
-            sweep(*next(rng))
+            mlp(i, 1, h1)
             # half 0: out[c] = v[swap[c]], v = couple_0(S0_i)
             g0 = p["g0"][i % 2]
             self._coupling_bwd(rows, p, p["g1"], self.ld, p["raw_in"][1], self.inv_swap, None, p["s0"][i], h0, p["y"][i][0][-1], None, g0,
                                self.ld, p["dz"][i][0][-1])
-            self._mlp_bwd(rows, p, h0, p["y"][i][0], p["dz"][i][0], p["raw_in"][0])
-            sweep(*next(rng))
+            mlp(i, 0, h0)
             gbase, ld_g, gsl = g0, self.ld, p["raw_in"][0]
         # the first step of the pass: S0_0 = A_0(x)
         self._coupling_bwd(rows, p, gbase, ld_g, gsl, None, self.blocks[0]["scale"], None, None, None, p["gfull"][0], p["dx"], self.C, None)
         _call("vunet_seq_actnorm_bwd", _p(tables["norm"]), n, self.C, rows, _p(p["dld"]), hpp, _stream())
         if side is not None:
             main.wait_stream(side)
-
-    def _issue_train_backward_fused(self, rows, p, gz, ld_gz, tables, hpp):
-        """The same pass with ONE pass over W per layer: ``vunet_seq_dwx`` updates the layer and leaves its input gradient as raw
-        slabs (no ``vunet_seq_dx``: the chain does not read W a second time)."""
-        n, b_pad = len(self.blocks), p["b_pad"]
-        dwx = tables["dwx"]
-
-        def mlp(bi, hi, half):
-            for li in reversed(range(len(half.dims))):
-                first, cnt = dwx["ranges"][(bi, hi, li)]
-                _call("vunet_seq_dwx", _p(dwx["table"]), dwx["n"], first, cnt, rows, hpp, _stream())
-                if li > 0:
-                    _call("vunet_seq_dz_finish", _p(p["raw"]), _p(p["y"][bi][hi][li - 1]), _p(p["dz"][bi][hi][li - 1]), half.nets,
-                          p["S"][li], b_pad, half.dims[li][1], LRELU_SLOPE, _stream())
-        gbase, ld_g, gsl = gz, ld_gz, None
-        for i in reversed(range(n)):
-            blk = self.blocks[i]
-            h0, h1 = blk["halves"]
-            last = i == n - 1
-            nxt = None if last else self.blocks[i + 1]
-            self._coupling_bwd(rows, p, gbase, ld_g, gsl, blk["bwd"], None if last else nxt["scale"], p["s1"][i], h1, p["y"][i][1][-1],
-                               None if last else p["gfull"][i + 1], p["g1"], self.ld, p["dz"][i][1][-1])
-            mlp(i, 1, h1)
-            g0 = p["g0"][i % 2]
-            self._coupling_bwd(rows, p, p["g1"], self.ld, p["raw_in"][1], self.inv_swap, None, p["s0"][i], h0, p["y"][i][0][-1], None, g0,
-                               self.ld, p["dz"][i][0][-1])
-            mlp(i, 0, h0)
-            gbase, ld_g, gsl = g0, self.ld, p["raw_in"][0]
-        self._coupling_bwd(rows, p, gbase, ld_g, gsl, None, self.blocks[0]["scale"], None, None, None, p["gfull"][0], p["dx"], self.C, None)
-        _call("vunet_seq_actnorm_bwd", _p(tables["norm"]), n, self.C, rows, _p(p["dld"]), hpp, _stream())
 
     def _side(self):
         if self._side_stream is None:
@@ -550,7 +508,7 @@ class FlowTrainEngine(FlowEngine):
             raise ValueError("ActNorm's data-dependent initialisation needs one batch of 2..64 rows")
         p = FlowEngine._plan(self, x2.shape[0])
         p["x_in"].copy_(x2)
-        self._issue_forward_init(x2.shape[0], p)
+        self._issue_forward(x2.shape[0], p, init=True)
         self._all_init = True
 
     def _check_input(self, x: torch.Tensor) -> torch.Tensor:
@@ -717,7 +675,7 @@ def flow_autograd(engine: FlowTrainEngine, x: torch.Tensor):
 from .seq import BehaviorEngine, SeqLinearDesc, SeqLstmDesc, ACT_NONE, linear   # noqa: E402
 
 
-class BehaviorTrainEngine(BehaviorEngine):
+class BehaviorTrainEngine(KeepsPasses, BehaviorEngine):
     """``ResidualBehaviorNet.forward(x1, x2, len)`` (models/pose_behavior_rnn.py:574-586) with every step's operand row, cell
     state and gate activations kept, and its backward pass: back-propagation through time over the decoder's roll-out and the
     encoder's LSTM (csrc/seq_bptt.hip + the matrix kernels of csrc/seq_train.hip).  One batch of <= 64 rows
@@ -740,9 +698,6 @@ class BehaviorTrainEngine(BehaviorEngine):
     def __init__(self, net):
         super().__init__(net)
         self._passes = PassPool(4, "the behaviour net")
-        # h handed from LSTM step to LSTM step as tiles too (vunet_seq_lstm_gates_tiled_h; batches of more than 32 rows);
-        # "0": the step reads its whole operand from the row-major rows (bit-identical)
-        self.tile_h = os.environ.get("VUNET_SEQ_LSTM_TILED_H", "1") != "0"
 
     def _check(self, dev=None):
         net = self.net
@@ -755,15 +710,6 @@ class BehaviorTrainEngine(BehaviorEngine):
         self._pack(dev)
         if self.H % 64:
             raise ValueError("dim_hidden_b must be a multiple of 64 for training on the HIP path")
-
-    @property
-    def max_passes(self) -> int:
-        """How many forward passes of one shape may be alive (under autograd) at the same time: each keeps a plan."""
-        return self._passes.max_passes
-
-    @max_passes.setter
-    def max_passes(self, n: int):
-        self._passes.max_passes = int(n)
 
     def _tplan(self, rows: int, t_in: int, t2: int, length: int, slot: int = 0) -> dict:
         """Slot 0 is the fused step's plan (its recorded graph points into it) and the first autograd pass's."""
@@ -783,8 +729,7 @@ class BehaviorTrainEngine(BehaviorEngine):
                  dgates_d=z(length, bp, 4 * H), dgates_e=z(t_in, bp, 4 * H), gx=z(length + 1, bp, 64), gc=z(bp, H), dy=z(2, bp, H),
                  S=(s_d, s_e, s_h), raw_d=z(s_d * bp * ldx), raw_e=z(s_e * bp * H), raw_h=z(2 * s_h * bp * H),
                  gxs=z(rows, length, n), gmu=z(rows, H), glogstd=z(rows, H),
-                 # h handed from step to step as tiles as well (include/vunet_seq_tiled.h: vunet_seq_lstm_gates_tiled_h), > 32 rows
-                 ht=[z(bp * H) for _ in range(2)] if (self.tile_h and bp >= 48 and H % 32 == 0 and self.hoff % 32 == 0) else None,
+                 ht=[z(bp * H) for _ in range(2)] if self._h_as_tiles(bp) else None,
                  g_dec=z(4 * H, ldx), gb_dec=z(4 * H), g_enc=z(4 * H, ldx), gb_enc=z(4 * H), g_out=z(64, H), gb_out=z(64),
                  g_mu=z(H, H), gb_mu=z(H), g_std=z(H, H), gb_std=z(H), zero_bias=z(4 * H),
                  part=z(length + 3 * rows), scalars=z(6), per_seq=z(length))
@@ -813,16 +758,10 @@ class BehaviorTrainEngine(BehaviorEngine):
         _call("vunet_seq_start", _p(x1), t_in * n, None, None, None, 0, _p(p["xh_e"][0]), self.ldx, self.hoff, _p(p["c_e"][0]), rows, n, H,
               _stream())
         d = SeqLstmDesc(rows, H, self.ldx, self.hoff, n, self.ldraw, t_in * n)
-        ht = p["ht"]
         for t in range(t_in):
             x_next = ctypes.c_void_p(x1.data_ptr() + (t + 1) * n * esz) if t + 1 < t_in else None
-            if ht is not None:
-                _call("vunet_seq_lstm_gates_tiled_h", ctypes.byref(d), _p(self.enc_wt), _p(p["xh_e"][t]), _p(ht[t & 1]) if t else None,
-                      _p(self.enc_b), _p(p["c_e"][t]), _p(p["c_e"][t + 1]), _p(p["xh_e"][t + 1]), _p(ht[(t + 1) & 1]),
-                      _p(p["pre"]) if t == t_in - 1 else None, x_next, _p(p["gates_e"][t]), _stream())
-                continue
-            _call("vunet_seq_lstm_gates_tiled", ctypes.byref(d), _p(self.enc_wt), _p(p["xh_e"][t]), _p(self.enc_b), _p(p["c_e"][t]),
-                  _p(p["c_e"][t + 1]), _p(p["xh_e"][t + 1]), _p(p["pre"]) if t == t_in - 1 else None, x_next, _p(p["gates_e"][t]), _stream())
+            self._lstm_step(d, self.enc_wt, self.enc_b, p["xh_e"][t], p["xh_e"][t + 1], p["c_e"][t], p["c_e"][t + 1], *self._ht(p, t),
+                            p["pre"] if t == t_in - 1 else None, x_next, p["gates_e"][t])
         w, bias = self.heads
         dl = SeqLinearDesc(rows, H, H, H, ACT_NONE, ACT_NONE, 2, 1, 1)
         linear(dl, w, p["pre"], bias, p["heads"])
@@ -834,13 +773,8 @@ class BehaviorTrainEngine(BehaviorEngine):
         d = SeqLstmDesc(rows, H, self.ldx, self.hoff, n, self.ldraw, length * n)
         xs, cs = p["xs"], p["cs"]
         for t in range(length):
-            if ht is not None:
-                _call("vunet_seq_lstm_gates_tiled_h", ctypes.byref(d), _p(self.dec_wt), _p(p["xh_d"][t]), _p(ht[t & 1]) if t else None,
-                      _p(self.dec_b), _p(p["c_d"][t]), _p(p["c_d"][t + 1]), _p(p["xh_d"][t + 1]), _p(ht[(t + 1) & 1]), None, None,
-                      _p(p["gates_d"][t]), _stream())
-            else:
-                _call("vunet_seq_lstm_gates_tiled", ctypes.byref(d), _p(self.dec_wt), _p(p["xh_d"][t]), _p(self.dec_b), _p(p["c_d"][t]),
-                      _p(p["c_d"][t + 1]), _p(p["xh_d"][t + 1]), None, None, _p(p["gates_d"][t]), _stream())
+            self._lstm_step(d, self.dec_wt, self.dec_b, p["xh_d"][t], p["xh_d"][t + 1], p["c_d"][t], p["c_d"][t + 1], *self._ht(p, t),
+                            None, None, p["gates_d"][t])
             _call("vunet_seq_decoder_out", ctypes.byref(d), _p(p["xh_d"][t + 1]), _p(dec.n_out.weight.detach()), _p(dec.n_out.bias.detach()),
                   _p(p["xraw"]), ctypes.c_void_p(xs.data_ptr() + t * n * esz), ctypes.c_void_p(cs.data_ptr() + t * n * esz), _stream())
 

@@ -104,6 +104,32 @@ def test_batched_start_times_and_graph_replay_are_bit_identical():
         assert eager["final"][si] == together["final"][si]
 
 
+def test_the_study_step_is_recorded_with_the_collector_off():
+    """``StudyEngine.step`` records its iteration under ``ops._graph_recording``: no collector run while the stream captures
+    (a finaliser that frees device memory there aborts the process), and the collector is back on afterwards."""
+    import gc
+    from behavior_driven_video_synthesis_amd import seq_cls as C
+    bs, t, h = 37, 7, 32
+    sets = {k: seeded_randn(f"k.{bs}.{k}", (3 * bs, t, 51), 3) for k in ("orig", "prior", "cross", "self")}
+    embed = seeded_randn(f"k.{bs}.embed", (3 * bs, h), 3)
+    init = R.inputs("noflow")[1][:1]
+    blocks = torch.stack([torch.stack([C.pack_classifier(init[0][k]) for k in ("prior", "cross", "self")])])
+    reg = torch.stack([C.pack_regressor(init[0]["regressor"], h)])
+    eng = C.StudyEngine(_cuda(sets), embed.cuda(), [t - 1], bs, 3, blocks, reg)
+    seen, issue = [], eng._iteration
+
+    def probe(final):
+        seen.append((torch.cuda.is_current_stream_capturing(), gc.isenabled()))
+        issue(final)
+    eng._iteration = probe
+    assert gc.isenabled()
+    eng.step(False)
+    eng.step(False)              # (a replay: nothing is issued)
+    torch.cuda.synchronize()
+    assert seen == [(True, False)]
+    assert gc.isenabled()
+
+
 def test_argument_checks():
     sets, init = R.inputs("noflow")
     E = _E()

@@ -524,6 +524,24 @@ def test_hip_graph_replay_is_bit_identical_to_eager(with_regressor):
         assert float(sa["regressor"]["optimizer"]["state"][0]["step"]) == 14.0
 
 
+def test_the_training_step_is_recorded_with_the_collector_off(monkeypatch):
+    """The trainer records its step under ``ops._graph_recording``: no collector run while the stream captures (a finaliser
+    that frees device memory there aborts the process); the eager steps before and the time after run with the collector on."""
+    import gc
+    from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import ShapePoseNet
+    seen, step = [], ShapePoseNet._step
+
+    def probe(self, *args):
+        seen.append((torch.cuda.is_current_stream_capturing(), gc.isenabled()))
+        return step(self, *args)
+    monkeypatch.setattr(ShapePoseNet, "_step", probe)
+    assert gc.isenabled()
+    tr, _ = _graph_run(True, 5)
+    assert len(tr._graphs) == 1
+    assert seen == [(False, True)] * 3 + [(True, False)]     # (three eager steps, the recording; the fifth step is a replay)
+    assert gc.isenabled()
+
+
 def test_hip_graph_replay_with_the_adversarial_term():
     """the step WITH the adversarial term -- generator loss through the PartDiscriminator on a random window
     whose corner is read from device memory (ops.CropWindow), one discriminator step with its own fused Adam -- replayed

@@ -4,15 +4,18 @@
     python tools/fused_conv_trace.py record run2.json                      # ... twice, in two fresh processes
     python tools/fused_conv_trace.py merge run1.json run2.json <commit> > tests/fused_conv_trace.json
     python tools/fused_conv_trace.py check tests/fused_conv_trace.json     # the tree under test against the fixture
+    python tools/fused_conv_trace.py --cases=seq_host_cases record|merge|check ...   # the same for tests/seq_host_trace.json
 
 `record` runs every case of tests/fused_conv_cases.py (copy that file and this one into the parent's checkout: they use
-only what both trees have) and writes the records and, with `values`, the tensors' bytes beside them (<out>.npz: needed
+only what both trees have), or of another cases module under tests/ named by a leading `--cases=MODULE` (one with CASES,
+record_case and missing_coverage: tests/seq_host_cases.py pins the seq engines' host code in tests/seq_host_trace.json) and writes the records and, with `values`, the tensors' bytes beside them (<out>.npz: needed
 only if a hash differs between the two recordings).  `merge` refuses
 recordings whose traces or profile triples differ or that miss a required entry point / return code; a tensor whose hash
 differs between the two is pinned by value instead (base64 fp32 in the fixture's "loose" section, listed in its header,
 compared at 1e-6 of its max-abs).  Never regenerate the fixture from the code under test.
 """
 import base64
+import importlib
 import json
 import os
 import sys
@@ -24,8 +27,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+CASES_MODULE = "fused_conv_cases"
+
+
 def record(out, values=None):
-    import fused_conv_cases as fc
+    fc = importlib.import_module(CASES_MODULE)
     records, blobs = {}, {}
     for name in fc.CASES:
         records[name], raw = fc.record_case(name)
@@ -82,7 +88,7 @@ def compare(fixture, name, rec, raw):
 
 
 def check(path):
-    import fused_conv_cases as fc
+    fc = importlib.import_module(CASES_MODULE)
     fixture, failed = json.load(open(path)), 0
     for name in fc.CASES:
         bad = compare(fixture, name, *fc.record_case(name))
@@ -93,6 +99,8 @@ def check(path):
 
 if __name__ == "__main__":
     cmds = {"record": record, "merge": merge, "check": check}
+    if len(sys.argv) > 1 and sys.argv[1].startswith("--cases="):
+        CASES_MODULE = sys.argv.pop(1)[len("--cases="):]
     if len(sys.argv) < 3 or sys.argv[1] not in cmds:
         sys.exit(__doc__)
     sys.exit(cmds[sys.argv[1]](*sys.argv[2:]))
