@@ -8,9 +8,10 @@ fixed-point coefficients, and the kernels restate it exactly (pinned against Pil
 * ``frames_to_images``  uint8 stack [N, Hmax, Wmax, 3] (+ one geometry row per image) -> images and a per-image status;
 * ``stack_frames``      frames of mixed sizes -> one padded stack and their sizes;
 * ``bounding_box``      keypoints -> the geometry row of the reference's square crop (``get_bounding_box``);
-* ``batch_images``      the trainers' hook: makes ``pose_img`` / ``app_img`` where a batch brings ``pose_img_u8`` / ``app_img_u8``.
+* ``batch_images``      the trainers' hook: makes ``pose_img`` / ``app_img`` where a batch brings ``pose_img_u8`` / ``app_img_u8``
+                        -- or ``pose_img_jpeg`` / ``app_img_jpeg``, encoded streams that jpeg_decode.py decodes into such a stack.
 
-The JPEG decode and the dataset plumbing stay on the host.  There is no CPU path."""
+The dataset plumbing stays on the host, and of the JPEG decode only the entropy walk (jpeg_decode.py).  There is no CPU path."""
 from __future__ import annotations
 
 import math
@@ -206,11 +207,42 @@ def bounding_box(kps, frame_hw, relax: float = 0.1) -> np.ndarray:
     return np.asarray(rows, dtype=np.int32)
 
 
+def decode_jpeg(batch: dict, device=None) -> dict:
+    """``batch`` with its encoded inputs decoded: for K in ``pose_img``, ``app_img``, where ``batch[K + "_jpeg"]`` (a sequence of
+    ``bytes``, baseline JPEG streams) is present and neither ``batch[K]`` nor ``batch[K + "_u8"]`` is, ``K + "_jpeg"`` is replaced by
+    ``K + "_u8"`` -- the stack of ``jpeg_decode.decode_batch`` on ``device`` (None: the current GPU), valid until the next batch is
+    decoded -- and, where the batch brings no ``K + "_geom"``, by whole-frame geometry rows from the decoded sizes.  (With
+    ``pose_img_aug``, whose route takes no geometry, the sizes go to ``pose_img_hw`` instead.)  The batch itself where it brings
+    no such key."""
+    out = None
+    for key in KEYS:
+        streams = batch.get(key + "_jpeg")
+        if streams is None or key in batch or key + "_u8" in batch:
+            continue
+        from . import jpeg_decode
+        out = dict(batch) if out is None else out
+        if device is None or torch.device(device).type != "cuda":
+            frames, hw = jpeg_decode.decode_batch(streams, tag=key)
+        else:
+            with torch.cuda.device(device):
+                frames, hw = jpeg_decode.decode_batch(streams, tag=key)
+        del out[key + "_jpeg"]
+        out[key + "_u8"] = frames
+        if key == "pose_img" and "pose_img_aug" in batch:
+            out.setdefault("pose_img_hw", hw)
+        elif key + "_geom" not in batch:
+            h, w = hw[:, 0:1], hw[:, 1:2]
+            out[key + "_geom"] = torch.cat([h, w, torch.zeros_like(h), torch.zeros_like(h), w, h], dim=1)
+    return batch if out is None else out
+
+
 def to_device(batch: dict, device) -> dict:
     """``batch`` with its raw-frame inputs (``K_u8``, ``K_geom`` for K in ``pose_img``, ``app_img``) as device tensors, host
     geometry checked first -- what a step that is recorded into a hipGraph needs (its inputs are static device buffers).  The
     batch itself where it brings none of them or they are on the device already.  ``pose_img_aug`` / ``pose_img_hw`` (the
-    matrices and frame sizes of appearance_aug.batch_appearance) are staged alike."""
+    matrices and frame sizes of appearance_aug.batch_appearance) are staged alike.  Encoded inputs (``K_jpeg``) are decoded first
+    (``decode_jpeg``): a recorded step is replayed on the stack the decode has just filled."""
+    batch = decode_jpeg(batch, device)
     out = None
     for key in KEYS:
         u8 = batch.get(key + "_u8")
@@ -237,7 +269,9 @@ def to_device(batch: dict, device) -> dict:
 def batch_images(batch: dict, size: int) -> Dict[str, torch.Tensor]:
     """The images a batch leaves to the package: for K in ``pose_img``, ``app_img``, where ``batch[K + "_u8"]`` is present and
     ``batch[K]`` is not, ``K -> frames_to_images(batch[K + "_u8"], batch.get(K + "_geom"), size)[0]`` (and ``K + "_status"``).
-    An empty dict -- no launch, nothing touched -- for a batch of ready fp32 images."""
+    A batch that brings ``K + "_jpeg"`` instead has it decoded first (``decode_jpeg``).  An empty dict -- no launch, nothing
+    touched -- for a batch of ready fp32 images."""
+    batch = decode_jpeg(batch)
     made = {}
     for key in KEYS:
         if key + "_u8" in batch and key not in batch:

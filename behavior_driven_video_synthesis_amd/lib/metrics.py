@@ -66,8 +66,9 @@ def psnr(rec: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> to
 
 def _with_images(model, batch):
     """``batch`` with ``pose_img`` / ``app_img`` made on the GPU from raw uint8 frames where it brings ``pose_img_u8`` /
-    ``app_img_u8`` (+ ``*_geom``) instead (image_input.batch_images); the batch itself otherwise."""
-    if "pose_img_u8" not in batch and "app_img_u8" not in batch:
+    ``app_img_u8`` (+ ``*_geom``) or encoded ``pose_img_jpeg`` / ``app_img_jpeg`` instead (image_input.batch_images); the batch
+    itself otherwise."""
+    if not any(k in batch for k in ("pose_img_u8", "app_img_u8", "pose_img_jpeg", "app_img_jpeg")):
         return batch
     from .. import image_input
     made = image_input.batch_images(batch, model.spatial_size)

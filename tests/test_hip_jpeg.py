@@ -1,0 +1,266 @@
+"""The JPEG decode on the GPU (csrc/jpeg.hip, behavior_driven_video_synthesis_amd/jpeg_decode.py) against Pillow's bytes
+(tests/golden/g23_jpeg.npz) and the restatement (tests/jpeg_ref.py, itself held to Pillow in tests/test_jpeg_ref.py): the whole
+fixture in one call (A), one stream at a time (B), no allocation on a second call (C), the chain into the bicubic route (D), the
+refused and damaged streams (E), a synthetic image wider than one block of lanes (F) and the trainers' wiring, eagerly and from a
+replayed hipGraph (G).
+
+Everything is exact: the decoder after the entropy walk is integer arithmetic, so there is no tolerance.  No case is skipped and
+none goes through the Pillow fallback (``fallback`` stays False throughout)."""
+import copy
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import jpeg_ref as R
+
+pytestmark = pytest.mark.gpu
+
+FIX = R.load_fixture()
+NAMES = list(FIX["cases"])
+SENTINEL = 0xAB
+
+
+def _streams(names=NAMES):
+    return [FIX["cases"][n]["data"] for n in names]
+
+
+def _check(frames, hw, names, pad=None):
+    got = frames.cpu().numpy()
+    for i, n in enumerate(names):
+        rgb = FIX["cases"][n]["rgb"]
+        h, w = rgb.shape[:2]
+        assert hw[i].tolist() == [h, w], n
+        assert np.array_equal(got[i, :h, :w], rgb), (n, int((got[i, :h, :w] != rgb).sum()))
+        if pad is not None:
+            assert (got[i, h:] == pad).all() and (got[i, :, w:] == pad).all(), n
+
+
+def test_whole_fixture_in_one_call_equals_pillow_and_leaves_the_padding():
+    """A: 20 streams of mixed sizes, samplings and gray, restart intervals and custom tables among them, in ONE call -- one upload,
+    two launches -- into a stack larger than any of them; bytes outside each image keep the sentinel."""
+    from behavior_driven_video_synthesis_amd import jpeg_decode as J
+    out = torch.full((len(NAMES), 53, 75, 3), SENTINEL, dtype=torch.uint8, device="cuda")
+    frames, hw = J.decode_batch(_streams(), hmax=53, wmax=75, out=out)
+    assert frames is out and hw.dtype == torch.int32 and tuple(hw.shape) == (len(NAMES), 2)
+    _check(frames, hw, NAMES, pad=SENTINEL)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_one_stream_at_a_time_equals_pillow(name):
+    """B: the same bytes from a batch of one (the stack is the image: no padding at all)."""
+    from behavior_driven_video_synthesis_amd import jpeg_decode as J
+    frames, hw = J.decode_batch([FIX["cases"][name]["data"]], threads=1)
+    assert tuple(frames.shape) == (1,) + FIX["cases"][name]["rgb"].shape
+    _check(frames, hw, [name])
+
+
+def test_second_call_at_a_shape_allocates_nothing():
+    """C: the staging buffer, its device mirror, the planes and the default output stack are reused -- same addresses, and the
+    allocator's count of live bytes does not move."""
+    from behavior_driven_video_synthesis_amd import jpeg_decode as J
+    J.clear_buffers()
+    names = NAMES[::2]
+    frames, hw = J.decode_batch(_streams(names), tag="c")
+    (buf,) = [b for k, b in J._buffers.items() if k[2] == "c"]
+    ptrs = (frames.data_ptr(), buf.stage.data_ptr(), buf.dev.data_ptr(), buf.planes.data_ptr())
+    torch.cuda.synchronize()
+    live = torch.cuda.memory_allocated()
+    again, hw2 = J.decode_batch(_streams(NAMES[1::2]), tag="c")      # other streams, the same sizes
+    assert (again.data_ptr(), buf.stage.data_ptr(), buf.dev.data_ptr(), buf.planes.data_ptr()) == ptrs
+    assert torch.cuda.memory_allocated() == live and buf.stage.is_pinned()
+    _check(again, hw2, NAMES[1::2])
+    J.clear_buffers()
+
+
+def test_frames_to_images_takes_the_decoded_stack_as_pillows_frames():
+    """D: the bicubic route fed ``decode_batch``'s stack equals the route fed Pillow's stored frames, bit for bit."""
+    from behavior_driven_video_synthesis_amd import image_input as I, jpeg_decode as J
+    names = ["s420_17x23_smooth", "gray_24x31_noise", "s422_33x41_noise", "s420_50x70_q30opt_smooth", "checker_24x24_noise"]
+    frames, hw = J.decode_batch(_streams(names))
+    geom = torch.cat([hw, torch.zeros_like(hw), hw[:, 1:2], hw[:, 0:1]], dim=1)
+    stack, hw_ref = I.stack_frames([FIX["cases"][n]["rgb"] for n in names])
+    assert torch.equal(hw, hw_ref)
+    got, status = I.frames_to_images(frames, geom, 32)
+    want, _ = I.frames_to_images(stack, geom, 32)
+    assert not status.cpu().numpy().any() and torch.equal(got, want)
+
+
+def test_refused_and_damaged_streams_raise():
+    """E: progressive and CMYK -> ``JpegUnsupported``; truncations -> ``JpegCorrupt``; nothing is decoded in their place."""
+    from behavior_driven_video_synthesis_amd import jpeg_decode as J
+    ok = FIX["cases"]["s420_16x16_smooth"]["data"]
+    for name, data in FIX["refused"].items():
+        with pytest.raises(J.JpegUnsupported) as e:
+            J.decode_batch([ok, data])
+        assert e.value.index == 1 and e.value.code in J.REASONS, name
+    name, offs = FIX["truncated"]
+    data = FIX["cases"][name]["data"]
+    for o in offs:
+        with pytest.raises(J.JpegCorrupt):
+            J.decode_batch([ok, data[:o]])
+
+
+def test_wide_synthetic_image_equals_the_restatement():
+    """F: coefficients made here (no encoder needed), 37 x 613 in 4:2:0 and 19 x 300 in 4:2:2 in one batch -- more than one block of
+    256 lanes per row, more than one group of 32 blocks per component, large coefficients that clamp -- through the library's two
+    entry points, against the restatement's planes and colours."""
+    from behavior_driven_video_synthesis_amd import jpeg_decode as J
+    from behavior_driven_video_synthesis_amd.ops import _call, _p, _stream
+    g = np.random.default_rng(7)
+    shapes = [(37, 613, 2, 2), (19, 300, 2, 1)]
+    rows = (J.JpegImg * len(shapes))()
+    coefs, qtabs, want, at, blocks = [], [], [], 0, 0
+    for j, (h, w, hs, vs) in enumerate(shapes):
+        mc, mr = -(-w // (8 * hs)), -(-h // (8 * vs))
+        grids = [(mr * vs, mc * hs), (mr, mc), (mr, mc)]
+        cs = []
+        for bh, bw in grids:
+            c = np.zeros((bh, bw, 64), dtype=np.int16)
+            c[..., 0] = g.integers(-1000, 1000, size=(bh, bw))
+            c[..., 1:10] = g.integers(-60, 60, size=(bh, bw, 9))
+            c[..., 63] = g.integers(-8, 8, size=(bh, bw))
+            cs.append(c)
+        q = g.integers(1, 24, size=(3, 64)).astype(np.uint16)
+        want.append(R.to_rgb(R.planes(cs, q), dict(height=h, width=w, ncomp=3, hsamp=hs, vsamp=vs)))
+        n = sum(bh * bw for bh, bw in grids)
+        r = rows[j]
+        r.coef_off, r.plane_off, r.q_off, r.block0, r.slot = at, at, 192 * j, blocks, j
+        r.height, r.width, r.ncomp, r.hsamp, r.vsamp = h, w, 3, hs, vs
+        (r.bh0, r.bw0), (r.bh1, r.bw1) = grids[0], grids[1]
+        coefs.append(R.flat_coef(cs))
+        qtabs.append(q.reshape(-1))
+        at, blocks = at + 64 * n, blocks + n
+    coef, qtab = torch.from_numpy(np.concatenate(coefs)).cuda(), torch.from_numpy(np.concatenate(qtabs).astype(np.int16)).cuda()
+    imgs = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).cuda()
+    planes = torch.empty(at, dtype=torch.uint8, device="cuda")
+    out = torch.full((2, 40, 613, 3), SENTINEL, dtype=torch.uint8, device="cuda")
+    host = ctypes.cast(rows, ctypes.c_void_p)
+    _call("vunet_jpeg_idct", _p(coef), at, _p(qtab), qtab.numel(), _p(imgs), host, 2, _p(planes), at, _stream())
+    _call("vunet_jpeg_to_rgb", _p(planes), at, _p(imgs), host, 2, 2, 40, 613, _p(out), _stream())
+    got = out.cpu().numpy()
+    for j, (h, w, _, _) in enumerate(shapes):
+        assert np.array_equal(got[j, :h, :w], want[j]), (j, int((got[j, :h, :w] != want[j]).sum()))
+        assert (got[j, h:] == SENTINEL).all() and (got[j, :, w:] == SENTINEL).all()
+    assert min(w.min() for w in want) == 0 and max(w.max() for w in want) == 255
+    # a descriptor that points outside its buffers is refused before anything is launched
+    rows[1].coef_off += 64
+    with pytest.raises(RuntimeError, match="vunet_jpeg_idct"):
+        _call("vunet_jpeg_idct", _p(coef), at, _p(qtab), qtab.numel(), _p(imgs), host, 2, _p(planes), at, _stream())
+    rows[1].coef_off -= 64
+    rows[1].height = 41
+    with pytest.raises(RuntimeError, match="vunet_jpeg_to_rgb"):
+        _call("vunet_jpeg_to_rgb", _p(planes), at, _p(imgs), host, 2, 2, 40, 613, _p(out), _stream())
+
+
+# ---- G: wiring ---------------------------------------------------------------------------------------------------------------
+MIXED = [("s420_17x23_smooth", "gray_24x31_noise"), ("s422_33x41_noise", "s420_41x39_rstrow_smooth"),
+         ("s444_40x56_rst4_noise", "checker_24x24_smooth")]
+SAME = [("s420_50x70_q30opt_smooth", "s420_50x70_q100_noise"), ("s420_50x70_q100_smooth", "s420_50x70_q30opt_noise")]
+
+
+def _tiny(default, **training):
+    """The smallest trainer config of tests/test_hip_image_input.py: 32^2, nf 8..16."""
+    cfg = copy.deepcopy(default)
+    cfg["data"]["spatial_size"] = 32
+    cfg["architecture"].update(nf_start=8, nf_max=16)
+    cfg["training"].update(training)
+    return cfg
+
+
+@functools.lru_cache(maxsize=None)
+def _pillow_stack(pair):
+    """Pillow's stored frames of a pair of streams as the ``pose_img_u8`` stack and its whole-frame geometry; made once."""
+    from behavior_driven_video_synthesis_amd import image_input as I
+    stack, hw = I.stack_frames([FIX["cases"][n]["rgb"] for n in pair])
+    return stack, torch.cat([hw, torch.zeros_like(hw), hw[:, 1:2], hw[:, 0:1]], dim=1)
+
+
+def _batch(seed, pair, jpeg):
+    from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import synthetic_batch
+    batch = synthetic_batch(2, 32, "cuda:0", seed=seed)
+    del batch["pose_img"]
+    if jpeg:
+        batch["pose_img_jpeg"] = _streams(pair)
+    else:
+        stack, geom = _pillow_stack(pair)
+        batch["pose_img_u8"], batch["pose_img_geom"] = stack.clone(), geom.clone()
+    return batch
+
+
+def _run(jpeg, capture, pairs, steps):
+    from behavior_driven_video_synthesis_amd import ops
+    from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import DEFAULT_CONFIG, ShapePoseNet
+    ops.set_dropout_seed(8642)
+    cfg = _tiny(DEFAULT_CONFIG, lr=2e-3, n_init_batches=1, gamma_step=1e-3, information_max=5.0, train_regressor=False)
+    tr = ShapePoseNet(cfg, device="cuda:0", vgg_width_div=8, total_steps=50, vgg_synthetic=True, hip_graph=False)
+    if capture is not None:
+        tr.enable_hip_graph(capture=capture)
+    outs = []
+    for i in range(steps):
+        o = tr.train_fn(_batch(900 + i, pairs[i % len(pairs)], jpeg))
+        outs.append({k: float(o[k]) for k in ("loss", "likelihood_loss", "kl_loss", "gamma")})
+    torch.cuda.synchronize()
+    ops.set_dropout_step(None)
+    return tr, outs
+
+
+def _same_state(a, b):
+    for (k, p), (_, q) in zip(a.vunet.state_dict().items(), b.vunet.state_dict().items()):
+        assert torch.equal(p, q), k
+    for x, y in zip(a.optimizer.buckets, b.optimizer.buckets):
+        assert torch.equal(x.exp_avg, y.exp_avg) and torch.equal(x.exp_avg_sq, y.exp_avg_sq)
+
+
+def test_shape_pose_net_trains_from_jpeg_bytes_as_from_pillows_frames():
+    """G: a ShapePoseNet given ``pose_img_jpeg`` (pairs of mixed sizes, samplings and gray) takes, bit for bit, the steps of a twin
+    fed ``pose_img_u8`` stacked from Pillow's frames of the same streams."""
+    a, oa = _run(True, None, MIXED, 3)
+    b, ob = _run(False, None, MIXED, 3)
+    assert oa == ob, (oa, ob)
+    assert all(o["loss"] == o["loss"] for o in oa) and len({o["loss"] for o in oa}) == 3
+    _same_state(a, b)
+
+
+def test_hip_graph_replay_fed_jpeg_bytes_follows_new_frames():
+    """G: the recorded step replayed on the stack each step's decode has just filled (the decode is issued ahead of the replay;
+    fresh streams every step, one stack shape, ONE graph), against the twin whose static input is Pillow's frames: 6 steps, every
+    one bit-identical."""
+    a, oa = _run(True, True, SAME, 6)
+    assert len(a._graphs) == 1
+    b, ob = _run(False, True, SAME, 6)
+    assert oa == ob, (oa, ob)
+    assert len({o["loss"] for o in oa}) == len(oa)
+    _same_state(a, b)
+
+
+def test_metrics_and_the_vunet_trainer_take_jpeg_batches():
+    """G: ``compute_ssim``, ``compute_fid`` and ``experiments.vunet.Vunet.train_fn`` fed ``pose_img_jpeg`` equal the calls fed
+    Pillow's frames."""
+    from behavior_driven_video_synthesis_amd import ops
+    from behavior_driven_video_synthesis_amd.experiments import vunet as V
+    from behavior_driven_video_synthesis_amd.lib import metrics
+    tr, _ = _run(False, None, MIXED, 1)
+    jb, ub = _batch(77, MIXED[1], True), _batch(77, MIXED[1], False)
+    feats = lambda im: im.flatten(1)[:, :4]   # noqa: E731
+    gt = np.random.default_rng(0).normal(size=(8, 4))
+    torch.manual_seed(3)
+    s_j = metrics.compute_ssim(tr.vunet, [jb])
+    f_j = metrics.compute_fid(tr.vunet, [jb, jb, jb, jb], feats, gt_features=gt)
+    torch.manual_seed(3)
+    s_u = metrics.compute_ssim(tr.vunet, [ub])
+    f_u = metrics.compute_fid(tr.vunet, [ub, ub, ub, ub], feats, gt_features=gt)
+    assert s_j == s_u and f_j == f_u and s_j == s_j
+
+    def run(jpeg):
+        ops.set_dropout_seed(1357)
+        cfg = _tiny(V.DEFAULT_CONFIG, dropout_prob=0.0)
+        t = V.Vunet(cfg, device="cuda:0", n_channels_x=3, vgg_width_div=8, total_steps=8, vgg_synthetic=True)
+        torch.manual_seed(5)
+        return t, float(t.train_fn(_batch(41, MIXED[0], jpeg))["loss"])
+    (a, la), (b, lb) = run(True), run(False)
+    assert la == lb and la == la
+    for (k, p), (_, q) in zip(a.vunet.state_dict().items(), b.vunet.state_dict().items()):
+        assert torch.equal(p, q), k
