@@ -9,6 +9,7 @@
 // each sample row with one 8-byte store; its two passes exchange the block through LDS (rows padded to 9 words).
 #include "common.h"
 #include "jpeg_entropy.h"
+#include "jpeg_imgs.h"
 
 namespace {
 
@@ -175,35 +176,6 @@ __global__ __launch_bounds__(256) void jpeg_to_rgb_kernel(const uint8_t* __restr
   o[2] = clamp255(b);
 }
 
-// every row of the host copy of the descriptors against the buffers: nothing is launched on a row that could index outside them
-bool imgs_ok(const vunet_jpeg_img* h, int N, int64_t coef_count, int64_t qtab_count, int64_t planes_bytes, int Hmax, int Wmax,
-             int slots, int64_t* total) {
-  int64_t blocks = 0;
-  for (int n = 0; n < N; ++n) {
-    const vunet_jpeg_img& m = h[n];
-    const bool s = (m.hsamp == 1 && m.vsamp == 1) || (m.ncomp == 3 && m.hsamp == 2 && (m.vsamp == 1 || m.vsamp == 2));
-    if (!s || (m.ncomp != 1 && m.ncomp != 3) || m.height < 1 || m.width < 1 || m.height > Hmax || m.width > Wmax) return false;
-    if (m.bw0 < (m.width + 7) / 8 || m.bh0 < (m.height + 7) / 8 || m.bw0 > 8192 || m.bh0 > 8192) return false;
-    if (m.ncomp == 3) {
-      const int cw = (m.width + m.hsamp - 1) / m.hsamp, ch = (m.height + m.vsamp - 1) / m.vsamp;
-      if (m.bw1 < (cw + 7) / 8 || m.bh1 < (ch + 7) / 8 || m.bw1 > 8192 || m.bh1 > 8192) return false;
-    } else if (m.bw1 != 0 || m.bh1 != 0) {
-      return false;
-    }
-    const int64_t nb = (int64_t)m.bw0 * m.bh0 + 2 * (int64_t)m.bw1 * m.bh1;
-    if (m.block0 != blocks || m.slot < 0 || m.slot >= slots) return false;
-    blocks += nb;
-    if (blocks > 0x7FFFFFFF) return false;
-    if (m.coef_off < 0 || m.coef_off % 64 || m.coef_off > coef_count - nb * 64) return false;
-    if (m.q_off < 0 || m.q_off % 8 || m.q_off > qtab_count - m.ncomp * 64) return false;
-    if (m.plane_off < 0 || m.plane_off % 16 || m.plane_off > planes_bytes - nb * 64) return false;
-  }
-  *total = blocks;
-  return true;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int vunet_jpeg_parse(const uint8_t* bytes, int64_t len, vunet_jpeg_info* info) {
@@ -220,8 +192,8 @@ extern "C" int vunet_jpeg_idct(const int16_t* coef, int64_t coef_count, const ui
                                int64_t planes_bytes, void* stream) {
   int64_t total = 0;
   if (!coef || !qtab || !imgs || !imgs_host || !planes || N < 1 || N > 65535 || coef_count < 0 || qtab_count < 0 || planes_bytes < 0 ||
-      !aligned16(coef) || !aligned16(qtab) || !aligned16(planes) ||
-      !imgs_ok(imgs_host, N, coef_count, qtab_count, planes_bytes, 65535, 65535, 65535, &total))
+      !vunet_jpeg::aligned16(coef) || !vunet_jpeg::aligned16(qtab) || !vunet_jpeg::aligned16(planes) ||
+      !vunet_jpeg::imgs_ok(imgs_host, N, coef_count, qtab_count, planes_bytes, 65535, 65535, 65535, &total))
     return VUNET_ERR_ARG;
   const unsigned groups = (unsigned)((total + kBlocksPerGroup - 1) / kBlocksPerGroup);
   VUNET_LAUNCH(jpeg_idct_kernel, dim3(groups), dim3(256), 0, (hipStream_t)stream, coef, qtab, imgs, (int)N, (int)total, planes);
@@ -233,7 +205,7 @@ extern "C" int vunet_jpeg_to_rgb(const uint8_t* planes, int64_t planes_bytes, co
                                  void* stream) {
   int64_t total = 0;
   if (!planes || !imgs || !imgs_host || !out || N < 1 || N > 65535 || Nslots < N || Nslots > 65535 || Hmax < 1 || Hmax > 65535 || Wmax < 1 || Wmax > 65535 ||
-      planes_bytes < 0 || !imgs_ok(imgs_host, N, INT64_MAX, INT64_MAX, planes_bytes, Hmax, Wmax, Nslots, &total))
+      planes_bytes < 0 || !vunet_jpeg::imgs_ok(imgs_host, N, INT64_MAX, INT64_MAX, planes_bytes, Hmax, Wmax, Nslots, &total))
     return VUNET_ERR_ARG;
   const unsigned lanes = Wmax >= 256 ? 256u : (unsigned)((Wmax + 63) / 64 * 64);
   VUNET_LAUNCH(jpeg_to_rgb_kernel, dim3((unsigned)((Wmax + (int)lanes - 1) / (int)lanes), (unsigned)Hmax, (unsigned)N), dim3(lanes), 0,
