@@ -257,17 +257,6 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restric
   }
 }
 
-// the block grids of every row are exactly what vunet_jpeg_encode_info gives (the kernels' padding and dummy-block rules assume it)
-bool grids_exact(const vunet_jpeg_img* h, int N, int ncomp) {
-  for (int n = 0; n < N; ++n) {
-    const vunet_jpeg_img& m = h[n];
-    vunet_jpeg_info I;
-    if (vunet_jpeg::encode_info(m.height, m.width, m.ncomp, m.hsamp, m.vsamp, &I) != VUNET_OK) return false;
-    if ((ncomp && m.ncomp != ncomp) || m.bw0 != I.bw0 || m.bh0 != I.bh0 || m.bw1 != I.bw1 || m.bh1 != I.bh1) return false;
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" int vunet_jpeg_encode_info(int32_t height, int32_t width, int32_t ncomp, int32_t hsamp, int32_t vsamp,
@@ -284,6 +273,38 @@ extern "C" int vunet_jpeg_entropy_encode(const int16_t* coef, const vunet_jpeg_i
   return vunet_jpeg::entropy_encode(coef, info, qtab, out, cap, len);
 }
 
+extern "C" int vunet_jpeg_symbol_histogram(const int16_t* coef, const vunet_jpeg_info* info, uint32_t* hist) {
+  return vunet_jpeg::symbol_histogram(coef, info, hist);
+}
+
+extern "C" int vunet_jpeg_optimal_table(const uint32_t* freq, uint8_t* counts, uint8_t* symbols, int32_t* nsym) {
+  return vunet_jpeg::optimal_table(freq, counts, symbols, nsym);
+}
+
+extern "C" int vunet_jpeg_optimal_tables(const uint32_t* hist, int32_t N, int32_t ntab, uint8_t* counts, uint8_t* symbols,
+                                         uint32_t* codes, int32_t* failed) {
+  return vunet_jpeg::optimal_tables(hist, N, ntab, counts, symbols, codes, failed);
+}
+
+extern "C" int vunet_jpeg_entropy_encode_tables(const int16_t* coef, const vunet_jpeg_info* info, const uint16_t* qtab,
+                                                const uint8_t* counts, const uint8_t* symbols, uint8_t* out, int64_t cap,
+                                                int64_t* len) {
+  return vunet_jpeg::entropy_encode_tables(coef, info, qtab, counts, symbols, out, cap, len);
+}
+
+extern "C" int vunet_jpeg_write_header(const vunet_jpeg_info* info, const uint16_t* qtab, const uint8_t* counts,
+                                       const uint8_t* symbols, uint8_t* out, int64_t cap, int64_t* len) {
+  return vunet_jpeg::write_header(info, qtab, counts, symbols, out, cap, len);
+}
+
+extern "C" int vunet_jpeg_code_words(const uint8_t* counts, const uint8_t* symbols, uint32_t* codes) {
+  if (!codes || !counts != !symbols) return VUNET_ERR_ARG;
+  vunet_jpeg::Tables t = vunet_jpeg::std_tables();
+  if (counts && !vunet_jpeg::caller_tables(counts, symbols, 4, t)) return VUNET_ERR_ARG;
+  vunet_jpeg::code_words(t, 4, codes);
+  return VUNET_OK;
+}
+
 extern "C" int vunet_jpeg_from_rgb(const uint8_t* frames, int32_t Nslots, int32_t Hmax, int32_t Wmax, int32_t channels,
                                    const vunet_jpeg_img* imgs, const vunet_jpeg_img* imgs_host, int32_t N, uint8_t* planes,
                                    int64_t planes_bytes, void* stream) {
@@ -291,7 +312,7 @@ extern "C" int vunet_jpeg_from_rgb(const uint8_t* frames, int32_t Nslots, int32_
   if (!frames || !imgs || !imgs_host || !planes || N < 1 || N > 65535 || Nslots < 1 || Nslots > 65535 || Hmax < 1 || Hmax > 65535 ||
       Wmax < 1 || Wmax > 65535 || (channels != 1 && channels != 3) || planes_bytes < 0 || !vunet_jpeg::aligned16(planes) ||
       !vunet_jpeg::imgs_ok(imgs_host, N, INT64_MAX, INT64_MAX, planes_bytes, Hmax, Wmax, Nslots, &total) ||
-      !grids_exact(imgs_host, N, channels))
+      !vunet_jpeg::grids_exact(imgs_host, N, channels))
     return VUNET_ERR_ARG;
   int pw = 0, ph = 0;   // the largest padded luma plane: what the grid has to cover
   for (int n = 0; n < N; ++n) {
@@ -312,7 +333,7 @@ extern "C" int vunet_jpeg_fdct(const uint8_t* planes, int64_t planes_bytes, cons
   if (!planes || !qtab || !imgs || !imgs_host || !coef || N < 1 || N > 65535 || coef_count < 0 || qtab_count < 0 || planes_bytes < 0 ||
       !vunet_jpeg::aligned16(coef) || !vunet_jpeg::aligned16(qtab) || !vunet_jpeg::aligned16(planes) ||
       !vunet_jpeg::imgs_ok(imgs_host, N, coef_count, qtab_count, planes_bytes, 65535, 65535, 65535, &total) ||
-      !grids_exact(imgs_host, N, 0))
+      !vunet_jpeg::grids_exact(imgs_host, N, 0))
     return VUNET_ERR_ARG;
   const unsigned groups = (unsigned)((total + kBlocksPerGroup - 1) / kBlocksPerGroup);
   VUNET_LAUNCH(jpeg_fdct_kernel, dim3(groups), dim3(256), 0, (hipStream_t)stream, planes, qtab, imgs, (int)N, (int)total, coef);

@@ -1,11 +1,14 @@
 // The host half of the baseline JPEG encoder: the quantisation tables, the stream's segments and the Huffman coder.  Plain C++17,
-// no HIP, header-only; included by jpeg_enc.hip (the C ABI of include/vunet_jpeg_enc.h) and by tools/jpeg_enc_host_check.cpp.  The
+// no HIP, header-only; included by jpeg_enc.hip (the C ABI of include/vunet_jpeg_enc.h), by jpeg_huff.hip (the same coder as device
+// launches; its argument checks are here) and by tools/jpeg_enc_host_check.cpp and tools/jpeg_opt_host_check.cpp.  The
 // mirror image of jpeg_entropy.h, whose coefficient layout and zigzag table it shares.  Every byte goes through Sink::put, which
 // counts it always and stores it only below `cap` (put_bits stores four at once where all four fit, and falls back to put where
 // they do not): nothing is written at or beyond out + cap, and the count at the end is the length the stream needs.
 // Errors are VUNET_ERR_ARG and VUNET_JPEG_ERR_CAPACITY / _RANGE; nothing throws, nothing is static but the constant tables.
 //
-// The Huffman tables are Annex K's (libjpeg's defaults, std_huff_tables); no optimised tables, no restart markers.
+// The Huffman tables are Annex K's (libjpeg's defaults, std_huff_tables) or the caller's; symbol_histogram and optimal_table give
+// the tables libjpeg's optimize_coding (Pillow's optimize=True) would: a second pass over the coefficients.  code_words states
+// tables as the device coder (jpeg_huff.hip) reads them, write_header writes SOI .. SOS alone for it.  No restart markers.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -49,6 +52,8 @@ static const uint8_t kAcChromaVals[162] = {
 
 constexpr int64_t kHeaderBound = 1024;    // SOI .. SOS and EOI: 623 bytes with three components
 constexpr int64_t kBlockBound = 416;      // 22 bits of DC + 63 * 26 bits of AC = 208 bytes, every one of them stuffed
+constexpr int64_t kBlockBits = 27 + 63 * 26;   // under any tables: a 16-bit code and 11 bits of DC, 16 and 10 per AC term
+constexpr int64_t kStuffChunk = 1024;     // the device coder's unstuffed streams start at multiples of it (jpeg_huff.hip)
 
 inline int encode_info(int32_t height, int32_t width, int32_t ncomp, int32_t hs, int32_t vs, vunet_jpeg_info* info) {
   if (!info || height < 1 || width < 1 || height > 65535 || width > 65535) return VUNET_ERR_ARG;
@@ -78,6 +83,18 @@ inline int encode_info(int32_t height, int32_t width, int32_t ncomp, int32_t hs,
 inline bool encode_info_ok(const vunet_jpeg_info& I) {
   vunet_jpeg_info want;
   return encode_info(I.height, I.width, I.ncomp, I.hsamp, I.vsamp, &want) == VUNET_OK && same_info(I, want);
+}
+
+// the block grids of every descriptor row are exactly what encode_info gives (the kernels' padding, dummy-block and scan-order
+// rules assume it); ncomp != 0: and every row has that many components
+inline bool grids_exact(const vunet_jpeg_img* h, int N, int ncomp) {
+  for (int n = 0; n < N; ++n) {
+    const vunet_jpeg_img& m = h[n];
+    vunet_jpeg_info I;
+    if (encode_info(m.height, m.width, m.ncomp, m.hsamp, m.vsamp, &I) != VUNET_OK) return false;
+    if ((ncomp && m.ncomp != ncomp) || m.bw0 != I.bw0 || m.bh0 != I.bh0 || m.bw1 != I.bw1 || m.bh1 != I.bh1) return false;
+  }
+  return true;
 }
 
 inline int quant_tables(int32_t quality, uint16_t* qtab) {
@@ -178,24 +195,71 @@ inline void put_dht(Sink& s, int cls_id, const uint8_t* counts, const uint8_t* s
 
 inline int bit_length(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
 
-inline int entropy_encode(const int16_t* coef, const vunet_jpeg_info* info, const uint16_t* qtab, uint8_t* out, int64_t cap,
-                          int64_t* len) {
-  if (!coef || !info || !qtab || !out || !len || cap < 0 || !encode_info_ok(*info)) return VUNET_ERR_ARG;
-  *len = 0;
-  const vunet_jpeg_info& I = *info;
-  for (int i = 0; i < 64 * I.ncomp; ++i)
-    if (qtab[i] < 1 || qtab[i] > 255) return VUNET_ERR_ARG;
-  if (I.ncomp == 3 && memcmp(qtab + 64, qtab + 128, 64 * sizeof(uint16_t)) != 0) return VUNET_ERR_ARG;
+// The four Huffman tables of a stream in DHT order -- DC0, AC0, DC1, AC1 -- as code counts per length 1 .. 16 and symbols.
+// Annex K's, or the caller's: counts [4][16] and symbols [4][256] (a gray image reads the first two of each).
+struct Tables {
+  const uint8_t* counts[4];
+  const uint8_t* symbols[4];
+  int total[4];
+};
+
+inline Tables std_tables() {
+  return Tables{{kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits}, {kDcVals, kAcLumaVals, kDcVals, kAcChromaVals}, {12, 162, 12, 162}};
+}
+
+// caller's tables: every code fits its length (the counts are a prefix code's), at most 256 symbols, no symbol twice
+inline bool caller_tables(const uint8_t* counts, const uint8_t* symbols, int ntab, Tables& t) {
+  for (int k = 0; k < ntab; ++k) {
+    const uint8_t* c = counts + 16 * k;
+    const uint8_t* v = symbols + 256 * k;
+    uint32_t code = 0;
+    int total = 0;
+    for (int len = 1; len <= 16; ++len) {
+      code += c[len - 1];
+      total += c[len - 1];
+      if (code > (1u << len)) return false;
+      code <<= 1;
+    }
+    if (total > 256) return false;
+    bool seen[256] = {};
+    for (int i = 0; i < total; ++i) {
+      if (seen[v[i]]) return false;
+      seen[v[i]] = true;
+    }
+    t.counts[k] = c;
+    t.symbols[k] = v;
+    t.total[k] = total;
+  }
+  return true;
+}
+
+// the tables as the device coder reads them: codes [ntab][256], len << 16 | code, 0 = no such symbol
+inline void code_words(const Tables& t, int ntab, uint32_t* codes) {
+  for (int k = 0; k < ntab; ++k) {
+    Codes c;
+    build_codes(t.counts[k], t.symbols[k], c);
+    for (int i = 0; i < 256; ++i) codes[256 * k + i] = ((uint32_t)c.len[i] << 16) | c.code[i];
+  }
+}
+
+inline bool encode_args_ok(const vunet_jpeg_info* info, const uint16_t* qtab) {
+  if (!info || !qtab || !encode_info_ok(*info)) return false;
+  for (int i = 0; i < 64 * info->ncomp; ++i)
+    if (qtab[i] < 1 || qtab[i] > 255) return false;
+  return info->ncomp != 3 || memcmp(qtab + 64, qtab + 128, 64 * sizeof(uint16_t)) == 0;
+}
+
+// SOI .. SOS: everything in front of the scan's bytes
+inline void put_header(Sink& s, const vunet_jpeg_info& I, const uint16_t* qtab, const Tables& t) {
   const int ntab = I.ncomp == 3 ? 2 : 1;
-  Sink s{out, cap};
   s.put16(0xFFD8);
   static const uint8_t app0[18] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
   s.put_bytes(app0, 18);
-  for (int t = 0; t < ntab; ++t) {
+  for (int k = 0; k < ntab; ++k) {
     s.put16(0xFFDB);
     s.put16(67);
-    s.put(t);
-    for (int i = 0; i < 64; ++i) s.put(qtab[64 * t + kZigzag[i]]);
+    s.put(k);
+    for (int i = 0; i < 64; ++i) s.put(qtab[64 * k + kZigzag[i]]);
   }
   s.put16(0xFFC0);
   s.put16(8 + 3 * I.ncomp);
@@ -208,12 +272,8 @@ inline int entropy_encode(const int16_t* coef, const vunet_jpeg_info* info, cons
     s.put(c == 0 ? (I.hsamp << 4 | I.vsamp) : 0x11);
     s.put(c == 0 ? 0 : 1);
   }
-  put_dht(s, 0x00, kDcLumaBits, kDcVals, 12);
-  put_dht(s, 0x10, kAcLumaBits, kAcLumaVals, 162);
-  if (I.ncomp == 3) {
-    put_dht(s, 0x01, kDcChromaBits, kDcVals, 12);
-    put_dht(s, 0x11, kAcChromaBits, kAcChromaVals, 162);
-  }
+  static const int ids[4] = {0x00, 0x10, 0x01, 0x11};
+  for (int k = 0; k < 2 * ntab; ++k) put_dht(s, ids[k], t.counts[k], t.symbols[k], t.total[k]);
   s.put16(0xFFDA);
   s.put16(6 + 2 * I.ncomp);
   s.put(I.ncomp);
@@ -224,12 +284,27 @@ inline int entropy_encode(const int16_t* coef, const vunet_jpeg_info* info, cons
   s.put(0);
   s.put(63);
   s.put(0);
+}
 
-  Codes dc[2], ac[2];
-  build_codes(kDcLumaBits, kDcVals, dc[0]);
-  build_codes(kAcLumaBits, kAcLumaVals, ac[0]);
-  build_codes(kDcChromaBits, kDcVals, dc[1]);
-  build_codes(kAcChromaBits, kAcChromaVals, ac[1]);
+// counts / symbols NULL (both): Annex K's tables
+inline int write_header(const vunet_jpeg_info* info, const uint16_t* qtab, const uint8_t* counts, const uint8_t* symbols, uint8_t* out,
+                        int64_t cap, int64_t* len) {
+  if (!out || !len || cap < 0 || !encode_args_ok(info, qtab) || !counts != !symbols) return VUNET_ERR_ARG;
+  *len = 0;
+  Tables t = std_tables();
+  if (counts && !caller_tables(counts, symbols, info->ncomp == 3 ? 4 : 2, t)) return VUNET_ERR_ARG;
+  Sink s{out, cap};
+  put_header(s, *info, qtab, t);
+  *len = s.n;
+  return s.n > cap ? VUNET_JPEG_ERR_CAPACITY : VUNET_OK;
+}
+
+// The one walk over an image's blocks in scan order: MCUs left to right, top to bottom; per MCU the blocks component by component,
+// row-major.  `on_dc(table, size, diff)` and `on_ac(table, symbol, size, value)` see exactly the symbols the coder emits -- the DC
+// difference's bit length; one 0xF0 per 16 zeros of a run (size 0), (run << 4) | size per non-zero term, 0x00 where the block does
+// not end at position 63 -- and return false to stop (a symbol their table lacks).  `table`: 0 for luma, 1 for chroma.
+template <class Dc, class Ac>
+inline int walk_blocks(const int16_t* coef, const vunet_jpeg_info& I, Dc&& on_dc, Ac&& on_ac) {
   const int16_t* base[3];
   int bw[3], nh[3], nv[3];
   base[0] = coef;
@@ -245,8 +320,7 @@ inline int entropy_encode(const int16_t* coef, const vunet_jpeg_info* info, cons
   for (int my = 0; my < I.mcu_rows; ++my) {
     for (int mx = 0; mx < I.mcu_cols; ++mx) {
       for (int c = 0; c < I.ncomp; ++c) {
-        const Codes& hd = dc[c ? 1 : 0];
-        const Codes& ha = ac[c ? 1 : 0];
+        const int t = c ? 1 : 0;
         for (int by = 0; by < nv[c]; ++by) {
           for (int bx = 0; bx < nh[c]; ++bx) {
             const int16_t* blk = base[c] + 64 * ((int64_t)(my * nv[c] + by) * bw[c] + (mx * nh[c] + bx));
@@ -254,8 +328,7 @@ inline int entropy_encode(const int16_t* coef, const vunet_jpeg_info* info, cons
             pred[c] = blk[0];
             int nb = bit_length((uint32_t)(diff < 0 ? -diff : diff));
             if (nb > 11) return VUNET_JPEG_ERR_RANGE;
-            s.put_bits(hd.code[nb], hd.len[nb]);
-            if (nb) s.put_bits((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1), nb);
+            if (!on_dc(t, nb, diff)) return VUNET_ERR_ARG;
             int run = 0;
             for (int k = 1; k < 64; ++k) {
               const int32_t v = blk[kZigzag[k]];
@@ -263,23 +336,194 @@ inline int entropy_encode(const int16_t* coef, const vunet_jpeg_info* info, cons
                 ++run;
                 continue;
               }
-              for (; run > 15; run -= 16) s.put_bits(ha.code[0xF0], ha.len[0xF0]);
+              for (; run > 15; run -= 16)
+                if (!on_ac(t, 0xF0, 0, 0)) return VUNET_ERR_ARG;
               nb = bit_length((uint32_t)(v < 0 ? -v : v));
               if (nb > 10) return VUNET_JPEG_ERR_RANGE;
-              const int sym = (run << 4) | nb;
-              s.put_bits(((uint32_t)ha.code[sym] << nb) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1)), ha.len[sym] + nb);
+              if (!on_ac(t, (run << 4) | nb, nb, v)) return VUNET_ERR_ARG;
               run = 0;
             }
-            if (run) s.put_bits(ha.code[0x00], ha.len[0x00]);
+            if (run && !on_ac(t, 0x00, 0, 0)) return VUNET_ERR_ARG;
           }
         }
       }
     }
   }
+  return VUNET_OK;
+}
+
+// hist [4][256] in DHT order (DC0, AC0, DC1, AC1; a gray image leaves the last two zero): how often the coder emits each symbol
+inline int symbol_histogram(const int16_t* coef, const vunet_jpeg_info* info, uint32_t* hist) {
+  if (!coef || !info || !hist || !encode_info_ok(*info)) return VUNET_ERR_ARG;
+  memset(hist, 0, 4 * 256 * sizeof(uint32_t));
+  return walk_blocks(
+      coef, *info,
+      [&](int t, int nb, int32_t) {
+        ++hist[512 * t + nb];
+        return true;
+      },
+      [&](int t, int sym, int, int32_t) {
+        ++hist[512 * t + 256 + sym];
+        return true;
+      });
+}
+
+// libjpeg's jpeg_gen_optimal_table (jchuff.c), restated: freq [256] -> the code counts per length 1 .. 16 and the symbols, ordered
+// by length and within a length by value; *nsym of them.  Symbol 256 is a reserved code point of frequency 1, so that no code is all
+// ones; it always ends up among the longest codes and is taken away last.  Code lengths above 16 are shortened pairwise
+// (section K.2's procedure).  A code that would need more than 32 bits before that is VUNET_ERR_ARG, as libjpeg refuses it.
+inline int optimal_table(const uint32_t* freq_in, uint8_t* counts, uint8_t* symbols, int32_t* nsym) {
+  if (!freq_in || !counts || !symbols || !nsym) return VUNET_ERR_ARG;
+  constexpr int kMaxLen = 32;
+  int64_t freq[257];
+  int codesize[257], others[257];
+  int long_bits[kMaxLen + 1] = {};
+  for (int i = 0; i < 256; ++i) freq[i] = freq_in[i];
+  freq[256] = 1;
+  for (int i = 0; i < 257; ++i) {
+    codesize[i] = 0;
+    others[i] = -1;
+  }
+  for (;;) {
+    // the two smallest non-zero frequencies, ties to the larger index
+    int c1 = -1, c2 = -1;
+    int64_t v = INT64_MAX;
+    for (int i = 0; i <= 256; ++i)
+      if (freq[i] && freq[i] <= v) {
+        v = freq[i];
+        c1 = i;
+      }
+    v = INT64_MAX;
+    for (int i = 0; i <= 256; ++i)
+      if (freq[i] && freq[i] <= v && i != c1) {
+        v = freq[i];
+        c2 = i;
+      }
+    if (c2 < 0) break;
+    freq[c1] += freq[c2];
+    freq[c2] = 0;
+    for (++codesize[c1]; others[c1] >= 0;) {
+      c1 = others[c1];
+      ++codesize[c1];
+    }
+    others[c1] = c2;
+    for (++codesize[c2]; others[c2] >= 0;) {
+      c2 = others[c2];
+      ++codesize[c2];
+    }
+  }
+  for (int i = 0; i <= 256; ++i)
+    if (codesize[i]) {
+      if (codesize[i] > kMaxLen) return VUNET_ERR_ARG;
+      ++long_bits[codesize[i]];
+    }
+  for (int i = kMaxLen; i > 16; --i)
+    while (long_bits[i] > 0) {
+      int j = i - 2;
+      while (long_bits[j] == 0) --j;
+      long_bits[i] -= 2;
+      ++long_bits[i - 1];
+      long_bits[j + 1] += 2;
+      --long_bits[j];
+    }
+  int last = 16;
+  while (last > 0 && long_bits[last] == 0) --last;
+  if (last > 0) --long_bits[last];   // (no symbol at all: an empty table)
+  for (int i = 1; i <= 16; ++i) counts[i - 1] = (uint8_t)long_bits[i];
+  int p = 0;
+  for (int len = 1; len <= kMaxLen; ++len)
+    for (int j = 0; j < 256; ++j)
+      if (codesize[j] == len) symbols[p++] = (uint8_t)j;
+  *nsym = p;
+  return VUNET_OK;
+}
+
+// A batch's tables from its histograms, as the device route needs them between two launches: hist [N][4][256] -> counts [N][4][16],
+// symbols [N][4][256] and codes [N][4][256] (code_words' form); the first `ntab` (2 or 4) tables of an image are built, the others
+// are empty.  -> the first code that is not VUNET_OK, *failed the image it belongs to
+inline int optimal_tables(const uint32_t* hist, int32_t N, int32_t ntab, uint8_t* counts, uint8_t* symbols, uint32_t* codes,
+                          int32_t* failed) {
+  if (!hist || !counts || !symbols || !codes || !failed || N < 1 || (ntab != 2 && ntab != 4)) return VUNET_ERR_ARG;
+  memset(counts, 0, (size_t)N * 64);
+  memset(symbols, 0, (size_t)N * 1024);
+  for (int n = 0; n < N; ++n) {
+    uint8_t* c = counts + (size_t)n * 64;
+    uint8_t* s = symbols + (size_t)n * 1024;
+    *failed = n;
+    for (int t = 0; t < ntab; ++t) {
+      int32_t nsym = 0;
+      const int rc = optimal_table(hist + (size_t)n * 1024 + 256 * t, c + 16 * t, s + 256 * t, &nsym);
+      if (rc != VUNET_OK) return rc;
+    }
+    Tables T;
+    if (!caller_tables(c, s, 4, T)) return VUNET_ERR_ARG;
+    code_words(T, 4, codes + (size_t)n * 1024);
+  }
+  *failed = -1;
+  return VUNET_OK;
+}
+
+// counts / symbols NULL (both): Annex K's tables, the stream vunet_jpeg_entropy_encode writes.  A symbol the caller's tables lack
+// is VUNET_ERR_ARG (*len is then 0).
+inline int entropy_encode_tables(const int16_t* coef, const vunet_jpeg_info* info, const uint16_t* qtab, const uint8_t* counts,
+                                 const uint8_t* symbols, uint8_t* out, int64_t cap, int64_t* len) {
+  if (!coef || !out || !len || cap < 0 || !encode_args_ok(info, qtab) || !counts != !symbols) return VUNET_ERR_ARG;
+  *len = 0;
+  const vunet_jpeg_info& I = *info;
+  Tables t = std_tables();
+  if (counts && !caller_tables(counts, symbols, I.ncomp == 3 ? 4 : 2, t)) return VUNET_ERR_ARG;
+  Sink s{out, cap};
+  put_header(s, I, qtab, t);
+  Codes dc[2], ac[2];
+  for (int k = 0; k < (I.ncomp == 3 ? 2 : 1); ++k) {
+    build_codes(t.counts[2 * k], t.symbols[2 * k], dc[k]);
+    build_codes(t.counts[2 * k + 1], t.symbols[2 * k + 1], ac[k]);
+  }
+  const int rc = walk_blocks(
+      coef, I,
+      [&](int k, int nb, int32_t diff) {
+        const Codes& h = dc[k];
+        if (!h.len[nb]) return false;
+        s.put_bits(h.code[nb], h.len[nb]);
+        if (nb) s.put_bits((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1), nb);
+        return true;
+      },
+      [&](int k, int sym, int nb, int32_t v) {
+        const Codes& h = ac[k];
+        if (!h.len[sym]) return false;
+        s.put_bits(((uint32_t)h.code[sym] << nb) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1)), h.len[sym] + nb);
+        return true;
+      });
+  if (rc != VUNET_OK) return rc;
   s.flush_bits();
   s.put16(0xFFD9);
   *len = s.n;
   return s.n > cap ? VUNET_JPEG_ERR_CAPACITY : VUNET_OK;
 }
 
+// The device coder's spans, one (offset, bits) pair per image: where the image's unstuffed scan bytes start in `raw` and how many
+// bits they are.  The images lie one after the other, each from a multiple of kStuffChunk: the pairs must say exactly that, no
+// image may have more bits than its blocks can code to (or than 32 bits count), and the buffers must hold what follows from them:
+// `raw` every chunk, `out` two bytes per unstuffed byte (every byte stuffed), `chunks` one word per chunk.  -> *nchunks
+inline bool spans_ok(const int64_t* spans, const vunet_jpeg_img* h, int N, int64_t raw_bytes, int64_t out_cap, int64_t chunk_count,
+                     int64_t* nchunks) {
+  int64_t at = 0, out = 0;
+  for (int n = 0; n < N; ++n) {
+    const int64_t nb = (int64_t)h[n].bw0 * h[n].bh0 + 2 * (int64_t)h[n].bw1 * h[n].bh1, bits = spans[2 * n + 1];
+    if (spans[2 * n] != at || bits < 1 || bits > nb * kBlockBits || bits > 0xFFFFFFFFll) return false;
+    const int64_t bytes = (bits + 7) / 8;
+    at += (bytes + kStuffChunk - 1) / kStuffChunk * kStuffChunk;
+    out += 2 * bytes;
+  }
+  if (at > raw_bytes || out > out_cap || out > 0xFFFFFFFFll || at / kStuffChunk > chunk_count) return false;
+  *nchunks = at / kStuffChunk;
+  return true;
+}
+
+inline int entropy_encode(const int16_t* coef, const vunet_jpeg_info* info, const uint16_t* qtab, uint8_t* out, int64_t cap,
+                          int64_t* len) {
+  return entropy_encode_tables(coef, info, qtab, nullptr, nullptr, out, cap, len);
+}
+
 }  // namespace vunet_jpeg
+

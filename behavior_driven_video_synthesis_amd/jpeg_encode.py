@@ -6,18 +6,25 @@ csrc/jpeg_huff_enc.h, include/vunet_jpeg_enc.h):
 * colour conversion, chroma down-sampling, the forward DCT and the quantiser are two HIP launches for the whole batch, whatever the
   images' sizes, after ONE small upload (descriptors and tables), and ONE download of the quantised coefficients into a reused
   pinned buffer;
-* the entropy coder, a serial bit walk, stays on the host: the library's C++ on ``jpeg_decode``'s small thread pool (ctypes
-  releases the GIL).
+* the entropy coder, a serial bit walk, runs on the host by default: the library's C++ on ``jpeg_decode``'s small thread pool
+  (ctypes releases the GIL);
+* ``entropy="device"`` keeps it on the GPU (csrc/jpeg_huff.hip): per block its bit count, a prefix sum per image, every block's
+  bits packed at its offset, the bytes stuffed -- one launch per stage, two host waits -- and ONLY the scans' bytes are downloaded;
+  the host writes the header and ``FF D9`` around them.  Same bytes as the host route;
+* ``optimize=True`` is Pillow's: Huffman tables built from the image's own symbol counts (libjpeg's ``jpeg_gen_optimal_table``),
+  a second pass over the coefficients on the host route, a histogram launch and one more round trip (histograms down, tables up)
+  on the device route.  The streams carry their tables: every decoder reads them.
 
 The bytes are Pillow's ``Image.save(.., "JPEG", quality=q, subsampling=s)`` (libjpeg-turbo's defaults: the "islow" integer forward
-DCT, the Annex K tables), pinned against Pillow 12.2.0 by tests/golden/g24_jpeg_encode.npz.  ASSUMED, NOT PINNED: ``cv2.imwrite``
+DCT, the Annex K tables), pinned against Pillow 12.2.0 by tests/golden/g24_jpeg_encode.npz, and with ``optimize=True`` Pillow's
+``optimize=True`` bytes (tests/golden/g25_jpeg_optimize.npz).  ASSUMED, NOT PINNED: ``cv2.imwrite``
 writes with other defaults (quality 95, 4:2:0) -- ``quality=95`` mimics it -- and OpenCV is no dependency of this package.
 
 * ``encode_batch``  frames -> ``list[bytes]``;
 * ``save_images``   a thin loop over it: one ``.jpg`` per frame;
 * ``JpegEncodeError``  carries the C error code.
 
-Not done: optimised Huffman tables, progressive mode, restart markers.  There is no CPU path."""
+Not done: progressive mode, restart markers.  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes
@@ -31,10 +38,14 @@ from .jpeg_decode import MAX_SIDE, MAX_THREADS, JpegImg, JpegInfoC, _pool
 from .ops import _call, _p, _stream
 
 SUBSAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+ENTROPY = ("host", "device")
+CHUNK = 1024                        # the device coder's unstuffed scans start at multiples of it (csrc/jpeg_huff_enc.h kStuffChunk)
+BLOCK_BITS = 1664                   # no block codes to more: 26 bits per coefficient
 ERR_CAPACITY = _lib.const("VUNET_JPEG_ERR_CAPACITY")
+ERR_RANGE, ERR_ARG = _lib.const("VUNET_JPEG_ERR_RANGE"), _lib.const("VUNET_ERR_ARG")
 REASONS = {ERR_CAPACITY: "the stream is longer than its output buffer",
-           _lib.const("VUNET_JPEG_ERR_RANGE"): "a coefficient outside baseline's range (DC difference > 11 bits or AC > 10 bits)",
-           _lib.const("VUNET_ERR_ARG"): "an argument the library refuses"}
+           ERR_RANGE: "a coefficient outside baseline's range (DC difference > 11 bits or AC > 10 bits)",
+           ERR_ARG: "an argument the library refuses"}
 
 
 class JpegEncodeError(ValueError):
@@ -60,6 +71,7 @@ class _Buffers:
     def __init__(self, device: torch.device):
         self.device, self.stage, self.dev, self.planes, self.coef, self.coef_host, self.event, self.out = \
             device, None, None, None, None, None, None, None
+        self.entropy = None                                # the device coder's memory (``_Entropy``), made when first asked for
 
     def reserve(self, up_bytes: int, coef_count: int, out_bytes: int):
         pin = self.device.type == "cuda"
@@ -72,6 +84,51 @@ class _Buffers:
             self.coef_host = torch.empty(coef_count, dtype=torch.int16, pin_memory=pin)
         if self.out is None or self.out.size < out_bytes:
             self.out = np.empty(out_bytes, dtype=np.uint8)
+
+
+def _r4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+class _Entropy:
+    """The device coder's reused memory, grow-only like ``_Buffers``.  ``up`` / ``up_dev``: the pinned block of what goes up and
+    its device mirror -- tab_row int32 [N] | spans int64 [N][2] | codes uint32 [rows][4][256].  ``small`` / ``small_host``: uint32
+    totals [r4(N)] | status [r4(2 N)] | img_start [N + 1].  ``bits``: one word per block.  ``hist``: [N][4][256] with ``optimize``.
+    ``raw``: the unstuffed scans, ``chunks`` one word per 1024 bytes of them, ``out`` / ``out_host`` the stuffed scans."""
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self.up = self.up_dev = self.small = self.small_host = self.bits = self.hist = self.hist_host = None
+        self.raw = self.chunks = self.out = self.out_host = None
+
+    def _grow(self, name: str, count: int, dtype, host: bool = False):
+        cur = getattr(self, name)
+        if cur is None or cur.numel() < count:
+            kw = dict(pin_memory=self.device.type == "cuda") if host else dict(device=self.device)
+            setattr(self, name, torch.empty(count, dtype=dtype, **kw))
+
+    def layout(self, n: int, rows: int):
+        """-> (spans_off, codes_off, up_bytes) of ``up``; (status_at, start_at, words) of ``small``."""
+        spans_off = (4 * n + 15) // 16 * 16
+        codes_off = spans_off + 16 * n
+        return (spans_off, codes_off, codes_off + 4096 * rows), (_r4(n), _r4(n) + _r4(2 * n), _r4(n) + _r4(2 * n) + n + 1)
+
+    def reserve(self, n: int, rows: int, blocks: int, optimize: bool):
+        (_, _, up_bytes), (_, _, words) = self.layout(n, rows)
+        self._grow("up", up_bytes, torch.uint8, host=True)
+        self._grow("up_dev", up_bytes, torch.uint8)
+        self._grow("small", words, torch.int32)
+        self._grow("small_host", words, torch.int32, host=True)
+        self._grow("bits", blocks, torch.int32)
+        if optimize:
+            self._grow("hist", 1024 * n, torch.int32)
+            self._grow("hist_host", 1024 * n, torch.int32, host=True)
+
+    def reserve_streams(self, raw_bytes: int, out_cap: int):
+        self._grow("raw", raw_bytes, torch.uint8)
+        self._grow("chunks", raw_bytes // CHUNK, torch.int32)
+        self._grow("out", out_cap, torch.uint8)
+        self._grow("out_host", out_cap, torch.uint8, host=True)
 
 
 _buffers: Dict[tuple, _Buffers] = {}
@@ -89,20 +146,122 @@ def quant_tables(quality: int) -> np.ndarray:
     return q
 
 
-def _launch(buf: _Buffers, frames: torch.Tensor, m: int, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int) -> None:
-    """One upload of the descriptors and tables, the two launches and the download of the coefficients into the pinned buffer, on the
-    current stream, waited for.  The host copy of the descriptors is what the library checks before it launches."""
+def _transform(buf: _Buffers, frames: torch.Tensor, m: int, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int) -> None:
+    """One upload of the descriptors and tables and the two launches, on the current stream, not waited for.  The host copy of the
+    descriptors is what the library checks before it launches."""
     n, hmax, wmax = (int(v) for v in frames.shape[:3])
     buf.dev[:up_bytes].copy_(buf.stage[:up_bytes], non_blocking=True)
     base = buf.dev.data_ptr()
     imgs, qtab, host = ctypes.c_void_p(base), ctypes.c_void_p(base + q_off), ctypes.c_void_p(buf.stage.data_ptr())
     _call("vunet_jpeg_from_rgb", _p(frames), n, hmax, wmax, channels, imgs, host, m, _p(buf.planes), coef_count, _stream())
     _call("vunet_jpeg_fdct", _p(buf.planes), coef_count, qtab, q_count, imgs, host, m, _p(buf.coef), coef_count, _stream())
-    buf.coef_host[:coef_count].copy_(buf.coef[:coef_count], non_blocking=True)
+
+
+def _wait(buf: _Buffers) -> None:
     if buf.event is None:
         buf.event = torch.cuda.Event()
     buf.event.record()
     buf.event.synchronize()
+
+
+def _launch(buf: _Buffers, frames: torch.Tensor, m: int, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int) -> None:
+    """The host route's device step: ``_transform`` and the download of the coefficients into the pinned buffer, waited for."""
+    _transform(buf, frames, m, channels, up_bytes, q_off, q_count, coef_count)
+    buf.coef_host[:coef_count].copy_(buf.coef[:coef_count], non_blocking=True)
+    _wait(buf)
+
+
+def _optimal_tables(lib, hist: np.ndarray, ntab: int):
+    """``hist`` uint32 [4, 256] -> (rc, counts uint8 [4, 16], symbols uint8 [4, 256]): the first ``ntab`` tables built, the rest empty."""
+    counts, symbols, nsym = np.zeros((4, 16), dtype=np.uint8), np.zeros((4, 256), dtype=np.uint8), ctypes.c_int32(0)
+    for t in range(ntab):
+        rc = lib.vunet_jpeg_optimal_table(hist[t].ctypes.data, counts[t].ctypes.data, symbols[t].ctypes.data, ctypes.byref(nsym))
+        if rc != 0:
+            return rc, counts, symbols
+    return 0, counts, symbols
+
+
+def _encode_on_device(buf: _Buffers, frames: torch.Tensor, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int,
+                      infos: list, qptrs: list, optimize: bool) -> List[bytes]:
+    """The device route behind ``_transform``: [histograms, a wait, tables up;] lengths and their prefix sums, a wait for the bit
+    totals, the spans up, pack and stuff, one wait for the scans' lengths and bytes.  The host writes header and EOI around them."""
+    n, lib, stream = len(infos), _lib.lib(), _stream()
+    if any(i.nblocks * BLOCK_BITS >= 1 << 32 for i in infos):
+        j = next(j for j, i in enumerate(infos) if i.nblocks * BLOCK_BITS >= 1 << 32)
+        raise ValueError(f"frame {j}: {infos[j].nblocks} blocks may code to more bits than the device coder's 32-bit offsets count; "
+                         f"use entropy=\"host\"")
+    ent = buf.entropy
+    if ent is None:
+        ent = buf.entropy = _Entropy(buf.device)
+    rows, blocks, ntab = (n if optimize else 1), sum(i.nblocks for i in infos), (4 if channels == 3 else 2)
+    ent.reserve(n, rows, blocks, optimize)
+    (spans_off, codes_off, tab_bytes), (status_at, start_at, small_words) = ent.layout(n, rows)
+    _transform(buf, frames, n, channels, up_bytes, q_off, q_count, coef_count)
+    up = ent.up.numpy()
+    tab_row, spans = up[:4 * n].view(np.int32), up[spans_off:spans_off + 16 * n].view(np.int64).reshape(n, 2)
+    hbase, dbase = ent.up.data_ptr(), ent.up_dev.data_ptr()
+    imgs, imgs_host, coef = ctypes.c_void_p(buf.dev.data_ptr()), ctypes.c_void_p(buf.stage.data_ptr()), _p(buf.coef)
+    counts = symbols = None
+    if optimize:
+        _call("vunet_jpeg_huff_count", coef, coef_count, imgs, imgs_host, n, _p(ent.hist), 1024 * n, stream)
+        ent.hist_host[:1024 * n].copy_(ent.hist[:1024 * n], non_blocking=True)
+        _wait(buf)
+        hist = ent.hist_host.numpy()[:1024 * n].view(np.uint32).reshape(n, 4, 256)
+        counts, symbols = np.empty((n, 4, 16), dtype=np.uint8), np.empty((n, 4, 256), dtype=np.uint8)
+        failed = ctypes.c_int32(-1)
+        rc = lib.vunet_jpeg_optimal_tables(hist.ctypes.data, n, ntab, counts.ctypes.data, symbols.ctypes.data, hbase + codes_off,
+                                           ctypes.byref(failed))
+        if rc != 0:
+            raise JpegEncodeError(rc, failed.value)
+        tab_row[:] = np.arange(n)
+    else:
+        _call("vunet_jpeg_code_words", None, None, hbase + codes_off)
+        tab_row[:] = 0
+    spans[:] = 0
+    ent.up_dev[:tab_bytes].copy_(ent.up[:tab_bytes], non_blocking=True)
+    codes, rows_dev, rows_host = ctypes.c_void_p(dbase + codes_off), ctypes.c_void_p(dbase), ctypes.c_void_p(hbase)
+    _call("vunet_jpeg_huff_lengths", coef, coef_count, imgs, imgs_host, n, codes, rows, rows_dev, rows_host, _p(ent.bits), blocks,
+          _p(ent.small), start_at, stream)
+    ent.small_host[:start_at].copy_(ent.small[:start_at], non_blocking=True)
+    _wait(buf)
+    small = ent.small_host.numpy().view(np.uint32)
+    status = small[status_at:status_at + 2 * n].reshape(n, 2)
+    if status.any():                                        # the lowest failing index
+        j = int(np.flatnonzero(status.any(axis=1))[0])
+        raise JpegEncodeError(ERR_RANGE if status[j, 0] else ERR_ARG, j)
+    nbytes = (small[:n].astype(np.int64) + 7) // 8
+    padded = (nbytes + CHUNK - 1) // CHUNK * CHUNK
+    spans[:, 0], spans[:, 1] = np.cumsum(padded) - padded, small[:n]
+    raw_bytes, out_cap, unstuffed = int(padded.sum()), int(2 * nbytes.sum()), int(nbytes.sum())
+    if out_cap >= 1 << 32:
+        raise ValueError(f"encode_batch: the batch's scans ({unstuffed} bytes before stuffing) pass the device coder's 32-bit offsets; "
+                         f"use smaller batches or entropy=\"host\"")
+    ent.reserve_streams(raw_bytes, out_cap)
+    ent.up_dev[spans_off:codes_off].copy_(ent.up[spans_off:codes_off], non_blocking=True)
+    spans_dev, spans_host = ctypes.c_void_p(dbase + spans_off), ctypes.c_void_p(hbase + spans_off)
+    _call("vunet_jpeg_huff_pack", coef, coef_count, imgs, imgs_host, n, codes, rows, rows_dev, rows_host, _p(ent.bits), blocks,
+          spans_dev, spans_host, _p(ent.raw), raw_bytes, stream)
+    _call("vunet_jpeg_huff_stuff", _p(ent.raw), raw_bytes, imgs_host, spans_dev, spans_host, n, _p(ent.chunks), raw_bytes // CHUNK,
+          _p(ent.out), out_cap, ctypes.c_void_p(ent.small.data_ptr() + 4 * start_at), stream)
+    # stuffing adds a byte per 0xFF, 1 in 256 of random bits: a sixteenth more than the unstuffed bytes comes down with the lengths,
+    # and the rest of a batch that needs more (saturated coefficients) in a second copy
+    first = min(out_cap, unstuffed + unstuffed // 16 + 4096)
+    ent.small_host[start_at:small_words].copy_(ent.small[start_at:small_words], non_blocking=True)
+    ent.out_host[:first].copy_(ent.out[:first], non_blocking=True)
+    _wait(buf)
+    starts = ent.small_host.numpy().view(np.uint32)[start_at:small_words].astype(np.int64)
+    if starts[n] > first:
+        ent.out_host[first:int(starts[n])].copy_(ent.out[first:int(starts[n])], non_blocking=True)
+        _wait(buf)
+    scans, header, length, res = ent.out_host.numpy(), np.empty(1024, dtype=np.uint8), ctypes.c_int64(0), []
+    for j in range(n):
+        c, s = (counts[j].ctypes.data, symbols[j].ctypes.data) if optimize else (None, None)
+        rc = lib.vunet_jpeg_write_header(ctypes.byref(infos[j]), ctypes.c_void_p(qptrs[j]), c, s, header.ctypes.data, header.size,
+                                         ctypes.byref(length))
+        if rc != 0:
+            raise JpegEncodeError(rc, j)
+        res.append(header[:length.value].tobytes() + scans[starts[j]:starts[j + 1]].tobytes() + b"\xff\xd9")
+    return res
 
 
 def _sizes(sizes, n: int, h: int, w: int) -> List[tuple]:
@@ -121,14 +280,19 @@ def _per_image(value, n: int, what: str) -> list:
     return values
 
 
-def encode_batch(frames: torch.Tensor, quality=75, subsampling="4:2:0", sizes=None, threads: int = 8) -> List[bytes]:
+def encode_batch(frames: torch.Tensor, quality=75, subsampling="4:2:0", sizes=None, threads: int = 8, entropy: str = "host",
+                 optimize: bool = False) -> List[bytes]:
     """``frames`` uint8 [N, H, W, 3] (RGB interleaved) or [N, H, W] (gray) on the current GPU -> N baseline JPEG streams, image n
     byte for byte ``Image.fromarray(frames[n, :h, :w]).save(.., "JPEG", quality=quality, subsampling=subsampling)``.
 
     ``quality``: libjpeg's 1 .. 100.  ``subsampling``: "4:4:4", "4:2:2" or "4:2:0" (ignored for gray).  Either may be a list with one
     value per image: the two launches take mixed samplings and tables as they take mixed sizes.  ``sizes``: per-image
     ``(h, w)`` inside the padded stack, as ``decode_batch`` returns them (default: every image fills it).  ``threads``: host threads
-    of the entropy coder, at most 16.
+    of the entropy coder, at most 16.  ``entropy``: "host" or "device", where the Huffman coder runs; the bytes are the same, and
+    with "device" ``threads`` has no effect and only the scans' bytes are downloaded (two host waits; an image of more blocks than
+    32-bit bit offsets cover, about 2.5 million, is refused with a ``ValueError``).  ``optimize``: Pillow's ``optimize=True`` --
+    per-image Huffman tables from the image's own symbol counts, written into the stream's DHT segments; smaller streams for a second
+    pass over the coefficients (host) or a histogram launch and one more round trip (device).
 
     One small upload, two launches, one download of the coefficients into a reused pinned buffer on the current stream, a wait for
     it, then the entropy coder on the host.  After the first call at a shape nothing is allocated on the device.  Not recordable
@@ -142,7 +306,9 @@ def encode_batch(frames: torch.Tensor, quality=75, subsampling="4:2:0", sizes=No
         raise ValueError(f"subsampling: one of {sorted(SUBSAMPLING)} expected, got {sorted(set(subsampling))}")
     if any(not isinstance(q, (int, np.integer)) or not 1 <= q <= 100 for q in quality):
         raise ValueError(f"quality: integers 1 .. 100 expected, got {sorted(set(quality), key=str)}")
-    threads = int(threads)
+    if entropy not in ENTROPY:
+        raise ValueError(f"entropy: one of {ENTROPY} expected, got {entropy!r}")
+    threads, optimize = int(threads), bool(optimize)
     if not 1 <= threads <= MAX_THREADS:
         raise ValueError(f"encode_batch: 1 <= threads <= {MAX_THREADS} expected, got {threads}")
     if not (1 <= n <= MAX_SIDE and 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
@@ -181,12 +347,35 @@ def encode_batch(frames: torch.Tensor, quality=75, subsampling="4:2:0", sizes=No
         r.height, r.width, r.ncomp, r.hsamp, r.vsamp = inf.height, inf.width, inf.ncomp, inf.hsamp, inf.vsamp
         r.bw0, r.bh0, r.bw1, r.bh1 = inf.bw0, inf.bh0, inf.bw1, inf.bh1
         coef_at, block_at = coef_at + inf.ncoef, block_at + inf.nblocks
+    if entropy == "device":
+        qptrs = [tables.ctypes.data + 2 * table_of[int(q)] for q in quality]
+        return _encode_on_device(buf, frames, channels, up_bytes, q_off, tables.size, coef_count, infos, qptrs, optimize)
     _launch(buf, frames, n, channels, up_bytes, q_off, tables.size, coef_count)
     fn, cbase, obase, qbase = lib.vunet_jpeg_entropy_encode, buf.coef_host.data_ptr(), buf.out.ctypes.data, tables.ctypes.data
     offs = np.concatenate([[0], np.cumsum(caps)]).tolist()
     coffs = np.concatenate([[0], np.cumsum([i.ncoef for i in infos])]).tolist()
 
+    def one_optimized(j):                                 # two passes over the pinned coefficients: count, then code
+        length, qptr, cptr = ctypes.c_int64(0), qbase + 2 * table_of[int(quality[j])], ctypes.c_void_p(cbase + 2 * coffs[j])
+        hist = np.empty((4, 256), dtype=np.uint32)
+        rc = lib.vunet_jpeg_symbol_histogram(cptr, ctypes.byref(infos[j]), hist.ctypes.data)
+        if rc == 0:
+            rc, counts, symbols = _optimal_tables(lib, hist, 4 if channels == 3 else 2)
+        if rc != 0:
+            return rc, b""
+        fn, out, cap = lib.vunet_jpeg_entropy_encode_tables, obase + offs[j], caps[j]
+        rc = fn(cptr, ctypes.byref(infos[j]), ctypes.c_void_p(qptr), counts.ctypes.data, symbols.ctypes.data, ctypes.c_void_p(out), cap,
+                ctypes.byref(length))
+        if rc == ERR_CAPACITY:
+            own = np.empty(length.value, dtype=np.uint8)
+            rc = fn(cptr, ctypes.byref(infos[j]), ctypes.c_void_p(qptr), counts.ctypes.data, symbols.ctypes.data, own.ctypes.data, own.size,
+                    ctypes.byref(length))
+            return rc, own.tobytes()
+        return rc, buf.out[offs[j]:offs[j] + length.value].tobytes()
+
     def one(j):
+        if optimize:
+            return one_optimized(j)
         length, qptr = ctypes.c_int64(0), qbase + 2 * table_of[int(quality[j])]
         rc = fn(ctypes.c_void_p(cbase + 2 * coffs[j]), ctypes.byref(infos[j]), ctypes.c_void_p(qptr), ctypes.c_void_p(obase + offs[j]),
                 caps[j], ctypes.byref(length))
@@ -215,10 +404,10 @@ def _paths(pattern: str, count: int, start: int = 0) -> List[str]:
 
 
 def save_images(pattern: str, frames: torch.Tensor, quality: int = 75, subsampling: str = "4:2:0", sizes=None, start: int = 0,
-                threads: int = 8) -> List[str]:
+                threads: int = 8, entropy: str = "host", optimize: bool = False) -> List[str]:
     """``encode_batch`` and one file per frame: ``pattern % index`` (``"img_%06d.jpg"``, the reference's frame names) or
     ``pattern.format(index)``, indices from ``start``.  -> the paths written."""
-    streams = encode_batch(frames, quality, subsampling, sizes, threads)
+    streams = encode_batch(frames, quality, subsampling, sizes, threads, entropy, optimize)
     paths = _paths(pattern, len(streams), start)
     for path, data in zip(paths, streams):
         with open(path, "wb") as f:

@@ -65,18 +65,20 @@ def write_mjpeg_streams(path: str, streams: Sequence[bytes], width: int, height:
     return path
 
 
-def write_mjpeg(path: str, frames: torch.Tensor, fps=12, quality: int = 75, subsampling: str = "4:2:0", threads: int = 8) -> str:
+def write_mjpeg(path: str, frames: torch.Tensor, fps=12, quality: int = 75, subsampling: str = "4:2:0", threads: int = 8,
+                entropy: str = "host", optimize: bool = False) -> str:
     """``frames`` uint8 [T, H, W, 3] on the GPU -> the Motion-JPEG AVI ``path``: ``jpeg_encode.encode_batch`` once for the whole clip,
-    then ``write_mjpeg_streams``.  The default of 12 frames per second is the reference's."""
+    then ``write_mjpeg_streams``.  The default of 12 frames per second is the reference's.  ``entropy`` and ``optimize`` are
+    ``encode_batch``'s: every frame carries its own Huffman tables, so a file of optimised frames needs nothing else."""
     from . import jpeg_encode
     if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[3] != 3:
         raise ValueError(f"write_mjpeg: frames uint8 [T, H, W, 3] expected, got {tuple(getattr(frames, 'shape', ()))}")
-    streams = jpeg_encode.encode_batch(frames, quality, subsampling, threads=threads)
+    streams = jpeg_encode.encode_batch(frames, quality, subsampling, threads=threads, entropy=entropy, optimize=optimize)
     return write_mjpeg_streams(path, streams, int(frames.shape[2]), int(frames.shape[1]), fps)
 
 
 def save_videos(pattern: str, frames: torch.Tensor, fps=12, quality: int = 75, subsampling: str = "4:2:0", start: int = 0,
-                threads: int = 8) -> List[str]:
+                threads: int = 8, entropy: str = "host", optimize: bool = False) -> List[str]:
     """``frames`` uint8 [B, T, H, W, 3] on the GPU (what ``render.*_video`` return) -> one file per row, ``pattern % index`` or
     ``pattern.format(index)`` from ``start``; all B * T frames are encoded in ONE batch.  -> the paths written."""
     from . import jpeg_encode
@@ -84,7 +86,8 @@ def save_videos(pattern: str, frames: torch.Tensor, fps=12, quality: int = 75, s
         raise ValueError(f"save_videos: frames uint8 [B, T, H, W, 3] expected, got {tuple(getattr(frames, 'shape', ()))}")
     b, t, h, w = (int(v) for v in frames.shape[:4])
     paths = jpeg_encode._paths(pattern, b, start)
-    streams = jpeg_encode.encode_batch(frames.reshape(b * t, h, w, 3), quality, subsampling, threads=threads)
+    streams = jpeg_encode.encode_batch(frames.reshape(b * t, h, w, 3), quality, subsampling, threads=threads, entropy=entropy,
+                                       optimize=optimize)
     for i, path in enumerate(paths):
         write_mjpeg_streams(path, streams[i * t:(i + 1) * t], w, h, fps)
     return paths

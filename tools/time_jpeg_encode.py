@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the JPEG encode (csrc/jpeg_enc.hip, csrc/jpeg_huff_enc.h) at two batch shapes, 50 frames of 256 x 256 and 16 frames of
+"""Time the JPEG encode (csrc/jpeg_enc.hip, csrc/jpeg_huff.hip, csrc/jpeg_huff_enc.h) at two batch shapes, 50 frames of 256 x 256 and 16 frames of
 1000 x 1002 (W x H), 4:2:0, quality 75 and 95, synthetic smooth content with a little noise:
 
   * each of the two launches, device events, with the bytes it moves and TB/s,
@@ -7,7 +7,13 @@
   * the host entropy coder of the batch (``vunet_jpeg_entropy_encode`` from the pinned coefficients) on 1, 4 and 8 threads, wall clock,
   * ``encode_batch`` as a whole (8 threads, wall clock to its end -- it ends synchronised: the bytes are on the host),
   * the same frames through a download of the pixels plus Pillow's ``Image.save`` on ONE host thread -- what a user of the package
-    pays without it.
+    pays without it,
+  * the device entropy coder (``entropy="device"``): each of its entry points, device events -- vunet_jpeg_huff_count (zero +
+    histogram), vunet_jpeg_huff_lengths (zero + lengths + prefix sum), vunet_jpeg_huff_pack (zero + pack), vunet_jpeg_huff_stuff
+    (count + prefix sum + write) -- and the bytes its final download carries against the coefficients' download,
+  * ``encode_batch`` as a whole on the four routes host / device x plain / ``optimize=True``, wall clock, alternating call by call in
+    one process; the optimised bytes are checked against Pillow's ``optimize=True`` first,
+  * the batch's stream bytes, plain against optimised.
 
 Device events around windows of many calls after a warm-up; the routes of a group alternate in the same process, ``--rounds``
 windows each, and the median and the spread (min .. max) are printed.  The encoded bytes are checked against Pillow's before anything
@@ -68,6 +74,21 @@ def wall(fn, rounds):
     return statistics.median(times), min(times), max(times)
 
 
+def wall_alternating(named, rounds):
+    """``wall`` for several routes whose calls alternate: {name: (median, min, max)} in ms."""
+    for _, fn in named:
+        fn()
+    times = {n: [] for n, _ in named}
+    for _ in range(rounds):
+        for n, fn in named:
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[n].append((time.perf_counter() - t) * 1e3)
+    return {n: (statistics.median(v), min(v), max(v)) for n, v in times.items()}
+
+
 def frames(n, h, w, seed):
     g = np.random.default_rng(seed)
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
@@ -101,9 +122,9 @@ def main():
         lines.append(f"{title:<30} {name:<62} {med:10.3f} {unit}  ({lo:.3f} .. {hi:.3f}){extra}")
         print(lines[-1], flush=True)
 
-    def pillow_bytes(f, q):
+    def pillow_bytes(f, q, optimize=False):
         buf = io.BytesIO()
-        Image.fromarray(f, "RGB").save(buf, "JPEG", quality=q, subsampling=2)
+        Image.fromarray(f, "RGB").save(buf, "JPEG", quality=q, subsampling=2, optimize=optimize)
         return buf.getvalue()
 
     for n, h, w in SHAPES:
@@ -155,6 +176,46 @@ def main():
             def pillow():
                 return [pillow_bytes(f, q) for f in dev.cpu().numpy()]
             row("host, one thread", f"quality {q}: download of the pixels + Pillow Image.save", wall(pillow, a.rounds), "ms")
+            # ---- the device entropy coder: the bytes first, then its entry points on what the last call left in the buffers
+            optimised = [pillow_bytes(f, q, True) for f in raw]
+            for entropy in ("host", "device"):
+                assert J.encode_batch(dev, quality=q, subsampling="4:2:0", entropy=entropy, optimize=True) == optimised, \
+                    f"quality {q}, {entropy}: the optimised bytes differ from Pillow's"
+            assert J.encode_batch(dev, quality=q, subsampling="4:2:0", entropy="device") == streams
+            plain_bytes, opt_bytes = sum(len(s) for s in streams), sum(len(s) for s in optimised)
+            lines.append(f"# quality {q}: the batch's streams: {plain_bytes} bytes plain, {opt_bytes} bytes with optimize=True "
+                         f"({100 * (1 - opt_bytes / plain_bytes):.1f} % smaller); both routes == Pillow's optimize=True, byte for byte")
+            print(lines[-1], flush=True)
+            ent, blocks = bufs.entropy, n * info.nblocks
+            (spans_off, codes_off, _), (_, start_at, _) = ent.layout(n, 1)          # the plain call above left one row of codes
+            hb, db = ent.up.data_ptr(), ent.up_dev.data_ptr()
+            spans = ent.up.numpy()[spans_off:spans_off + 16 * n].view(np.int64).reshape(n, 2)
+            unstuffed = int(((spans[:, 1] + 7) // 8).sum())
+            raw_bytes, out_cap = int(spans[-1, 0] + ((spans[-1, 1] + 7) // 8 + J.CHUNK - 1) // J.CHUNK * J.CHUNK), 2 * unstuffed
+            coef = (_p(bufs.coef), count, imgs, host, n)
+            tabs = (ctypes.c_void_p(db + codes_off), 1, ctypes.c_void_p(db), ctypes.c_void_p(hb))
+            sp = (ctypes.c_void_p(db + spans_off), ctypes.c_void_p(hb + spans_off))
+            res = compare([("count", lambda: _call("vunet_jpeg_huff_count", *coef, _p(ent.hist), 1024 * n, _stream())),
+                           ("lengths", lambda: _call("vunet_jpeg_huff_lengths", *coef, *tabs, _p(ent.bits), blocks, _p(ent.small), start_at, _stream())),
+                           ("pack", lambda: _call("vunet_jpeg_huff_pack", *coef, *tabs, _p(ent.bits), blocks, *sp, _p(ent.raw), raw_bytes, _stream())),
+                           ("stuff", lambda: _call("vunet_jpeg_huff_stuff", _p(ent.raw), raw_bytes, host, *sp, n, _p(ent.chunks), raw_bytes // J.CHUNK,
+                                                   _p(ent.out), out_cap, ctypes.c_void_p(ent.small.data_ptr() + 4 * start_at), _stream()))],
+                          a.calls, a.rounds)
+            names = {"count": "vunet_jpeg_huff_count (zero, histogram)", "lengths": "vunet_jpeg_huff_lengths (zero, lengths, prefix sum)",
+                     "pack": "vunet_jpeg_huff_pack (zero, pack)", "stuff": "vunet_jpeg_huff_stuff (count, prefix sum, write)"}
+            for k, r in res.items():
+                row("launches", f"quality {q}: {names[k]}", r, "us")
+            torch.cuda.synchronize()
+            assert J.encode_batch(dev, quality=q, subsampling="4:2:0", entropy="device") == streams       # (the buffers are as a call leaves them)
+            down = min(out_cap, unstuffed + unstuffed // 16 + 4096) + 4 * (n + 1)
+            lines.append(f"# quality {q}: the device route's final download: {down} bytes ({down / 1e6:.2f} MB; the scans are "
+                         f"{sum(len(t) - t.index(bytes([0xFF, 0xDA])) - 16 for t in streams)} of them) against {2 * count} bytes of coefficients ({2 * count / 1e6:.1f} MB) on the host route")
+            print(lines[-1], flush=True)
+            routes = [(f"{entropy}{', optimize' if opt else ''}", (lambda e=entropy, o=opt: J.encode_batch(dev, quality=q, subsampling="4:2:0",
+                                                                                                        entropy=e, optimize=o)))
+                      for entropy in ("host", "device") for opt in (False, True)]
+            for k, r in wall_alternating(routes, a.rounds).items():
+                row("encode_batch, alternating", f"quality {q}: entropy={k} (8 threads on the host route)", r, "ms")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
