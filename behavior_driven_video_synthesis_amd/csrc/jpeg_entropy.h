@@ -13,6 +13,8 @@
 
 #include "../../include/vunet_hip.h"
 #include "../../include/vunet_jpeg.h"
+#include "../../include/vunet_jpeg_huffdec.h"
+#include "jpeg_sync.h"
 
 namespace vunet_jpeg {
 
@@ -363,6 +365,187 @@ inline int entropy_decode(const uint8_t* d, int64_t len, const vunet_jpeg_info* 
   if (d[p] == 0xD9) return VUNET_OK;
   if (d[p] == 0xDA || d[p] == 0xC4 || d[p] == 0xDB) return VUNET_JPEG_ERR_SCANS;
   return VUNET_JPEG_ERR_MARKER;
+}
+
+// ---- the host side of the device entropy decoder (jpeg_huff_dec.hip): no bit walk, a byte-level marker scan
+
+// the stream's decoding tables as one device row; false where more than two DC or two AC tables are in use.  The row is a valid
+// one either way (the MCU's shape is the image's, every table index is in range): such a stream brings no subsequences, but its
+// row travels with the batch's and is checked with them
+inline bool flatten_tables(const Header& H, vunet_jpeg_sync::Tables& T) {
+  memset(&T, 0, sizeof(T));
+  const vunet_jpeg_info& I = H.info;
+  T.hv = I.ncomp == 3 ? I.hsamp * I.vsamp : 1;
+  T.per_mcu = I.ncomp == 3 ? T.hv + 2 : 1;
+  T.restart = I.restart;
+  int ids[2][2] = {{-1, -1}, {-1, -1}};
+  for (int c = 0; c < I.ncomp; ++c)
+    for (int kind = 0; kind < 2; ++kind) {
+      const int id = kind ? H.ta[c] : H.td[c];
+      int slot = ids[kind][0] == id ? 0 : (ids[kind][1] == id ? 1 : -1);
+      if (slot < 0) {
+        slot = ids[kind][0] < 0 ? 0 : (ids[kind][1] < 0 ? 1 : -1);
+        if (slot < 0) return false;
+        ids[kind][slot] = id;
+        const Huff& h = H.huff[kind][id];
+        vunet_jpeg_sync::Table& t = T.t[2 * kind + slot];
+        memcpy(t.look, h.look, sizeof(t.look));
+        memcpy(t.maxcode, h.maxcode, sizeof(t.maxcode));
+        memcpy(t.symbols, h.symbols, sizeof(t.symbols));
+        for (int len = 1; len <= 16; ++len) t.valoff[len] = h.valoff[len];
+      }
+      (kind ? T.ac : T.dc)[c] = 2 * kind + slot;
+    }
+  return true;
+}
+
+inline int64_t expected_segments(const vunet_jpeg_info& I) {
+  const int64_t mcus = (int64_t)I.mcu_cols * I.mcu_rows;
+  return I.restart > 0 ? (mcus + I.restart - 1) / I.restart : 1;
+}
+
+inline int scan_segments(const uint8_t* d, int64_t len, const vunet_jpeg_info* info, int64_t* segs, int64_t seg_cap, int64_t* nseg,
+                         uint16_t* qtab, uint8_t* tab) {
+  if (!d || !info || !segs || !nseg || !qtab || !tab || len < 0) return VUNET_ERR_ARG;
+  Header* Hp = new Header();
+  struct Free {
+    Header* h;
+    ~Free() { delete h; }
+  } guard{Hp};
+  Header& H = *Hp;
+  const int rc = parse(d, len, H);
+  if (rc != VUNET_OK) return rc;
+  const vunet_jpeg_info& I = H.info;
+  if (!same_info(I, *info)) return VUNET_ERR_ARG;
+  const int64_t expected = expected_segments(I);
+  if (seg_cap < expected) return VUNET_ERR_ARG;
+  *nseg = 0;
+  for (int c = 0; c < I.ncomp; ++c) memcpy(qtab + 64 * c, H.qt[H.tq[c]], 64 * sizeof(uint16_t));
+  vunet_jpeg_sync::Tables* T = new vunet_jpeg_sync::Tables();
+  const bool flat = flatten_tables(H, *T);
+  memcpy(tab, T, sizeof(*T));
+  delete T;
+  if (!flat) return VUNET_JPEG_HUFFDEC_IRREGULAR;
+  int64_t p = H.scan, begin = H.scan, count = 0;
+  for (;;) {
+    const uint8_t* q = p < len ? (const uint8_t*)memchr(d + p, 0xFF, (size_t)(len - p)) : nullptr;
+    if (!q) return VUNET_JPEG_HUFFDEC_IRREGULAR;              // no EOI
+    p = q - d;
+    if (p + 1 >= len) return VUNET_JPEG_HUFFDEC_IRREGULAR;    // an FF at the end of the data
+    const int m = d[p + 1];
+    if (m == 0) {
+      p += 2;
+      continue;
+    }
+    const bool rst = m >= 0xD0 && m <= 0xD7;
+    if (!rst && m != 0xD9) return VUNET_JPEG_HUFFDEC_IRREGULAR;   // fill bytes, any other marker
+    if (p == begin || count >= expected) return VUNET_JPEG_HUFFDEC_IRREGULAR;
+    if (rst && (I.restart == 0 || m != 0xD0 + (int)(count & 7))) return VUNET_JPEG_HUFFDEC_IRREGULAR;
+    segs[3 * count] = begin;
+    segs[3 * count + 1] = p;
+    segs[3 * count + 2] = count * (int64_t)I.restart;
+    ++count;
+    if (!rst) break;
+    begin = p = p + 2;
+  }
+  if (count != expected) return VUNET_JPEG_HUFFDEC_IRREGULAR;
+  *nseg = count;
+  return VUNET_OK;
+}
+
+inline int subseq_rows(const int64_t* segs, int64_t nseg, const vunet_jpeg_info* info, int32_t img, int64_t byte_off, int64_t row0,
+                       vunet_jpeg_subseq* rows, int64_t row_cap, int64_t* nrows, int64_t subseq_bytes = VUNET_JPEG_SUBSEQ_BYTES) {
+  if (!segs || !info || !rows || !nrows || nseg < 1 || img < 0 || row0 < 0 || row0 % VUNET_JPEG_HUFFDEC_GROUP || subseq_bytes < 8)
+    return VUNET_ERR_ARG;
+  const vunet_jpeg_info& I = *info;
+  const int64_t per_mcu = I.ncomp == 3 ? I.hsamp * I.vsamp + 2 : 1, mcus = (int64_t)I.mcu_cols * I.mcu_rows;
+  int64_t at = 0;
+  for (int64_t s = 0; s < nseg; ++s) {
+    const int64_t b = segs[3 * s] + byte_off, e = segs[3 * s + 1] + byte_off, mcu0 = segs[3 * s + 2];
+    if (b < 0 || e <= b || e > VUNET_JPEG_HUFFDEC_MAX_BYTES || mcu0 < 0 || mcu0 >= mcus) return VUNET_ERR_ARG;
+    const int64_t in_seg = I.restart > 0 && mcus - mcu0 > I.restart ? I.restart : mcus - mcu0;
+    const int64_t n = (e - b + subseq_bytes - 1) / subseq_bytes;
+    if (at + n > row_cap || row0 + at + n > 0x7FFFFFFF) return VUNET_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+      vunet_jpeg_subseq& r = rows[at + i];
+      r.img = img;
+      r.seg_begin = (int32_t)b;
+      r.seg_end = (int32_t)e;
+      r.begin = (int32_t)(b + i * subseq_bytes);
+      r.end = (int32_t)(i + 1 == n ? e : b + (i + 1) * subseq_bytes);
+      r.first_block = (int32_t)(mcu0 * per_mcu);
+      r.seg_blocks = (int32_t)(in_seg * per_mcu);
+      r.seg_row = (int32_t)(row0 + at);
+      r.flags = (i == 0 ? VUNET_JPEG_SUBSEQ_FIRST : 0) | (i + 1 == n ? VUNET_JPEG_SUBSEQ_LAST : 0) |
+                (s + 1 == nseg ? VUNET_JPEG_SUBSEQ_TAIL : 0);
+      r.reserved = 0;
+    }
+    at += n;
+  }
+  const int64_t padded = (at + VUNET_JPEG_HUFFDEC_GROUP - 1) / VUNET_JPEG_HUFFDEC_GROUP * VUNET_JPEG_HUFFDEC_GROUP;
+  if (padded > row_cap) return VUNET_ERR_ARG;
+  for (; at < padded; ++at) {
+    memset(&rows[at], 0, sizeof(rows[at]));
+    rows[at].img = img;
+    rows[at].flags = VUNET_JPEG_SUBSEQ_PAD;
+  }
+  *nrows = padded;
+  return VUNET_OK;
+}
+
+// every row of the host copy against the buffers and against its neighbours: nothing is launched on rows that could make a
+// kernel read outside `bytes`, take another image's tables or index outside `state`
+inline bool subseq_rows_ok(const vunet_jpeg_subseq* h, int64_t nsub, int64_t bytes_count, const vunet_jpeg_img* imgs, int N,
+                           int64_t subseq_bytes = VUNET_JPEG_SUBSEQ_BYTES) {
+  if (nsub < VUNET_JPEG_HUFFDEC_GROUP || nsub % VUNET_JPEG_HUFFDEC_GROUP || nsub > 0x7FFFFFFF / 16) return false;
+  if (bytes_count < 0 || bytes_count > VUNET_JPEG_HUFFDEC_MAX_BYTES) return false;
+  for (int64_t i = 0; i < nsub; ++i) {
+    const vunet_jpeg_subseq& r = h[i];
+    const vunet_jpeg_subseq& lead = h[i - i % VUNET_JPEG_HUFFDEC_GROUP];
+    if (r.img < 0 || r.img >= N || r.img != lead.img) return false;
+    if (r.flags & VUNET_JPEG_SUBSEQ_PAD) {
+      if (i % VUNET_JPEG_HUFFDEC_GROUP == 0) return false;   // (a workgroup's first row names its image: never padding)
+      continue;
+    }
+    if (r.flags & ~7) return false;
+    const vunet_jpeg_img& m = imgs[r.img];
+    const int64_t nb = (int64_t)m.bw0 * m.bh0 + 2 * (int64_t)m.bw1 * m.bh1;
+    if (r.seg_begin < 0 || r.begin < r.seg_begin || r.end <= r.begin || r.seg_end < r.end || r.seg_end > bytes_count ||
+        r.end - r.begin > subseq_bytes)
+      return false;
+    if (r.first_block < 0 || r.seg_blocks < 1 || (int64_t)r.first_block + r.seg_blocks > nb) return false;
+    const bool first = r.flags & VUNET_JPEG_SUBSEQ_FIRST, last = r.flags & VUNET_JPEG_SUBSEQ_LAST;
+    if (first != (r.begin == r.seg_begin) || last != (r.end == r.seg_end)) return false;
+    if (first) {
+      if (r.seg_row != i) return false;
+    } else {
+      if (i == 0) return false;
+      const vunet_jpeg_subseq& p = h[i - 1];
+      if ((p.flags & (VUNET_JPEG_SUBSEQ_PAD | VUNET_JPEG_SUBSEQ_LAST)) || p.img != r.img || p.seg_begin != r.seg_begin ||
+          p.seg_end != r.seg_end || p.end != r.begin || p.seg_row != r.seg_row || p.first_block != r.first_block ||
+          p.seg_blocks != r.seg_blocks || (p.flags & VUNET_JPEG_SUBSEQ_TAIL) != (r.flags & VUNET_JPEG_SUBSEQ_TAIL))
+        return false;
+    }
+    if (!last) {
+      if (i + 1 >= nsub || (h[i + 1].flags & (VUNET_JPEG_SUBSEQ_PAD | VUNET_JPEG_SUBSEQ_FIRST))) return false;
+    }
+  }
+  return true;
+}
+
+// the host copy of the table rows against the images they belong to: every index a kernel takes from a row is in range
+inline bool table_rows_ok(const uint8_t* tabs, const vunet_jpeg_img* imgs, int N) {
+  for (int n = 0; n < N; ++n) {
+    vunet_jpeg_sync::Tables* T = new vunet_jpeg_sync::Tables();
+    memcpy(T, tabs + (size_t)n * sizeof(*T), sizeof(*T));
+    const vunet_jpeg_img& m = imgs[n];
+    const int hv = m.ncomp == 3 ? m.hsamp * m.vsamp : 1;
+    bool ok = T->hv == hv && T->per_mcu == (m.ncomp == 3 ? hv + 2 : 1) && T->restart >= 0;
+    for (int c = 0; c < 3; ++c) ok = ok && T->dc[c] >= 0 && T->dc[c] <= 3 && T->ac[c] >= 0 && T->ac[c] <= 3;
+    delete T;
+    if (!ok) return false;
+  }
+  return true;
 }
 
 }  // namespace vunet_jpeg

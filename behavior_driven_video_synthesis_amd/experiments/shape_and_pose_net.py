@@ -349,7 +349,7 @@ class ShapePoseNet:
         self.averager.start_step()
         # raw frames (``pose_img_u8`` + ``pose_img_geom`` instead of ``pose_img``): on the device from here on -- the step makes the
         # image itself (image_input.batch_images), and a recorded step takes them as static inputs.  Other batches: untouched.
-        batch = image_input.to_device(batch, self.device)
+        batch = image_input.to_device(batch, self.device, self.config["data"].get("jpeg_entropy", "host"))
         if self.gan is not None:
             # one (patch x patch) window per step, the same for the real and the generated batch: drawn on the host, handed
             # to the step through device memory (ops.CropWindow), so that the step's launch arguments never change

@@ -97,7 +97,7 @@ class Vunet:
         self.averager.start_step()
         self.optimizer.zero_grad()
         data = self.config["data"]
-        made = image_input.batch_images(batch, data["spatial_size"])   # ``pose_img`` from ``pose_img_u8`` (+ ``pose_img_geom``)
+        made = image_input.batch_images(batch, data["spatial_size"], data.get("jpeg_entropy", "host"))   # ``pose_img`` from ``pose_img_u8`` / ``pose_img_jpeg``
         if made:
             batch = {**batch, **made}
         made = appearance_aug.batch_appearance(batch, data["spatial_size"], self.appearance_aug)   # ``pose_img_inplane`` from ``pose_img_aug``

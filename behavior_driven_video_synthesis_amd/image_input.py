@@ -207,13 +207,13 @@ def bounding_box(kps, frame_hw, relax: float = 0.1) -> np.ndarray:
     return np.asarray(rows, dtype=np.int32)
 
 
-def decode_jpeg(batch: dict, device=None) -> dict:
+def decode_jpeg(batch: dict, device=None, entropy: str = "host") -> dict:
     """``batch`` with its encoded inputs decoded: for K in ``pose_img``, ``app_img``, where ``batch[K + "_jpeg"]`` (a sequence of
     ``bytes``, baseline JPEG streams) is present and neither ``batch[K]`` nor ``batch[K + "_u8"]`` is, ``K + "_jpeg"`` is replaced by
     ``K + "_u8"`` -- the stack of ``jpeg_decode.decode_batch`` on ``device`` (None: the current GPU), valid until the next batch is
     decoded -- and, where the batch brings no ``K + "_geom"``, by whole-frame geometry rows from the decoded sizes.  (With
     ``pose_img_aug``, whose route takes no geometry, the sizes go to ``pose_img_hw`` instead.)  The batch itself where it brings
-    no such key."""
+    no such key.  ``entropy``: ``decode_batch``'s keyword (``"device"``: the Huffman walk runs on the GPU too)."""
     out = None
     for key in KEYS:
         streams = batch.get(key + "_jpeg")
@@ -222,10 +222,10 @@ def decode_jpeg(batch: dict, device=None) -> dict:
         from . import jpeg_decode
         out = dict(batch) if out is None else out
         if device is None or torch.device(device).type != "cuda":
-            frames, hw = jpeg_decode.decode_batch(streams, tag=key)
+            frames, hw = jpeg_decode.decode_batch(streams, tag=key, entropy=entropy)
         else:
             with torch.cuda.device(device):
-                frames, hw = jpeg_decode.decode_batch(streams, tag=key)
+                frames, hw = jpeg_decode.decode_batch(streams, tag=key, entropy=entropy)
         del out[key + "_jpeg"]
         out[key + "_u8"] = frames
         if key == "pose_img" and "pose_img_aug" in batch:
@@ -236,13 +236,13 @@ def decode_jpeg(batch: dict, device=None) -> dict:
     return batch if out is None else out
 
 
-def to_device(batch: dict, device) -> dict:
+def to_device(batch: dict, device, entropy: str = "host") -> dict:
     """``batch`` with its raw-frame inputs (``K_u8``, ``K_geom`` for K in ``pose_img``, ``app_img``) as device tensors, host
     geometry checked first -- what a step that is recorded into a hipGraph needs (its inputs are static device buffers).  The
     batch itself where it brings none of them or they are on the device already.  ``pose_img_aug`` / ``pose_img_hw`` (the
     matrices and frame sizes of appearance_aug.batch_appearance) are staged alike.  Encoded inputs (``K_jpeg``) are decoded first
-    (``decode_jpeg``): a recorded step is replayed on the stack the decode has just filled."""
-    batch = decode_jpeg(batch, device)
+    (``decode_jpeg``, which takes ``entropy``): a recorded step is replayed on the stack the decode has just filled."""
+    batch = decode_jpeg(batch, device, entropy)
     out = None
     for key in KEYS:
         u8 = batch.get(key + "_u8")
@@ -266,12 +266,12 @@ def to_device(batch: dict, device) -> dict:
     return batch
 
 
-def batch_images(batch: dict, size: int) -> Dict[str, torch.Tensor]:
+def batch_images(batch: dict, size: int, entropy: str = "host") -> Dict[str, torch.Tensor]:
     """The images a batch leaves to the package: for K in ``pose_img``, ``app_img``, where ``batch[K + "_u8"]`` is present and
     ``batch[K]`` is not, ``K -> frames_to_images(batch[K + "_u8"], batch.get(K + "_geom"), size)[0]`` (and ``K + "_status"``).
-    A batch that brings ``K + "_jpeg"`` instead has it decoded first (``decode_jpeg``).  An empty dict -- no launch, nothing
+    A batch that brings ``K + "_jpeg"`` instead has it decoded first (``decode_jpeg``, which takes ``entropy``).  An empty dict -- no launch, nothing
     touched -- for a batch of ready fp32 images."""
-    batch = decode_jpeg(batch)
+    batch = decode_jpeg(batch, entropy=entropy)
     made = {}
     for key in KEYS:
         if key + "_u8" in batch and key not in batch:

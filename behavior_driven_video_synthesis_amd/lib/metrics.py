@@ -64,14 +64,14 @@ def psnr(rec: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> to
     return 10.0 * torch.log10(data_range * data_range / mse)
 
 
-def _with_images(model, batch):
+def _with_images(model, batch, jpeg_entropy: str = "host"):
     """``batch`` with ``pose_img`` / ``app_img`` made on the GPU from raw uint8 frames where it brings ``pose_img_u8`` /
     ``app_img_u8`` (+ ``*_geom``) or encoded ``pose_img_jpeg`` / ``app_img_jpeg`` instead (image_input.batch_images); the batch
     itself otherwise."""
     if not any(k in batch for k in ("pose_img_u8", "app_img_u8", "pose_img_jpeg", "app_img_jpeg")):
         return batch
     from .. import image_input
-    made = image_input.batch_images(batch, model.spatial_size)
+    made = image_input.batch_images(batch, model.spatial_size, jpeg_entropy)
     return {**batch, **made} if made else batch
 
 
@@ -90,14 +90,14 @@ def _inplane_app(model, batch, inplane_parts):
 
 @torch.no_grad()
 def compute_ssim(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor]], max_n_samples: int = 8000,
-                 inplane_normalize: bool = False, inplane_parts=None) -> float:
+                 inplane_normalize: bool = False, inplane_parts=None, jpeg_entropy: str = "host") -> float:
     """lib/metrics.py:22-116 on an iterable of batches: reconstruct (``model(app, stickman)[0]``), scale both images
     to [0, 1] (:86-92) and average the per-image SSIM over at most ``max_n_samples`` samples."""
     was_training = model.training
     model.eval()
     total, count = None, 0
     for batch in batches:
-        batch = _with_images(model, batch)
+        batch = _with_images(model, batch, jpeg_entropy)
         target = batch["pose_img"]
         if "app_img" in batch and type(model).__name__ == "VunetOrg":   # :71-74
             app = batch["app_img"]
@@ -153,7 +153,8 @@ def fid_from_features_device(gt_features, gen_features, tol: float = 1e-14, max_
     return float(fid_device(gt_features, gen_features, tol, max_iter).fid)
 
 
-def _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_samples, inplane_normalize, inplane_parts) -> float:
+def _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_samples, inplane_normalize, inplane_parts,
+                        jpeg_entropy="host") -> float:
     """``compute_fid`` with the features gathered on the device: one clone per batch (an ``InceptionV3`` returns views into its
     arena), no host copy, ``gt_features`` uploaded once."""
     def _keep(f):
@@ -164,7 +165,7 @@ def _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_sa
     gts, gens, n = [], [], 0
     try:
         for batch in batches:
-            batch = _with_images(model, batch)
+            batch = _with_images(model, batch, jpeg_entropy)
             target = batch["pose_img"]
             if "app_img" in batch and type(model).__name__ == "VunetOrg":
                 app = batch["app_img"]
@@ -185,21 +186,22 @@ def _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_sa
 @torch.no_grad()
 def compute_fid(model: torch.nn.Module, batches: Iterable[Dict[str, torch.Tensor]], feature_extractor: Callable,
                 gt_features: Optional[np.ndarray] = None, max_n_samples: int = 8000,
-                inplane_normalize: bool = False, inplane_parts=None, on_device: bool = False) -> float:
+                inplane_normalize: bool = False, inplane_parts=None, on_device: bool = False, jpeg_entropy: str = "host") -> float:
     """lib/metrics.py:119-282 on an iterable of batches.  ``feature_extractor(images) -> [N, D]`` stands for the
     reference's ``FIDInceptionModel`` (``models.imagenet_pretrained.FIDInceptionModel`` with the user's torchvision weights, or any
     other callable); ground-truth features are
     computed from ``batch["pose_img"]`` unless ``gt_features`` (the reference's cached ``<dataset>-fid-features.npy``) is
     given; generated features come from the reconstructions ``model(app, stickman)[0]`` (:243-258).  ``on_device``: the features
     of all batches stay in device buffers and the statistic is ``fid_from_features_device`` -- no per-batch host copy, no
-    ``np.cov``, no ``scipy.linalg.sqrtm``."""
+    ``np.cov``, no ``scipy.linalg.sqrtm``.  ``jpeg_entropy``: ``jpeg_decode.decode_batch``'s ``entropy`` for batches of encoded frames."""
     if on_device:
-        return _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_samples, inplane_normalize, inplane_parts)
+        return _compute_fid_device(model, batches, feature_extractor, gt_features, max_n_samples, inplane_normalize, inplane_parts,
+                                   jpeg_entropy)
     was_training = model.training
     model.eval()
     gts, gens, n = [], [], 0
     for batch in batches:
-        batch = _with_images(model, batch)
+        batch = _with_images(model, batch, jpeg_entropy)
         target = batch["pose_img"]
         if "app_img" in batch and type(model).__name__ == "VunetOrg":
             app = batch["app_img"]

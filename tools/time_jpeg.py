@@ -16,6 +16,15 @@ windows each, and the median and the spread (min .. max) are printed.  The decod
 anything is timed.  Needs the GPU and, to make the streams, PIL; there is no fallback.
 
     python tools/time_jpeg.py --out profiles/jpeg_time.txt
+
+``--entropy device`` (or ``both``) times the device entropy route (csrc/jpeg_huff_dec.hip, ``decode_batch(.., entropy="device")``)
+on the same streams instead of (or after) the above: each of its entry points (device events around every call of a decode), the
+rounds and launches the sync took, the one upload, ``decode_batch`` through the host route (8 threads) against the device route,
+alternating call by call in one process, and the graph step fed bytes through each route against the resident stack.
+``--table LABEL`` prints one line per quality for the library that is loaded (``VUNET_HIP_LIB``): the subsequence / workgroup size
+table is made of such lines, one build per pair of constants.
+
+    python tools/time_jpeg.py --entropy device --out profiles/jpeg_huffdec_time.txt
 """
 import argparse
 import copy
@@ -80,12 +89,108 @@ def frames(seed):
     return out
 
 
+def device_route(a, J, batches, lines, row):
+    """The device entropy route on ``batches`` {quality: streams}: see the module's docstring."""
+    from PIL import Image
+    real_call, spans = J._call, {}
+
+    def traced(name, *args):
+        e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        e[0].record()
+        real_call(name, *args)
+        e[1].record()
+        spans.setdefault(name, []).append(e)
+    for q, streams in batches.items():
+        want = np.stack([np.asarray(Image.open(io.BytesIO(s)).convert("RGB")) for s in streams])
+        out, hw = J.decode_batch(streams, tag=("device", q), entropy="device")
+        stats = J.last_stats()
+        assert hw.tolist() == [[H, W]] * N and np.array_equal(out.cpu().numpy(), want), f"quality {q}: the device route's bytes differ from Pillow's"
+        assert stats["host_fallbacks"] == 0, stats
+        (bufs,) = [b for k, b in J._buffers.items() if k[2] == ("device", q)]
+        nbytes, scan = bufs.entropy.upload_bytes, sum(len(s) for s in streams)
+        if a.table:
+            for _ in range(3):
+                J.decode_batch(streams, tag=("device", q), entropy="device")
+            med, lo, hi = wall(lambda: J.decode_batch(streams, tag=("device", q), entropy="device"), a.rounds)
+            lines.append(f"table  {a.table:<28} quality {q}: decode_batch entropy=device {med:8.3f} ms  ({lo:.3f} .. {hi:.3f})  rounds {stats['rounds']}, "
+                         f"launches {stats['launches']}, subsequences {stats['subsequences']}")
+            print(lines[-1], flush=True)
+            continue
+        lines.append(f"# quality {q}: {scan / N / 1024:.0f} KiB per stream; decode_batch(entropy=\"device\") == Pillow, bit for bit; sync: {stats['rounds']} rounds "
+                     f"in {stats['launches']} launches, {stats['subsequences']} subsequences ({-(-stats['subsequences'] // 64)} waves), 0 host fallbacks")
+        print(lines[-1], flush=True)
+        # ---- every entry point of one decode, device events around each call
+        J._call = traced
+        try:
+            for i in range(3 + a.rounds):
+                if i == 3:
+                    spans.clear()
+                J.decode_batch(streams, tag=("device", q), entropy="device")
+        finally:
+            J._call = real_call
+        torch.cuda.synchronize()
+        for name, events in spans.items():
+            calls = len(events) // a.rounds                     # of one decode; their times are summed
+            per = [sum(x.elapsed_time(y) for x, y in events[r * calls:(r + 1) * calls]) * 1e3 for r in range(a.rounds)]
+            row("launch", f"quality {q}: {name}" + (f" ({calls} calls, {stats['launches']} launches)" if calls > 1 else ""),
+                (statistics.median(per), min(per), max(per)), "us")
+        res = compare([("upload", lambda: bufs.dev[:nbytes].copy_(bufs.stage[:nbytes], non_blocking=True))], a.calls, a.rounds)
+        row("upload", f"quality {q}: descriptors + tables + rows + scan bytes, pinned", res["upload"], "us",
+            f"  {nbytes / 1e6:.2f} MB, {nbytes / res['upload'][0] / 1e3:.1f} GB/s")
+        # ---- the two routes, alternating call by call
+        routes = {"host": lambda: J.decode_batch(streams, tag=("host", q)), "device": lambda: J.decode_batch(streams, tag=("device", q), entropy="device")}
+        times = {k: [] for k in routes}
+        for k, fn in routes.items():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):
+            for k, fn in routes.items():
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t) * 1e3)
+        for k, v in times.items():
+            row("decode_batch, to the sync", f"quality {q}: entropy=\"{k}\"" + (", 8 threads" if k == "host" else ""),
+                (statistics.median(v), min(v), max(v)), "ms")
+        assert np.array_equal(out.cpu().numpy(), want)
+    if a.table or a.no_step:
+        return
+    from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import DEFAULT_CONFIG, ShapePoseNet, synthetic_batch
+    cfg = copy.deepcopy(DEFAULT_CONFIG)
+    cfg["training"].update(train_regressor=False)
+    size = cfg["data"]["spatial_size"]
+    tr = ShapePoseNet(cfg, device="cuda:0", total_steps=150000, vgg_synthetic=True, hip_graph=True)
+    base = synthetic_batch(N, size, "cuda:0", seed=42)
+    base.pop("pose_img")
+    ready = dict(base, pose_img_u8=J.decode_batch(batches[75], tag="ready")[0].clone())
+
+    def fed(q, mode):
+        batch = dict(base, pose_img_jpeg=batches[q])
+
+        def step():
+            tr.config["data"]["jpeg_entropy"] = mode            # (read at every step)
+            return tr.train_fn(batch)
+        return step
+    named = [("ready device-resident pose_img_u8", lambda: tr.train_fn(ready))]
+    named += [(f"pose_img_jpeg, quality {q}, entropy=\"{mode}\"", fed(q, mode)) for q in (75, 95) for mode in ("host", "device")]
+    for _ in range(8):
+        for _, fn in named:
+            fn()
+    torch.cuda.synchronize()
+    res = compare(named, max(a.calls // 4, 5), a.rounds, warm=2)
+    for n, r in res.items():
+        row(f"{size}^2 bs {N} step (hipGraph)", n, tuple(v * 1e-3 for v in r), "ms")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--entropy", choices=("host", "device", "both"), default="host")
+    ap.add_argument("--table", default=None, help="print one line per quality for the loaded library, labelled so, and stop")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_jpeg needs an MI355X")
@@ -105,7 +210,17 @@ def main():
 
     raw = frames(0)
     batches = {}
-    for q in (75, 95):
+    if a.entropy != "host" or a.table:
+        lines[0] = lines[0].replace("tools/time_jpeg.py:", f"tools/time_jpeg.py --entropy {a.entropy}:") + \
+            f"; subsequences of {J.SUBSEQ_BYTES} bytes, workgroups of {J.GROUP}"
+        for q in (75, 95):
+            batches[q] = []
+            for f in raw:
+                buf = io.BytesIO()
+                Image.fromarray(f, "RGB").save(buf, "JPEG", quality=q, subsampling=2)
+                batches[q].append(buf.getvalue())
+        device_route(a, J, batches, lines, row)
+    for q in (75, 95) if a.entropy != "device" and not a.table else ():
         streams = []
         for f in raw:
             buf = io.BytesIO()
@@ -156,7 +271,7 @@ def main():
         row("host, one thread + upload", f"quality {q}: Pillow Image.open + convert + asarray", wall(pillow, a.rounds), "ms")
 
     # ---- the flagship step from its hipGraph: JPEG bytes against a ready pose_img_u8
-    if not a.no_step:
+    if not a.no_step and a.entropy != "device" and not a.table:
         from behavior_driven_video_synthesis_amd.experiments.shape_and_pose_net import DEFAULT_CONFIG, ShapePoseNet, synthetic_batch
         cfg = copy.deepcopy(DEFAULT_CONFIG)
         cfg["training"].update(train_regressor=False)
