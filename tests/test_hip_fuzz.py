@@ -45,6 +45,19 @@ def test_fused_conv_random_config_vs_oracle(case):
     _check(case)
 
 
+@pytest.mark.parametrize("case", _cases(36, 2024), ids=_ids)
+def test_fused_conv_random_config_vs_oracle_f32(case):
+    """The same 36 cases at the same tolerances in the f32 scheme: in the default one the fp32-input kernels see only what
+    the split router refuses.  (A test of its own, so that the default scheme's cases keep their ids.)"""
+    from behavior_driven_video_synthesis_amd import ops
+    before = ops.conv_precision()
+    ops.set_conv_precision("f32")
+    try:
+        _check(case)
+    finally:
+        ops.set_conv_precision(before)
+
+
 # the streaming 1x1 kernel (csrc/conv_1x1.hip) takes channel counts in multiples of 32 on maps too large for split-K:
 # one / two / four m-tiles, ragged M, two sources, pixel tiles that straddle rows (W = 40), ELU + dropout, residual
 @pytest.mark.parametrize("case", [

@@ -198,7 +198,29 @@ def test_rnb_dual_source_tiled_wgrad_vs_oracle():
 @pytest.mark.parametrize("cin,cout,dual", [(32, 32, False), (16, 64, True), (64, 128, False), (8, 3, False)])
 def test_lds_tiled_conv_vs_oracle(nt, cin, cout, dual, monkeypatch):
     """LDS-tiled 3x3 kernel (forward with ELU+dropout prologue, data gradient with mirrored taps), every tile
-    height, one and two m-tiles, single and dual source; forced on small tensors through ops.set_tuning("tiled_force_nt")."""
+    height, one and two m-tiles, single and dual source; forced on small tensors through ops.set_tuning("tiled_force_nt").
+    Run in the f32 scheme (in the default one the split router has first refusal and these shapes may never reach the
+    LDS-tiled kernel), and the profiler's kernel names must show a conv_tiled_kernel of the forced tile height for the
+    forward and for the data gradient."""
+    from behavior_driven_video_synthesis_amd import ops
+    before = ops.conv_precision()
+    ops.set_conv_precision("f32")
+    ops.profile_start()
+    try:
+        _lds_tiled_conv_vs_oracle(nt, cin, cout, dual)
+    finally:
+        kernels = ops.profile_stop(by_kernel=True)
+        ops.set_conv_precision(before)
+    tiled = [[f.strip() for f in k[len("conv_tiled_kernel<"):-1].split(",")] for k in kernels
+             if k.startswith("conv_tiled_kernel<")]
+    want_nt, want_tw = ("1", "16") if nt == 16 else (str(nt), "32")
+    assert any(f[1] == want_nt and f[3] == "0" and f[5] == want_tw for f in tiled), kernels
+    # (cout = 3: the data gradient gathers 3 channels, which the LDS-tiled kernel -- whole 8-channel chunks -- does not take)
+    if cout % 8 == 0:
+        assert any(f[1] == want_nt and f[3] == "1" and f[5] == want_tw for f in tiled), kernels
+
+
+def _lds_tiled_conv_vs_oracle(nt, cin, cout, dual):
     from oracle import vunet_oracle as O
     from behavior_driven_video_synthesis_amd import ops
     M = _mods()
