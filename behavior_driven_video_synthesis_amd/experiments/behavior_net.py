@@ -144,11 +144,8 @@ class BehaviorNet:
         mode = eng.graph.run_step(("cvae", rows, t_in, self.use_regressor, self.cvae, bool(update), self._reg_generation), issue)
         if mode == "replayed" and update:
             self.optimizer.note_replayed_steps(1)
-        if update:
-            eng._packed_for = None     # the parameters moved: an inference call re-fills the images
-            inf = self.net._engine     # ... the inference engine's too: FusedAdam writes through a kernel, no version counter moves
-            if inf is not None:
-                inf._packed_for = None
+        if rp is not None:
+            self.regressor_engine.mark_written()
         p["reg"] = rp
         return p
 

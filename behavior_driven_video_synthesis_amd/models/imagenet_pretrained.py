@@ -271,7 +271,7 @@ class _P2Engine:
         """conv1_1 (3 input channels: the VALU kernel of csrc/conv_thin.hip, writing planes): its K-major weights for the
         forward and the data gradient and the bound constants, packed once (the stack is frozen)."""
         m = self.program[0]
-        stamp = (m.weight.data_ptr(), m.weight._version, m.bias._version)
+        stamp = ops._versions((m.weight, m.bias))
         rec = m.__dict__.get("_p2first")
         if rec is None or rec[0] != stamp:
             w, b = m.weight.detach().contiguous(), m.bias.detach().contiguous()

@@ -428,7 +428,7 @@ class InceptionV3(nn.Module):
         else:
             m = self.layer(name)
             params = (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var)
-        stamp = tuple((t.data_ptr(), t._version) for t in params)
+        stamp = ops._versions(params)
         hit = self._packs.get(name)
         if hit is not None and hit[0] == stamp:
             return hit

@@ -90,6 +90,19 @@ def _c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return None if t is None else (t if t.is_contiguous() else t.contiguous())
 
 
+def _versions(tensors) -> tuple:
+    """The stamp every weight-image cache compares: (storage address, version counter) per tensor, None for None."""
+    return tuple(None if t is None else (t.data_ptr(), t._version) for t in tensors)
+
+
+def mark_written(tensors):
+    """A kernel wrote these module tensors through raw pointers (or through ``.data``): move their version counters, as an
+    in-place torch operation would have.  Host-only -- nothing is launched, so it is harmless while a stream records."""
+    tensors = [t for t in tensors if t is not None]
+    if tensors:
+        torch.autograd.graph.increment_version(tensors)
+
+
 def _r2(x: int) -> int:
     return (x + 1) // 2 * 2
 
@@ -1070,7 +1083,7 @@ def _packed_weights(cfg, v, g, bias, gamma, beta, c1, c2, need_x):
     # frozen feature extractor (VGG19): pack once, reuse for every pass.  The packed buffers hang off the weight
     # tensor itself (they die with it) and are stamped with every operand's storage address and version counter.
     sub = (c1, c2, cfg.kind, bool(need_x), _scheme())
-    stamp = tuple(None if t is None else (t.data_ptr(), t._version) for t in (v, g, bias, gamma, beta))
+    stamp = _versions((v, g, bias, gamma, beta))
     hit = getattr(v, "_vunet_frozen_pack", {}).get(sub)
     if hit is not None and hit[0] == stamp:
         return hit[1], False
@@ -1973,7 +1986,7 @@ class P2Weights:
 
     def image(self, dgrad: bool):
         rec = self._img.get(dgrad)
-        stamp = (self.weight.data_ptr(), self.weight._version, None if self.bias is None else self.bias._version)
+        stamp = _versions((self.weight, self.bias))
         if rec is None or rec[0] != stamp:
             nbytes = _lib.lib().vunet_p2_weight_image_bytes(self.cout, self.cin, int(dgrad))
             if nbytes <= 0:

@@ -96,6 +96,9 @@ class FusedAdam:
             b.step = 0
             self.buckets.append(b)
             self.param_groups.append(g)
+        # the update kernels write the flat buffers the parameters are views of: every step announces that on the parameters
+        # themselves (ops.mark_written), so that whatever was packed from them, or saved for a backward, is seen to be stale
+        self._params = [p for b in self.buckets for p in b.params]
         self.lr_dev = self.step_dev = None
 
     def _uniform(self):
@@ -123,9 +126,11 @@ class FusedAdam:
 
     def note_replayed_steps(self, n: int = 1):
         """A captured graph containing ``n`` calls of ``step()`` was replayed: advance the host-side step counts (the
-        checkpoint layout carries them) without launching anything."""
+        checkpoint layout carries them) without launching anything.  The parameters' version counters move once: they tell
+        that a write happened, not how many."""
         for b in self.buckets:
             b.step += n
+        ops.mark_written(self._params)
 
     def zero_grad(self, set_to_none: bool = False):
         if self._arena is not None:
@@ -135,6 +140,10 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
+        self._issue_step(grad_scale)
+        ops.mark_written(self._params)
+
+    def _issue_step(self, grad_scale: float):
         if self.buckets[0].grad.is_cuda:
             ops.join_wgrad_streams()   # gradients written in place by backward's companion streams come first
         if self.step_dev is not None:

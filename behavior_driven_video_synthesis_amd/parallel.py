@@ -307,5 +307,7 @@ def _scale_(t: torch.Tensor, a: float):
 def broadcast_parameters(buckets, src: int = 0, process_group=None):
     """One-time replica initialisation (replaces DataParallel's per-step broadcast)."""
     if dist.is_initialized() and (dist.get_world_size(process_group) > 1 or os.environ.get("VUNET_DP_FORCE") == "1"):
+        from . import ops
         for b in buckets:
             dist.broadcast(b.flat, src=src, group=process_group)
+            ops.mark_written(b.params)     # torch counted the write on the flat buffer, not on the parameters viewing it

@@ -26,7 +26,7 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import _lib
-from .ops import _call, _p, _stream
+from .ops import _call, _p, _stream, mark_written
 from .seq import ACT_NONE, SeqLinearDesc, _GraphCache, _need_device, _need_module_on, _up, linear
 from .seq_train import (ACT_RELU_SEQ, AdamState, SeqDxDesc, TrainLayer, _table, adam_state_dict, dx_chain, dx_split,
                         load_adam_state)
@@ -91,6 +91,7 @@ class RegProbeEngine:
             self.lin.append(TrainLayer(f"linears.{i}", lin_.weight, lin_.bias, pc, kp))
             kp = self.lin[-1].mp
         self.n_out = r.linears[-1].weight.shape[0]
+        self._inplace = [t for lay in self.layers() for t in lay.inplace_params()]
         self.adam.step_dev.zero_()
         self._reset_recordings()
 
@@ -194,6 +195,7 @@ class RegProbeEngine:
         _need_device(targets)
         p["tgt"].copy_(targets.detach().reshape(rows, self.n_out))
         self.graph.run_step(rows, lambda: self._issue_step(rows, p))
+        mark_written(self._inplace)      # (the padded images' parameters: ``write_back``)
         return self.last
 
     def losses(self) -> torch.Tensor:

@@ -97,7 +97,7 @@ class BlockedTransfer:
     # ---- weights ------------------------------------------------------------------------------------------------
     def _pack(self, m, c1: int, c2: int = 0) -> _Packed:
         params = m._params()
-        stamp = (c1, c2) + tuple((t.data_ptr(), t._version) for t in params)
+        stamp = (c1, c2) + ops._versions(params)
         hit = self._packs.get(id(m))
         if hit is not None and hit.stamp == stamp:
             return hit

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .ops import _call, _graph_recording, _p, _stream
+from .ops import _call, _graph_recording, _p, _stream, _versions, mark_written
 
 MAX_ROWS = 64   # batch rows per launch (four 16-row MFMA tiles); larger batches are processed in chunks
 
@@ -292,6 +292,7 @@ def actnorm_initialize(mod, x: torch.Tensor):
     x2 = _flat2(x).contiguous()
     b, c = x2.shape
     _call("vunet_seq_actnorm_init", _p(x2), c, b, c, _p(mod.loc.data), _p(mod.scale.data), _stream())
+    mark_written((mod.loc, mod.scale))
 
 
 def actnorm_apply(mod, x: torch.Tensor, reverse: bool):
@@ -380,10 +381,6 @@ def _inference_only(params):
                            "torch.no_grad() or freeze the parameters")
 
 
-def _versions(params) -> tuple:
-    return tuple((p.data_ptr(), p._version) for p in params)
-
-
 class FlowEngine:
     """``UnconditionalFlow2`` (models/flow/blocks.py:95-128) in both directions for batches of <= 64 rows."""
 
@@ -415,9 +412,11 @@ class FlowEngine:
         self.graph.clear()
 
     # ---- weights
+    def _key(self) -> tuple:
+        return (self.weights,) + _versions(list(self.flow.parameters()) + list(self.flow.buffers()))
+
     def _pack(self, dev=None):
-        params = list(self.flow.parameters()) + list(self.flow.buffers())
-        key = (self.weights,) + _versions(params)
+        key = self._key()
         if key == self._packed_for:
             return
         if dev is not None:
@@ -516,6 +515,7 @@ class FlowEngine:
                 norm = self.flow.sub_layers[i].norm_layer
                 if norm.initialized.item() == 0:
                     _call("vunet_seq_actnorm_init", _p(s0[i]), self.ld, rows, self.C, _p(norm.loc.data), _p(norm.scale.data), _stream())
+                    mark_written((norm.loc, norm.scale))
                     norm.initialized.fill_(1)
                 self._step(rows, s0[i], self.ld, s0[i], self.ld, 0, scale=blk["scale"], loc=blk["loc"], logdet=ld_acc)
             h0, h1 = blk["halves"]

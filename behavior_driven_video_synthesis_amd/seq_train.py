@@ -22,8 +22,8 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .ops import _call, _p, _stream
-from .seq import (ACT_LRELU, BF16_INFERENCE_ONLY, FlowEngine, SeqCouplingDesc, _need_device, _up, _versions, padded_vector,  # noqa: F401
+from .ops import _call, _p, _stream, _versions, mark_written
+from .seq import (ACT_LRELU, BF16_INFERENCE_ONLY, FlowEngine, SeqCouplingDesc, _need_device, _up, padded_vector,  # noqa: F401
                   weight_image)
 from .seq_passes import KeepsPasses, PassPool
 
@@ -133,8 +133,9 @@ class TrainLayer:
 
     The images are [mp, kp] / [mp], multiples of 64.  A parameter whose 2-D view [out, in k k] fits and is contiguous IS its image
     and is updated in place; any other trains as a zero-padded image (padded rows produce zeros and receive no update) that
-    ``write_back`` copies into the parameter.  ``pieces``: (first column of the parameter's matrix, columns, first column in the
-    image) per column block of a padded image.  ``images``: a (weight, bias) image pair the caller already holds -- nothing is
+    ``write_back`` copies into the parameter.  Either way the write goes through a raw pointer: ``write_back`` announces its
+    own (``ops.mark_written``), and the engine that launches the update sweep announces ``inplace_params()`` after it.
+    ``pieces``: (first column of the parameter's matrix, columns, first column in the image) per column block of a padded image.  ``images``: a (weight, bias) image pair the caller already holds -- nothing is
     allocated or loaded here.  The moments ``m, v, bm, bv`` are shaped like the images and allocated on first use."""
 
     def __init__(self, name: str, weight: torch.Tensor, bias: torch.Tensor, pieces=None, kp: Optional[int] = None, images=None):
@@ -158,6 +159,10 @@ class TrainLayer:
     def inplace(self) -> bool:
         return self.w_inplace and self.b_inplace
 
+    def inplace_params(self) -> list:
+        """The module tensors the update sweep itself writes: those that are their own image."""
+        return [t for t, hit in ((self.weight, self.w_inplace), (self.bias, self.b_inplace)) if hit]
+
     def load(self):
         """The parameter's values -> the padded images."""
         if not self.w_inplace:
@@ -174,6 +179,7 @@ class TrainLayer:
                 self.weight.data.copy_(self._gather(self.w))
         if not self.b_inplace:
             _call("vunet_seq_unpack_rows", _p(self.b), self.mp, 0, 0, 1, _p(self.bias.data), 1, self.rows, 0, _stream())
+        mark_written([t for t, hit in ((self.weight, self.w_inplace), (self.bias, self.b_inplace)) if not hit])
 
     def _gather(self, img: Optional[torch.Tensor]) -> torch.Tensor:
         """An image's valid part in the weight's own shape, as a copy (no image: zeros)."""
@@ -528,6 +534,7 @@ class FlowTrainEngine(KeepsPasses, FlowEngine):
         ``reference_nll_loss`` (None: ``torch.randn``, as :309 does)."""
         x2 = self._check_input(x.detach())
         rows = x2.shape[0]
+        first = not self._initialised()
         self._initialise_actnorm(x2)
         p = self._plan(rows)
         p["x_in"].copy_(x2)
@@ -547,15 +554,15 @@ class FlowTrainEngine(KeepsPasses, FlowEngine):
             self._issue_train_backward(rows, p, p["dzl"], self.ld, p["tables"], self.adam.hp)
             self._write_back()
         self.graph.run_step(("train", rows), issue)
-        inf = getattr(self.flow, "_engine", None)
-        if inf is not None:
-            inf._packed_for = None       # its tile-major weight copies are a step behind: re-packed at its next call
+        # the step wrote every parameter of the flow; a replayed recording runs no host code, so it is announced here.  This
+        # engine's images are what was written: it takes the new stamp instead of re-packing at its next call (the step that
+        # ran ActNorm's initialisation does not: the ``initialized`` buffers moved too, and the call after it re-packs once)
+        mark_written(self.flow.parameters())
+        if not first:
+            self._packed_for = self._key()
         return p["scalars"]
 
     # ---- autograd's view of the same kernels
-    def _param_versions(self) -> tuple:
-        return _versions(list(self.flow.parameters()) + list(self.flow.buffers()))
-
     def train_forward(self, x: torch.Tensor):
         """-> (z, logdet, token).  With ``max_passes`` > 1 the pass takes the lowest free slot of its batch size and keeps that
         plan until ``token`` (held by the autograd node) is collected, as the behaviour net's passes do.  With ``max_passes`` 1
@@ -570,20 +577,19 @@ class FlowTrainEngine(KeepsPasses, FlowEngine):
         p["x_in"].copy_(x2)
         self._issue_train_forward(rows, p)
         p["pass"] = p.get("pass", 0) + 1      # which forward the plan's activations belong to
-        return p["x_out"].clone(), p["logdet"][:rows].clone(), (p, lease, rows, p["pass"], self._param_versions())
+        return p["x_out"].clone(), p["logdet"][:rows].clone(), (p, lease, rows, p["pass"], self._key())
 
     def train_backward(self, token, gz: Optional[torch.Tensor], gld: Optional[torch.Tensor]):
         """-> (dx [B, C], {parameter name: gradient}) for the forward pass ``token`` came from.  The pass is not spent: every
         buffer the chain writes is written anew by each run, so a second call returns the same bits.  Parameters that were
         modified since the forward are refused, as torch refuses them (the kernels read the weights in place: the gradients would
-        be those of another function).  ``train_step``'s fused Adam writes through a kernel and moves no version counter: mixing it
-        with passes under autograd goes undetected."""
+        be those of another function)."""
         p, _, rows, pass_id, versions = token
         if pass_id != p["pass"]:
             raise RuntimeError("the flow was run again before this pass's backward: its saved activations are gone (with max_passes "
                                "= 1, the default, the engine keeps one forward pass at a time: raise its max_passes attribute to keep "
                                "several in flight)")
-        if versions != self._param_versions():
+        if versions != self._key():
             raise RuntimeError(STALE_WEIGHTS.format("flow"))
         dev = p["x_in"].device
         p["dzl"].zero_()
@@ -686,12 +692,8 @@ class BehaviorTrainEngine(KeepsPasses, BehaviorEngine):
     :681: three calls of one shape per iteration): every pass keeps a plan of its own -- the lowest free slot of its shape,
     ``seq_passes.PassPool``; slot k is allocated when k + 1 passes of that shape are alive, at most ``max_passes`` (4) -- until its
     autograd node dies, and its backward may run more than once (``retain_graph=True``).  A backward after the parameters were
-    modified raises, as torch's does.  ``optim.FusedAdam`` writes through a raw kernel and moves no version counter: mixing the
-    fused optimiser (or ``experiments.behavior_net.BehaviorNet``'s fused step, which works in slot 0 without taking it) with
-    passes under autograd goes undetected, and so does a write through ``p.data``.  The weight images are re-packed when a
-    counter moved, not on every pass: after such an uncounted write the next forward under autograd would run on the OLD
-    images -- whoever writes that way sets ``_packed_for = None`` on this engine afterwards, as ``BehaviorNet``'s fused step
-    does (experiments/behavior_net.py, ``_cvae_step``)."""
+    modified raises, as torch's does -- after a step of ``optim.FusedAdam`` too, which announces its writes
+    (``ops.mark_written``).  ``experiments.behavior_net.BehaviorNet``'s fused step works in slot 0 without taking it."""
 
     HOFF_PAD = 64
 
@@ -956,6 +958,7 @@ class RegressorTrainEngine:
         self.layers = [self.fc1, self.fc2, self.fc3, self.fc4, self.fc5]          # the order of ``reg.parameters()``
         for layer in self.layers:
             layer.ensure_moments()
+        self._inplace = [t for layer in self.layers for t in layer.inplace_params()]
         self.w5, self.b5 = self.fc5.w, self.fc5.b
         self.adam.step_dev.zero_()
         self._plans.clear()
@@ -1019,6 +1022,10 @@ class RegressorTrainEngine:
         d = SeqDxDesc(rows, H, H, 1, s1, 0)
         _call("vunet_seq_dx", ctypes.byref(d), _p(r.fc1.weight.data), None, _p(p["dz1"]), _p(p["raw"]), _stream())
         _call("vunet_seq_reg_adv", _p(p["raw"]), s1, rows, H, _p(p["reg"]), _p(gmu), _p(p["adv"]), _stream())
+
+    def mark_written(self):
+        """``issue_step`` ran, or a recording that holds it was replayed: announce the parameters its updates wrote in place."""
+        mark_written(self._inplace)
 
     # ---- checkpoints: the reference's layout (``Regressor_fly`` keys; torch.optim.Adam's state)
     def write_back(self):

@@ -233,8 +233,8 @@ def test_full_size_smoke():
 # ---- 7. the inference engine after fused training steps
 def test_inference_after_fused_training_steps_uses_the_new_weights():
     """generate_seq, three fused cVAE steps (graph on, update), generate_seq again: equal, bit for bit, to a fresh net loaded
-    with the current state_dict.  FusedAdam writes the parameters through a kernel, so no version counter moves: the
-    inference engine's weight images must be invalidated by the step itself."""
+    with the current state_dict.  FusedAdam writes the parameters through a kernel and announces it (``ops.mark_written``):
+    the inference engine's stamp no longer matches and it fills its weight images again."""
     from behavior_driven_video_synthesis_amd.experiments.behavior_net import BehaviorNet, DEFAULT_CONFIG
     from behavior_driven_video_synthesis_amd.models.pose_behavior_rnn import ResidualBehaviorNet
     cfg = copy.deepcopy(DEFAULT_CONFIG)
