@@ -18,27 +18,26 @@ The bytes are Pillow's (libjpeg-turbo's defaults: the "islow" integer inverse DC
 * ``decode_batch``  streams -> ``(frames uint8 [N, Hmax, Wmax, 3] on the device, hw int32 [N, 2] on the host)``;
 * ``JpegUnsupported`` / ``JpegCorrupt``  carry the C error code and its reason.
 
+What this module shares with ``jpeg_encode`` -- the descriptor table, the reused memory, the upload layouts, the thread pool -- is
+``jpeg_host``.
+
 Supported: baseline sequential, 8-bit, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, restart intervals.
 Progressive, arithmetic-coded, 12-bit and CMYK streams are refused (``fallback=True`` hands them to Pillow on the host where PIL
 imports).  There is no CPU path for the supported ones."""
 from __future__ import annotations
 
 import ctypes
+import functools
 import io
 from collections import namedtuple
-from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, jpeg_host
+from .jpeg_host import MAX_SIDE, MAX_THREADS, Arena, JpegImg, JpegInfoC, fill_rows, layout, per_image
 from .ops import _call, _p, _stream
-
-JpegInfoC = _lib.struct("vunet_jpeg_info")
-JpegImg = _lib.struct("vunet_jpeg_img")
-MAX_SIDE = 65535                         # N, Hmax, Wmax of one call (grid dimensions)
-MAX_THREADS = 16
 
 REASONS = {_lib.const("VUNET_JPEG_ERR_TRUNCATED"): "the stream ends inside a segment, a table or the scan, or before EOI",
            _lib.const("VUNET_JPEG_ERR_MARKER"): "no SOI, a marker out of place, a malformed segment or a missing table",
@@ -54,13 +53,9 @@ _UNSUPPORTED = range(-119, -109)         # VUNET_JPEG_ERR_*: -110 .. -119 unsupp
 JpegInfo = namedtuple("JpegInfo", "height width ncomp hsamp vsamp mcu_cols mcu_rows restart bw0 bh0 bw1 bh1 nblocks ncoef")
 
 
-class JpegError(ValueError):
+class JpegError(jpeg_host._CodecError):
     """``code``: the library's VUNET_JPEG_ERR_* value; ``reason``: what it says; ``index``: the stream's place in the batch."""
-
-    def __init__(self, code: int, index: Optional[int] = None):
-        self.code, self.reason, self.index = int(code), REASONS.get(int(code), "unknown error"), index
-        where = "" if index is None else f"stream {index}: "
-        super().__init__(f"{where}{self.reason} (code {self.code})")
+    REASONS, WHAT = REASONS, "stream"
 
 
 class JpegUnsupported(JpegError):
@@ -99,54 +94,13 @@ def parse(data) -> JpegInfo:
     return JpegInfo(*(getattr(info, f) for f in JpegInfo._fields))
 
 
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("decode_batch needs the GPU (hand-written gfx950 kernels; no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-class _Buffers:
-    """The reused memory of one (device, stream, tag): the pinned staging buffer, its device mirror, the component planes, the
-    default output stacks.  Grow-only: a second call at a shape allocates nothing."""
-
-    def __init__(self, device: torch.device):
-        self.device, self.stage, self.dev, self.planes, self.event, self.outs = device, None, None, None, None, {}
-        self.entropy = None               # the device entropy route's own buffers (``_Entropy``), made on its first call
-
-    def reserve(self, nbytes: int, plane_bytes: int):
-        if self.event is not None:
-            self.event.synchronize()      # the last upload has left the pinned buffer before the host writes it again
-        if self.stage is None or self.stage.numel() < nbytes:
-            pin = self.device.type == "cuda"
-            self.stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=pin)
-            self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        if self.planes is None or self.planes.numel() < plane_bytes:
-            self.planes = torch.empty(plane_bytes, dtype=torch.uint8, device=self.device)
-
-    def out(self, n: int, hmax: int, wmax: int) -> torch.Tensor:
-        key = (n, hmax, wmax)
-        if key not in self.outs:
-            self.outs[key] = torch.zeros(n, hmax, wmax, 3, dtype=torch.uint8, device=self.device)
-        return self.outs[key]
-
-
-_buffers: Dict[tuple, _Buffers] = {}
-_pools: Dict[int, ThreadPoolExecutor] = {}
+_device = functools.partial(jpeg_host.device, "decode_batch")     # (a module attribute: the CPU tests replace it)
+_buffers: Dict[tuple, Arena] = {}        # by (device, stream, tag): ``stage`` / ``dev`` / ``planes``, the default output stacks ``outs``
 
 
 def clear_buffers() -> None:
     """Drop the cached buffers (not while frames returned without ``out=`` are still in use)."""
     _buffers.clear()
-
-
-def _pool(threads: int) -> ThreadPoolExecutor:
-    if threads not in _pools:
-        _pools[threads] = ThreadPoolExecutor(max_workers=threads, thread_name_prefix="vunet-jpeg")
-    return _pools[threads]
-
-
-def _round(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
 
 
 def _pillow_rgb(data: bytes, index: int, err: JpegError) -> np.ndarray:
@@ -157,19 +111,52 @@ def _pillow_rgb(data: bytes, index: int, err: JpegError) -> np.ndarray:
     return np.array(Image.open(io.BytesIO(data)).convert("RGB"))   # (a writable copy)
 
 
-def _launch(buf: _Buffers, m: int, nbytes: int, q_off: int, c_off: int, coef_count: int, plane_bytes: int, out: torch.Tensor) -> None:
-    """One upload of the staging buffer's first ``nbytes`` (descriptors | tables | coefficients) and the two launches, on the current
-    stream.  The host copy of the descriptors is what the library checks before it launches."""
+def _finish(buf: Arena, coef, coef_count: int, q_off: int, m: int, plane_bytes: int, out: torch.Tensor) -> None:
+    """What every route ends in, two launches on the current stream: the coefficients at the device pointer ``coef`` -> the planes
+    -> ``out``, by the descriptors and tables of the uploaded block.  The host copy of the descriptors is what the library checks
+    before it launches."""
     n, hmax, wmax = (int(v) for v in out.shape[:3])
-    buf.dev[:nbytes].copy_(buf.stage[:nbytes], non_blocking=True)
-    if buf.event is None:
-        buf.event = torch.cuda.Event()
-    buf.event.record()
-    base = buf.dev.data_ptr()
-    coef, qtab, imgs = ctypes.c_void_p(base + c_off), ctypes.c_void_p(base + q_off), ctypes.c_void_p(base)
-    host = ctypes.c_void_p(buf.stage.data_ptr())
-    _call("vunet_jpeg_idct", coef, coef_count, qtab, m * 192, imgs, host, m, _p(buf.planes), plane_bytes, _stream())
-    _call("vunet_jpeg_to_rgb", _p(buf.planes), plane_bytes, imgs, host, m, n, hmax, wmax, _p(out), _stream())
+    base, host, stream = buf.dev.data_ptr(), ctypes.c_void_p(buf.stage.data_ptr()), _stream()
+    imgs, qtab = ctypes.c_void_p(base), ctypes.c_void_p(base + q_off)
+    _call("vunet_jpeg_idct", coef, coef_count, qtab, m * 192, imgs, host, m, _p(buf.planes), plane_bytes, stream)
+    _call("vunet_jpeg_to_rgb", _p(buf.planes), plane_bytes, imgs, host, m, n, hmax, wmax, _p(out), stream)
+
+
+_HostPlan = namedtuple("_HostPlan", "m nbytes q_off c_off coef_count plane_bytes")     # (the arguments of ``_launch`` behind ``buf``)
+
+
+def _host_plan(m: int, coef_count: int) -> _HostPlan:
+    """The host route's upload: descriptors | quantisation tables | coefficients, these on a 128-byte line."""
+    offs, nbytes = layout(("imgs", m * ctypes.sizeof(JpegImg), 1), ("qtab", 384 * m, 1), ("coef", 2 * coef_count, 128))
+    return _HostPlan(m, nbytes, offs["qtab"], offs["coef"], coef_count, max(coef_count, 16))
+
+
+def _launch(buf: Arena, m: int, nbytes: int, q_off: int, c_off: int, coef_count: int, plane_bytes: int, out: torch.Tensor) -> None:
+    """The host route's device step: one upload of the staging buffer's first ``nbytes`` (descriptors | tables | coefficients) and
+    the two launches."""
+    buf.upload(nbytes)
+    _finish(buf, ctypes.c_void_p(buf.dev.data_ptr() + c_off), coef_count, q_off, m, plane_bytes, out)
+
+
+def _decode_host(buf: Arena, data, infos, native, threads: int, out: torch.Tensor) -> None:
+    """The host route of ``decode_batch`` for the streams ``native``: the entropy decode of every stream on the thread pool, straight
+    into the pinned staging buffer, then ``_launch``."""
+    own = [infos[i] for i in native]
+    plan = buf.layout = _host_plan(len(native), sum(inf.ncoef for inf in own))
+    buf.staging(plan.nbytes)
+    buf.get("planes", plan.plane_bytes, torch.uint8)
+    base = buf.stage.data_ptr()
+    rows = (JpegImg * plan.m).from_address(base)
+    fill_rows(rows, own, range(0, 192 * plan.m, 192), native)
+    fn, coef_offs = _lib.lib().vunet_jpeg_entropy_decode, [r.coef_off for r in rows]
+
+    def one(j):
+        d = data[native[j]]
+        return fn(d, len(d), ctypes.byref(own[j]), ctypes.c_void_p(base + plan.c_off + 2 * coef_offs[j]), ctypes.c_void_p(base + plan.q_off + 384 * j))
+    for i, rc in zip(native, per_image(one, range(plan.m), threads)):
+        if rc != 0:
+            raise _error(rc, i)
+    _launch(buf, *plan, out)
 
 
 Subseq = _lib.struct("vunet_jpeg_subseq")
@@ -188,29 +175,6 @@ def last_stats() -> dict:
     return dict(_stats)
 
 
-class _Entropy:
-    """The device route's own reused memory (grow-only, as ``_Buffers``): the coefficients, the walk's state, the counters and flags
-    with their pinned mirror, and a pinned scratch for coefficients the host walk decodes instead."""
-
-    def __init__(self, device: torch.device):
-        self.device, self.coef, self.state, self.small, self.small_host, self.scratch = device, None, None, None, None, None
-        self.upload_bytes = 0
-
-    def reserve(self, coef_count: int, state_words: int, small_words: int):
-        if self.coef is None or self.coef.numel() < coef_count:
-            self.coef = torch.empty(coef_count, dtype=torch.int16, device=self.device)
-        if self.state is None or self.state.numel() < state_words:
-            self.state = torch.empty(state_words, dtype=torch.int32, device=self.device)
-        if self.small is None or self.small.numel() < small_words:
-            self.small = torch.empty(small_words, dtype=torch.int32, device=self.device)
-            self.small_host = torch.empty(small_words, dtype=torch.int32, pin_memory=self.device.type == "cuda")
-
-    def host_coef(self, count: int) -> torch.Tensor:
-        if self.scratch is None or self.scratch.numel() < count:
-            self.scratch = torch.empty(count, dtype=torch.int16, pin_memory=self.device.type == "cuda")
-        return self.scratch
-
-
 def _scan(lib, d: bytes, inf):
     """The marker scan of one stream -> (code, segments int64 [nseg, 3], qtab + table row as one uint8 array)."""
     mcus = inf.mcu_cols * inf.mcu_rows
@@ -221,14 +185,20 @@ def _scan(lib, d: bytes, inf):
     return rc, segs[:nseg.value], tabs
 
 
-def _decode_device(buf: _Buffers, data, infos, native, threads: int, out: torch.Tensor) -> None:
+def _device_layout(m: int, nsub: int, nscan: int):
+    """The device route's upload -> (offsets by name, bytes): descriptors | quantisation tables | table rows | spans | subsequence
+    rows | scan bytes, and 16 bytes past their rounded end for the walk's last loads."""
+    return layout(("imgs", m * ctypes.sizeof(JpegImg), 1), ("qtab", 384 * m, 1), ("tabs", m * TAB_BYTES, 16), ("spans", 8 * m, 1),
+                  ("rows", nsub * ctypes.sizeof(Subseq), 16), ("bytes", nscan, 1), ("tail", 16, 16))
+
+
+def _decode_device(buf: Arena, data, infos, native, threads: int, out: torch.Tensor) -> None:
     """The device route of ``decode_batch`` for the streams ``native`` (indices with a parsed header): marker scan on the host (no bit
     walk), ONE upload of descriptors | quantisation tables | table rows | spans | subsequence rows | scan bytes, the sync launches
     with a readback of their counters every ``SYNC_BATCH`` (the first wait), block ordinals, write and DC sums, a readback of the
-    per-image flags (the second wait), the host walk for what was irregular or flagged, then the two launches of the host route."""
+    per-image flags (the second wait), the host walk for what was irregular or flagged, then ``_finish``."""
     lib, m = _lib.lib(), len(native)
-    scans = [_scan(lib, data[i], infos[i]) for i in native] if threads == 1 or m == 1 else \
-        list(_pool(threads).map(lambda i: _scan(lib, data[i], infos[i]), native))
+    scans = per_image(lambda i: _scan(lib, data[i], infos[i]), native, threads)
     for i, (rc, _, _) in zip(native, scans):
         if rc < 0:
             raise _error(rc, i)
@@ -236,38 +206,37 @@ def _decode_device(buf: _Buffers, data, infos, native, threads: int, out: torch.
     counts, offs, nsub, nscan, nthreads = [], [], 0, 0, 0
     for rc, segs, _ in scans:
         rows = 0 if rc else int(((segs[:, 1] - segs[:, 0] + SUBSEQ_BYTES - 1) // SUBSEQ_BYTES).sum())
-        counts.append(_round(rows, GROUP))
+        counts.append(jpeg_host.round_up(rows, GROUP))
         nthreads += rows
         offs.append(nscan - (int(segs[0, 0]) if rows else 0))
-        nsub, nscan = nsub + counts[-1], nscan + (_round(int(segs[-1, 1] - segs[0, 0]), 16) if rows else 0)
+        nsub, nscan = nsub + counts[-1], nscan + (jpeg_host.round_up(int(segs[-1, 1] - segs[0, 0]), 16) if rows else 0)
     if nscan > MAX_SCAN_BYTES:
         raise ValueError(f'decode_batch: {nscan} bytes of scans in one call; entropy="device" takes at most {MAX_SCAN_BYTES} '
                          '(entropy="host" has no such limit)')
-    q_off = m * ctypes.sizeof(JpegImg)
-    t_off = _round(q_off + m * 384, 16)
-    s_off = t_off + m * TAB_BYTES
-    r_off = _round(s_off + 8 * m, 16)
-    b_off = r_off + nsub * ctypes.sizeof(Subseq)
-    nbytes = _round(b_off + nscan, 16) + 16
-    coef_count = sum(infos[i].ncoef for i in native)
+    buf.layout = offs_up, nbytes = _device_layout(m, nsub, nscan)
+    q_off, t_off, s_off, r_off, b_off = (offs_up[k] for k in ("qtab", "tabs", "spans", "rows", "bytes"))
+    own = [infos[i] for i in native]
+    coef_count = sum(inf.ncoef for inf in own)
     plane_bytes = max(coef_count, 16)
-    buf.reserve(nbytes, plane_bytes)
-    if buf.entropy is None:
-        buf.entropy = _Entropy(buf.device)
+    buf.staging(nbytes)
+    buf.get("planes", plane_bytes, torch.uint8)
+    if buf.entropy is None:               # coefficients, the walk's state, counters | flags and their pinned mirror; ``scratch``:
+        buf.entropy = Arena(buf.device, "coef state small small_host scratch")   # pinned, for what the host walk decodes instead
     ent = buf.entropy
     bound = max(counts) // GROUP + 1
-    ncounters = _round(bound, SYNC_BATCH)
-    ent.reserve(coef_count, max(nsub * STATE_WORDS, 4), ncounters + m)
+    ncounters = jpeg_host.round_up(bound, SYNC_BATCH)
+    ent.get("coef", coef_count, torch.int16)
+    ent.get("state", max(nsub * STATE_WORDS, 4), torch.int32)
+    ent.get("small", ncounters + m, torch.int32)
+    ent.get("small_host", ncounters + m, torch.int32, "pinned")
     ent.upload_bytes = nbytes                                          # (what tools/time_jpeg.py reports)
     base = buf.stage.data_ptr()
     stage = buf.stage.numpy()
     rows, spans = (JpegImg * m).from_address(base), stage[s_off:s_off + 8 * m].view(np.int32).reshape(m, 2)
-    coef_at, block_at, row_at = 0, 0, 0
+    fill_rows(rows, own, range(0, 192 * m, 192), native)
+    row_at = 0
     for j, i in enumerate(native):
-        inf, r, (rc, segs, tabs) = infos[i], rows[j], scans[j]
-        r.coef_off, r.plane_off, r.q_off, r.block0, r.slot = coef_at, coef_at, 192 * j, block_at, i
-        r.height, r.width, r.ncomp, r.hsamp, r.vsamp = inf.height, inf.width, inf.ncomp, inf.hsamp, inf.vsamp
-        r.bw0, r.bh0, r.bw1, r.bh1 = inf.bw0, inf.bh0, inf.bw1, inf.bh1
+        inf, (rc, segs, tabs) = own[j], scans[j]
         stage[q_off + 384 * j:q_off + 384 * (j + 1)] = tabs[:384]
         stage[t_off + TAB_BYTES * j:t_off + TAB_BYTES * (j + 1)] = tabs[384:]
         spans[j] = (row_at, counts[j])
@@ -279,11 +248,8 @@ def _decode_device(buf: _Buffers, data, infos, native, threads: int, out: torch.
                 raise RuntimeError(f"vunet_jpeg_huffdec_rows failed on stream {i} (code {rc})")
             lo, hi = int(segs[0, 0]), int(segs[-1, 1])
             stage[b_off + offs[j] + lo:b_off + offs[j] + hi] = np.frombuffer(data[i], dtype=np.uint8, count=hi - lo, offset=lo)
-        coef_at, block_at, row_at = coef_at + inf.ncoef, block_at + inf.nblocks, row_at + counts[j]
-    buf.dev[:nbytes].copy_(buf.stage[:nbytes], non_blocking=True)
-    if buf.event is None:
-        buf.event = torch.cuda.Event()
-    buf.event.record()
+        row_at += counts[j]
+    buf.upload(nbytes)
     dev, host, stream = buf.dev.data_ptr(), ctypes.c_void_p(base), _stream()
     at = lambda off: ctypes.c_void_p(dev + off)                       # noqa: E731
     at_host = lambda off: ctypes.c_void_p(base + off)                 # noqa: E731
@@ -315,7 +281,7 @@ def _decode_device(buf: _Buffers, data, infos, native, threads: int, out: torch.
     _stats.update(rounds=rounds, launches=done, subsequences=nthreads, host_fallbacks=len(suspects))
     if suspects:
         # the host walk decides: its error is raised (the lowest index first), what it accepts goes into the image's slot
-        scratch = ent.host_coef(sum(infos[native[j]].ncoef for j in suspects))
+        scratch = ent.get("scratch", sum(own[j].ncoef for j in suspects), torch.int16, "pinned")
         qtab, put = np.empty(192, dtype=np.uint16), 0
         for j in suspects:
             i = native[j]
@@ -326,9 +292,7 @@ def _decode_device(buf: _Buffers, data, infos, native, threads: int, out: torch.
             ent.coef[rows[j].coef_off:rows[j].coef_off + infos[i].ncoef].copy_(scratch[put:put + infos[i].ncoef], non_blocking=True)
             put += infos[i].ncoef
         torch.cuda.current_stream().synchronize()                      # (the scratch is free again when the next call writes it)
-    n, hmax, wmax = (int(v) for v in out.shape[:3])
-    _call("vunet_jpeg_idct", _p(ent.coef), coef_count, at(q_off), m * 192, at(0), host, m, _p(buf.planes), plane_bytes, stream)
-    _call("vunet_jpeg_to_rgb", _p(buf.planes), plane_bytes, at(0), host, m, n, hmax, wmax, _p(out), stream)
+    _finish(buf, _p(ent.coef), coef_count, q_off, m, plane_bytes, out)
 
 
 def decode_batch(streams: Sequence, hmax: Optional[int] = None, wmax: Optional[int] = None, out: Optional[torch.Tensor] = None,
@@ -387,39 +351,14 @@ def decode_batch(streams: Sequence, hmax: Optional[int] = None, wmax: Optional[i
     key = (str(device), _stream().value if device.type == "cuda" else 0, tag)
     buf = _buffers.get(key)
     if buf is None:
-        buf = _buffers[key] = _Buffers(device)
+        buf = _buffers[key] = Arena(device, "planes")
+        buf.outs = {}
+    if out is None and (n, hm, wm) not in buf.outs:
+        buf.outs[n, hm, wm] = torch.zeros(n, hm, wm, 3, dtype=torch.uint8, device=device)
+    frames = buf.outs[n, hm, wm] if out is None else out
     native = [i for i in range(n) if infos[i] is not None]
-    m = len(native)
-    q_off = m * ctypes.sizeof(JpegImg)
-    c_off = _round(q_off + m * 384, 128)
-    coef_count = sum(infos[i].ncoef for i in native)
-    nbytes, plane_bytes = c_off + 2 * coef_count, max(coef_count, 16)
-    if not (m and entropy == "device"):      # (the device route sizes its own, smaller, upload)
-        buf.reserve(max(nbytes, 16), plane_bytes)
-    frames = buf.out(n, hm, wm) if out is None else out
-    if m and entropy == "device":
-        _decode_device(buf, data, infos, native, threads, frames)
-    elif m:
-        base = buf.stage.data_ptr()
-        rows = (JpegImg * m).from_address(base)
-        jobs, coef_at, block_at = [], 0, 0
-        for j, i in enumerate(native):
-            inf, r = infos[i], rows[j]
-            r.coef_off, r.plane_off, r.q_off, r.block0, r.slot = coef_at, coef_at, 192 * j, block_at, i
-            r.height, r.width, r.ncomp, r.hsamp, r.vsamp = inf.height, inf.width, inf.ncomp, inf.hsamp, inf.vsamp
-            r.bw0, r.bh0, r.bw1, r.bh1 = inf.bw0, inf.bh0, inf.bw1, inf.bh1
-            jobs.append((i, inf, base + c_off + 2 * coef_at, base + q_off + 384 * j))
-            coef_at, block_at = coef_at + inf.ncoef, block_at + inf.nblocks
-        fn = _lib.lib().vunet_jpeg_entropy_decode
-
-        def one(job):
-            i, inf, cptr, qptr = job
-            return fn(data[i], len(data[i]), ctypes.byref(inf), ctypes.c_void_p(cptr), ctypes.c_void_p(qptr))
-        codes = [one(j) for j in jobs] if threads == 1 or m == 1 else list(_pool(threads).map(one, jobs))
-        for (i, *_), rc in zip(jobs, codes):
-            if rc != 0:
-                raise _error(rc, i)
-        _launch(buf, m, nbytes, q_off, c_off, coef_count, plane_bytes, frames)
+    if native:
+        (_decode_device if entropy == "device" else _decode_host)(buf, data, infos, native, threads, frames)
     for i, f in foreign.items():
         frames[i, :f.shape[0], :f.shape[1]].copy_(torch.from_numpy(f))
     return frames, torch.tensor(sizes, dtype=torch.int32).reshape(n, 2)

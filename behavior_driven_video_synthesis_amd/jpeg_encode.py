@@ -6,8 +6,8 @@ csrc/jpeg_huff_enc.h, include/vunet_jpeg_enc.h):
 * colour conversion, chroma down-sampling, the forward DCT and the quantiser are two HIP launches for the whole batch, whatever the
   images' sizes, after ONE small upload (descriptors and tables), and ONE download of the quantised coefficients into a reused
   pinned buffer;
-* the entropy coder, a serial bit walk, runs on the host by default: the library's C++ on ``jpeg_decode``'s small thread pool
-  (ctypes releases the GIL);
+* the entropy coder, a serial bit walk, runs on the host by default: the library's C++ on the codec's small thread pool
+  (``jpeg_host.per_image``; ctypes releases the GIL);
 * ``entropy="device"`` keeps it on the GPU (csrc/jpeg_huff.hip): per block its bit count, a prefix sum per image, every block's
   bits packed at its offset, the bytes stuffed -- one launch per stage, two host waits -- and ONLY the scans' bytes are downloaded;
   the host writes the header and ``FF D9`` around them.  Same bytes as the host route;
@@ -28,13 +28,15 @@ Not done: progressive mode, restart markers.  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Optional
+import functools
+from collections import namedtuple
+from typing import Dict, List
 
 import numpy as np
 import torch
 
-from . import _lib
-from .jpeg_decode import MAX_SIDE, MAX_THREADS, JpegImg, JpegInfoC, _pool
+from . import _lib, jpeg_host
+from .jpeg_host import MAX_SIDE, MAX_THREADS, Arena, JpegImg, JpegInfoC, fill_rows, frame_paths, layout, per_image
 from .ops import _call, _p, _stream
 
 SUBSAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
@@ -48,90 +50,31 @@ REASONS = {ERR_CAPACITY: "the stream is longer than its output buffer",
            ERR_ARG: "an argument the library refuses"}
 
 
-class JpegEncodeError(ValueError):
+class JpegEncodeError(jpeg_host._CodecError):
     """``code``: the library's value; ``index``: the frame's place in the batch."""
-
-    def __init__(self, code: int, index: Optional[int] = None):
-        self.code, self.reason, self.index = int(code), REASONS.get(int(code), "unknown error"), index
-        where = "" if index is None else f"frame {index}: "
-        super().__init__(f"{where}{self.reason} (code {self.code})")
+    REASONS, WHAT = REASONS, "frame"
 
 
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("encode_batch needs the GPU (hand-written gfx950 kernels; no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
+_device = functools.partial(jpeg_host.device, "encode_batch")     # (a module attribute: the CPU tests replace it)
+# by (device, stream): the pinned descriptor / table block ``stage`` and its device mirror ``dev``, the component planes and the
+# coefficients on the device, the pinned coefficients ``coef_host`` and the streams' bytes ``out`` on the host
+_buffers: Dict[tuple, Arena] = {}
+# The device coder's arena, ``buf.entropy``.  ``up`` / ``up_dev``: the pinned block of what goes up and its device mirror -- tab_row
+# int32 [N] | spans int64 [N][2] | codes uint32 [rows][4][256].  ``small`` / ``small_host``: uint32 totals [r4(N)] | status [r4(2 N)] |
+# img_start [N + 1].  ``bits``: one word per block.  ``hist``: [N][4][256] with ``optimize``.  ``raw``: the unstuffed scans,
+# ``chunks`` one word per 1024 bytes of them, ``out`` / ``out_host`` the stuffed scans.
+_ENTROPY = "up up_dev small small_host bits hist hist_host raw chunks out out_host"
+# what one call hands its device steps.  ``steps``: the arguments of ``_transform`` and ``_launch`` behind the frames -- images,
+# channels, the upload's bytes, where its tables lie and how many entries they have, the coefficients of the batch; for the device
+# coder the infos, each image's host table pointer and ``optimize``
+_Plan = namedtuple("_Plan", "steps infos qptrs optimize")
 
 
-class _Buffers:
-    """The reused memory of one (device, stream): the pinned descriptor / table block and its device mirror, the component planes
-    and the coefficients on the device, the pinned coefficients and the streams' bytes on the host.  Grow-only: a second call at a
-    shape allocates nothing."""
-
-    def __init__(self, device: torch.device):
-        self.device, self.stage, self.dev, self.planes, self.coef, self.coef_host, self.event, self.out = \
-            device, None, None, None, None, None, None, None
-        self.entropy = None                                # the device coder's memory (``_Entropy``), made when first asked for
-
-    def reserve(self, up_bytes: int, coef_count: int, out_bytes: int):
-        pin = self.device.type == "cuda"
-        if self.stage is None or self.stage.numel() < up_bytes:
-            self.stage = torch.empty(up_bytes, dtype=torch.uint8, pin_memory=pin)
-            self.dev = torch.empty(up_bytes, dtype=torch.uint8, device=self.device)
-        if self.coef is None or self.coef.numel() < coef_count:
-            self.planes = torch.empty(coef_count, dtype=torch.uint8, device=self.device)
-            self.coef = torch.empty(coef_count, dtype=torch.int16, device=self.device)
-            self.coef_host = torch.empty(coef_count, dtype=torch.int16, pin_memory=pin)
-        if self.out is None or self.out.size < out_bytes:
-            self.out = np.empty(out_bytes, dtype=np.uint8)
-
-
-def _r4(n: int) -> int:
-    return (n + 3) // 4 * 4
-
-
-class _Entropy:
-    """The device coder's reused memory, grow-only like ``_Buffers``.  ``up`` / ``up_dev``: the pinned block of what goes up and
-    its device mirror -- tab_row int32 [N] | spans int64 [N][2] | codes uint32 [rows][4][256].  ``small`` / ``small_host``: uint32
-    totals [r4(N)] | status [r4(2 N)] | img_start [N + 1].  ``bits``: one word per block.  ``hist``: [N][4][256] with ``optimize``.
-    ``raw``: the unstuffed scans, ``chunks`` one word per 1024 bytes of them, ``out`` / ``out_host`` the stuffed scans."""
-
-    def __init__(self, device: torch.device):
-        self.device = device
-        self.up = self.up_dev = self.small = self.small_host = self.bits = self.hist = self.hist_host = None
-        self.raw = self.chunks = self.out = self.out_host = None
-
-    def _grow(self, name: str, count: int, dtype, host: bool = False):
-        cur = getattr(self, name)
-        if cur is None or cur.numel() < count:
-            kw = dict(pin_memory=self.device.type == "cuda") if host else dict(device=self.device)
-            setattr(self, name, torch.empty(count, dtype=dtype, **kw))
-
-    def layout(self, n: int, rows: int):
-        """-> (spans_off, codes_off, up_bytes) of ``up``; (status_at, start_at, words) of ``small``."""
-        spans_off = (4 * n + 15) // 16 * 16
-        codes_off = spans_off + 16 * n
-        return (spans_off, codes_off, codes_off + 4096 * rows), (_r4(n), _r4(n) + _r4(2 * n), _r4(n) + _r4(2 * n) + n + 1)
-
-    def reserve(self, n: int, rows: int, blocks: int, optimize: bool):
-        (_, _, up_bytes), (_, _, words) = self.layout(n, rows)
-        self._grow("up", up_bytes, torch.uint8, host=True)
-        self._grow("up_dev", up_bytes, torch.uint8)
-        self._grow("small", words, torch.int32)
-        self._grow("small_host", words, torch.int32, host=True)
-        self._grow("bits", blocks, torch.int32)
-        if optimize:
-            self._grow("hist", 1024 * n, torch.int32)
-            self._grow("hist_host", 1024 * n, torch.int32, host=True)
-
-    def reserve_streams(self, raw_bytes: int, out_cap: int):
-        self._grow("raw", raw_bytes, torch.uint8)
-        self._grow("chunks", raw_bytes // CHUNK, torch.int32)
-        self._grow("out", out_cap, torch.uint8)
-        self._grow("out_host", out_cap, torch.uint8, host=True)
-
-
-_buffers: Dict[tuple, _Buffers] = {}
+def _entropy_layout(n: int, rows: int):
+    """-> (spans_off, codes_off, up_bytes) of ``up``, in bytes; (status_at, start_at, words) of ``small``, in words."""
+    up, up_bytes = layout(("tab_row", 4 * n, 1), ("spans", 16 * n, 16), ("codes", 4096 * rows, 1))
+    small, words = layout(("totals", n, 1), ("status", 2 * n, 4), ("img_start", n + 1, 4))
+    return (up["spans"], up["codes"], up_bytes), (small["status"], small["img_start"], words)
 
 
 def clear_buffers() -> None:
@@ -146,25 +89,23 @@ def quant_tables(quality: int) -> np.ndarray:
     return q
 
 
-def _transform(buf: _Buffers, frames: torch.Tensor, m: int, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int) -> None:
+def _transform(buf: Arena, frames: torch.Tensor, m: int, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int) -> None:
     """One upload of the descriptors and tables and the two launches, on the current stream, not waited for.  The host copy of the
     descriptors is what the library checks before it launches."""
     n, hmax, wmax = (int(v) for v in frames.shape[:3])
-    buf.dev[:up_bytes].copy_(buf.stage[:up_bytes], non_blocking=True)
+    buf.upload(up_bytes)
     base = buf.dev.data_ptr()
     imgs, qtab, host = ctypes.c_void_p(base), ctypes.c_void_p(base + q_off), ctypes.c_void_p(buf.stage.data_ptr())
     _call("vunet_jpeg_from_rgb", _p(frames), n, hmax, wmax, channels, imgs, host, m, _p(buf.planes), coef_count, _stream())
     _call("vunet_jpeg_fdct", _p(buf.planes), coef_count, qtab, q_count, imgs, host, m, _p(buf.coef), coef_count, _stream())
 
 
-def _wait(buf: _Buffers) -> None:
-    if buf.event is None:
-        buf.event = torch.cuda.Event()
-    buf.event.record()
-    buf.event.synchronize()
+def _wait(buf: Arena) -> None:
+    buf.record()
+    buf.wait()
 
 
-def _launch(buf: _Buffers, frames: torch.Tensor, m: int, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int) -> None:
+def _launch(buf: Arena, frames: torch.Tensor, m: int, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int) -> None:
     """The host route's device step: ``_transform`` and the download of the coefficients into the pinned buffer, waited for."""
     _transform(buf, frames, m, channels, up_bytes, q_off, q_count, coef_count)
     buf.coef_host[:coef_count].copy_(buf.coef[:coef_count], non_blocking=True)
@@ -181,22 +122,29 @@ def _optimal_tables(lib, hist: np.ndarray, ntab: int):
     return 0, counts, symbols
 
 
-def _encode_on_device(buf: _Buffers, frames: torch.Tensor, channels: int, up_bytes: int, q_off: int, q_count: int, coef_count: int,
-                      infos: list, qptrs: list, optimize: bool) -> List[bytes]:
+def _encode_on_device(buf: Arena, frames: torch.Tensor, plan: _Plan) -> List[bytes]:
     """The device route behind ``_transform``: [histograms, a wait, tables up;] lengths and their prefix sums, a wait for the bit
     totals, the spans up, pack and stuff, one wait for the scans' lengths and bytes.  The host writes header and EOI around them."""
-    n, lib, stream = len(infos), _lib.lib(), _stream()
+    (n, channels, _, _, _, coef_count), infos, qptrs, optimize = plan
+    lib, stream = _lib.lib(), _stream()
     if any(i.nblocks * BLOCK_BITS >= 1 << 32 for i in infos):
         j = next(j for j, i in enumerate(infos) if i.nblocks * BLOCK_BITS >= 1 << 32)
         raise ValueError(f"frame {j}: {infos[j].nblocks} blocks may code to more bits than the device coder's 32-bit offsets count; "
                          f"use entropy=\"host\"")
     ent = buf.entropy
     if ent is None:
-        ent = buf.entropy = _Entropy(buf.device)
+        ent = buf.entropy = Arena(buf.device, _ENTROPY)
     rows, blocks, ntab = (n if optimize else 1), sum(i.nblocks for i in infos), (4 if channels == 3 else 2)
-    ent.reserve(n, rows, blocks, optimize)
-    (spans_off, codes_off, tab_bytes), (status_at, start_at, small_words) = ent.layout(n, rows)
-    _transform(buf, frames, n, channels, up_bytes, q_off, q_count, coef_count)
+    ent.layout = (spans_off, codes_off, tab_bytes), (status_at, start_at, small_words) = _entropy_layout(n, rows)
+    ent.get("up", tab_bytes, torch.uint8, "pinned")
+    ent.get("up_dev", tab_bytes, torch.uint8)
+    ent.get("small", small_words, torch.int32)
+    ent.get("small_host", small_words, torch.int32, "pinned")
+    ent.get("bits", blocks, torch.int32)
+    if optimize:
+        ent.get("hist", 1024 * n, torch.int32)
+        ent.get("hist_host", 1024 * n, torch.int32, "pinned")
+    _transform(buf, frames, *plan.steps)
     up = ent.up.numpy()
     tab_row, spans = up[:4 * n].view(np.int32), up[spans_off:spans_off + 16 * n].view(np.int64).reshape(n, 2)
     hbase, dbase = ent.up.data_ptr(), ent.up_dev.data_ptr()
@@ -236,7 +184,10 @@ def _encode_on_device(buf: _Buffers, frames: torch.Tensor, channels: int, up_byt
     if out_cap >= 1 << 32:
         raise ValueError(f"encode_batch: the batch's scans ({unstuffed} bytes before stuffing) pass the device coder's 32-bit offsets; "
                          f"use smaller batches or entropy=\"host\"")
-    ent.reserve_streams(raw_bytes, out_cap)
+    ent.get("raw", raw_bytes, torch.uint8)
+    ent.get("chunks", raw_bytes // CHUNK, torch.int32)
+    ent.get("out", out_cap, torch.uint8)
+    ent.get("out_host", out_cap, torch.uint8, "pinned")
     ent.up_dev[spans_off:codes_off].copy_(ent.up[spans_off:codes_off], non_blocking=True)
     spans_dev, spans_host = ctypes.c_void_p(dbase + spans_off), ctypes.c_void_p(hbase + spans_off)
     _call("vunet_jpeg_huff_pack", coef, coef_count, imgs, imgs_host, n, codes, rows, rows_dev, rows_host, _p(ent.bits), blocks,
@@ -262,6 +213,18 @@ def _encode_on_device(buf: _Buffers, frames: torch.Tensor, channels: int, up_byt
             raise JpegEncodeError(rc, j)
         res.append(header[:length.value].tobytes() + scans[starts[j]:starts[j + 1]].tobytes() + b"\xff\xd9")
     return res
+
+
+def _code_with_retry(code, dst: int, cap: int):
+    """``code(dst, cap, length)`` codes one stream into the ``cap`` bytes at the host address ``dst``; one that is longer (the
+    capacity code) is coded again into a buffer of the length the first call asked for.  -> (code, the stream's bytes)"""
+    length = ctypes.c_int64(0)
+    rc = code(ctypes.c_void_p(dst), cap, ctypes.byref(length))
+    if rc == ERR_CAPACITY:
+        own = np.empty(length.value, dtype=np.uint8)
+        rc = code(ctypes.c_void_p(own.ctypes.data), own.size, ctypes.byref(length))
+        return rc, own.tobytes()
+    return rc, ctypes.string_at(dst, length.value)
 
 
 def _sizes(sizes, n: int, h: int, w: int) -> List[tuple]:
@@ -328,79 +291,49 @@ def encode_batch(frames: torch.Tensor, quality=75, subsampling="4:2:0", sizes=No
     key = (str(device), _stream().value if device.type == "cuda" else 0)
     buf = _buffers.get(key)
     if buf is None:
-        buf = _buffers[key] = _Buffers(device)
+        buf = _buffers[key] = Arena(device, "planes coef coef_host out")
     q_off = n * ctypes.sizeof(JpegImg)
     levels = sorted(set(int(q) for q in quality))     # one [3][64] table block per distinct quality
     tables = np.concatenate([quant_tables(q)[[0, 1, 1]] for q in levels])
-    table_of = {q: 192 * i for i, q in enumerate(levels)}
+    table_of = [192 * levels.index(int(q)) for q in quality]
     up_bytes = q_off + tables.nbytes
-    coef_count = sum(i.ncoef for i in infos)
     caps = [1024 + 2 * i.ncoef for i in infos]        # two bytes per coefficient (0/255 noise at quality 100 takes 1.6); a longer one: below
-    buf.reserve(up_bytes, coef_count, sum(caps))
+    coef_count = sum(i.ncoef for i in infos)
+    buf.staging(up_bytes)
+    buf.get("planes", coef_count, torch.uint8)
+    buf.get("coef", coef_count, torch.int16)
+    buf.get("coef_host", coef_count, torch.int16, "pinned")
+    buf.get("out", sum(caps), torch.uint8, "host")
     base = buf.stage.data_ptr()
     rows = (JpegImg * n).from_address(base)
-    ctypes.memmove(base + q_off, tables.ctypes.data, tables.nbytes)
-    coef_at, block_at = 0, 0
-    for j, inf in enumerate(infos):
-        r = rows[j]
-        r.coef_off, r.plane_off, r.q_off, r.block0, r.slot = coef_at, coef_at, table_of[int(quality[j])], block_at, j
-        r.height, r.width, r.ncomp, r.hsamp, r.vsamp = inf.height, inf.width, inf.ncomp, inf.hsamp, inf.vsamp
-        r.bw0, r.bh0, r.bw1, r.bh1 = inf.bw0, inf.bh0, inf.bw1, inf.bh1
-        coef_at, block_at = coef_at + inf.ncoef, block_at + inf.nblocks
+    qbase = tables.ctypes.data
+    ctypes.memmove(base + q_off, qbase, tables.nbytes)
+    fill_rows(rows, infos, table_of, range(n))
+    qptrs = [qbase + 2 * t for t in table_of]
+    steps = (n, channels, up_bytes, q_off, tables.size, coef_count)
     if entropy == "device":
-        qptrs = [tables.ctypes.data + 2 * table_of[int(q)] for q in quality]
-        return _encode_on_device(buf, frames, channels, up_bytes, q_off, tables.size, coef_count, infos, qptrs, optimize)
-    _launch(buf, frames, n, channels, up_bytes, q_off, tables.size, coef_count)
-    fn, cbase, obase, qbase = lib.vunet_jpeg_entropy_encode, buf.coef_host.data_ptr(), buf.out.ctypes.data, tables.ctypes.data
-    offs = np.concatenate([[0], np.cumsum(caps)]).tolist()
-    coffs = np.concatenate([[0], np.cumsum([i.ncoef for i in infos])]).tolist()
-
-    def one_optimized(j):                                 # two passes over the pinned coefficients: count, then code
-        length, qptr, cptr = ctypes.c_int64(0), qbase + 2 * table_of[int(quality[j])], ctypes.c_void_p(cbase + 2 * coffs[j])
-        hist = np.empty((4, 256), dtype=np.uint32)
-        rc = lib.vunet_jpeg_symbol_histogram(cptr, ctypes.byref(infos[j]), hist.ctypes.data)
-        if rc == 0:
-            rc, counts, symbols = _optimal_tables(lib, hist, 4 if channels == 3 else 2)
-        if rc != 0:
-            return rc, b""
-        fn, out, cap = lib.vunet_jpeg_entropy_encode_tables, obase + offs[j], caps[j]
-        rc = fn(cptr, ctypes.byref(infos[j]), ctypes.c_void_p(qptr), counts.ctypes.data, symbols.ctypes.data, ctypes.c_void_p(out), cap,
-                ctypes.byref(length))
-        if rc == ERR_CAPACITY:
-            own = np.empty(length.value, dtype=np.uint8)
-            rc = fn(cptr, ctypes.byref(infos[j]), ctypes.c_void_p(qptr), counts.ctypes.data, symbols.ctypes.data, own.ctypes.data, own.size,
-                    ctypes.byref(length))
-            return rc, own.tobytes()
-        return rc, buf.out[offs[j]:offs[j] + length.value].tobytes()
+        return _encode_on_device(buf, frames, _Plan(steps, infos, qptrs, optimize))
+    _launch(buf, frames, *steps)
+    cbase, obase, ntab = buf.coef_host.data_ptr(), buf.out.data_ptr(), (4 if channels == 3 else 2)
+    coffs, offs = [2 * r.coef_off for r in rows], np.concatenate([[0], np.cumsum(caps)]).tolist()
 
     def one(j):
-        if optimize:
-            return one_optimized(j)
-        length, qptr = ctypes.c_int64(0), qbase + 2 * table_of[int(quality[j])]
-        rc = fn(ctypes.c_void_p(cbase + 2 * coffs[j]), ctypes.byref(infos[j]), ctypes.c_void_p(qptr), ctypes.c_void_p(obase + offs[j]),
-                caps[j], ctypes.byref(length))
-        if rc == ERR_CAPACITY:                            # the stream is coded again into a buffer of the length it asked for
-            own = np.empty(length.value, dtype=np.uint8)
-            rc = fn(ctypes.c_void_p(cbase + 2 * coffs[j]), ctypes.byref(infos[j]), ctypes.c_void_p(qptr), own.ctypes.data,
-                    own.size, ctypes.byref(length))
-            return rc, own.tobytes()
-        return rc, buf.out[offs[j]:offs[j] + length.value].tobytes()
-    res = [one(j) for j in range(n)] if threads == 1 or n == 1 else list(_pool(threads).map(one, range(n)))
+        cptr, info, qptr = ctypes.c_void_p(cbase + coffs[j]), ctypes.byref(infos[j]), ctypes.c_void_p(qptrs[j])
+        if not optimize:
+            return _code_with_retry(lambda *dst: lib.vunet_jpeg_entropy_encode(cptr, info, qptr, *dst), obase + offs[j], caps[j])
+        hist = np.empty((4, 256), dtype=np.uint32)        # two passes over the pinned coefficients: count, then code
+        rc = lib.vunet_jpeg_symbol_histogram(cptr, info, hist.ctypes.data)
+        if rc == 0:
+            rc, counts, symbols = _optimal_tables(lib, hist, ntab)
+        if rc != 0:
+            return rc, b""
+        return _code_with_retry(lambda *dst: lib.vunet_jpeg_entropy_encode_tables(cptr, info, qptr, counts.ctypes.data, symbols.ctypes.data, *dst),
+                                obase + offs[j], caps[j])
+    res = per_image(one, range(n), threads)
     for j, (rc, _) in enumerate(res):
         if rc != 0:
             raise JpegEncodeError(rc, j)
     return [data for _, data in res]
-
-
-def _paths(pattern: str, count: int, start: int = 0) -> List[str]:
-    """``pattern`` with one ``%d``-style or one ``{}``-style field -> ``count`` file names from index ``start``."""
-    if "%" in pattern:
-        names = [pattern % (start + i) for i in range(count)]
-    else:
-        names = [pattern.format(start + i) for i in range(count)]
-    if len(set(names)) != count:
-        raise ValueError(f"pattern {pattern!r} names {count} files alike: it needs an index field such as %06d or {{:06d}}")
-    return names
 
 
 def save_images(pattern: str, frames: torch.Tensor, quality: int = 75, subsampling: str = "4:2:0", sizes=None, start: int = 0,
@@ -408,7 +341,7 @@ def save_images(pattern: str, frames: torch.Tensor, quality: int = 75, subsampli
     """``encode_batch`` and one file per frame: ``pattern % index`` (``"img_%06d.jpg"``, the reference's frame names) or
     ``pattern.format(index)``, indices from ``start``.  -> the paths written."""
     streams = encode_batch(frames, quality, subsampling, sizes, threads, entropy, optimize)
-    paths = _paths(pattern, len(streams), start)
+    paths = frame_paths(pattern, len(streams), start)
     for path, data in zip(paths, streams):
         with open(path, "wb") as f:
             f.write(data)

@@ -85,7 +85,7 @@ def save_videos(pattern: str, frames: torch.Tensor, fps=12, quality: int = 75, s
     if not torch.is_tensor(frames) or frames.dim() != 5 or frames.shape[4] != 3:
         raise ValueError(f"save_videos: frames uint8 [B, T, H, W, 3] expected, got {tuple(getattr(frames, 'shape', ()))}")
     b, t, h, w = (int(v) for v in frames.shape[:4])
-    paths = jpeg_encode._paths(pattern, b, start)
+    paths = jpeg_encode.frame_paths(pattern, b, start)
     streams = jpeg_encode.encode_batch(frames.reshape(b * t, h, w, 3), quality, subsampling, threads=threads, entropy=entropy,
                                        optimize=optimize)
     for i, path in enumerate(paths):

@@ -264,3 +264,27 @@ def test_metrics_and_the_vunet_trainer_take_jpeg_batches():
     assert la == lb and la == la
     for (k, p), (_, q) in zip(a.vunet.state_dict().items(), b.vunet.state_dict().items()):
         assert torch.equal(p, q), k
+
+
+def test_each_route_issues_its_library_calls_in_order(monkeypatch):
+    """H: the launches of a call, by name and in order, for the two smallest streams of different sampling: the host route is the two
+    launches; the device route is one sync call per ``SYNC_BATCH`` launches, the three launches behind them and the same two."""
+    from behavior_driven_video_synthesis_amd import jpeg_decode as J
+    by_size = sorted(NAMES, key=lambda n: len(FIX["cases"][n]["data"]))
+    sampling = lambda n: J.parse(FIX["cases"][n]["data"])[3:5]   # noqa: E731
+    names = [by_size[0], next(n for n in by_size if sampling(n) != sampling(by_size[0]))]
+    seen, real = [], J._call
+
+    def recorded(name, *args):
+        seen.append(name.replace("vunet_jpeg_", ""))
+        real(name, *args)
+    monkeypatch.setattr(J, "_call", recorded)
+    frames, hw = J.decode_batch(_streams(names), tag="h")
+    _check(frames, hw, names)
+    assert seen == ["idct", "to_rgb"]
+    del seen[:]
+    frames, hw = J.decode_batch(_streams(names), tag="h", entropy="device")
+    _check(frames, hw, names)
+    syncs = -(-J.last_stats()["launches"] // J.SYNC_BATCH)
+    assert syncs >= 1 and seen == ["huffdec_sync"] * syncs + ["huffdec_blocks", "huffdec_write", "huffdec_dc", "idct", "to_rgb"]
+    J.clear_buffers()

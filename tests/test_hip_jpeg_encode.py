@@ -244,3 +244,31 @@ def test_skeleton_video_goes_through_save_videos_one_file_per_row():
             fps, streams = V.read_mjpeg(path)            # (raises where chunk sizes or the index disagree with the file)
             assert fps == 12.0 and len(streams) == 4
             assert streams == [E.encode(host[row, t], 95, "4:2:0") for t in range(4)], row
+
+
+def test_each_route_issues_its_library_calls_in_order(monkeypatch):
+    """I: the library calls of a call, by name and in order, for two images of different size and sampling in one stack: one
+    ``encode_info`` per image, one ``quant_tables`` per distinct quality and the two launches on every route; behind them nothing
+    on the host route, the device coder's four calls on the other, with the histogram in place of the fixed code words under
+    ``optimize``."""
+    from behavior_driven_video_synthesis_amd import jpeg_encode as J
+    J.clear_buffers()
+    g = np.random.default_rng(11)
+    frames = torch.from_numpy(g.integers(0, 256, size=(2, 17, 23, 3), dtype=np.uint8)).cuda()
+    kw = dict(sizes=[(16, 16), (17, 23)], subsampling=["4:2:0", "4:4:4"])
+    seen, real = [], J._call
+
+    def recorded(name, *args):
+        seen.append(name.replace("vunet_jpeg_", ""))
+        real(name, *args)
+    monkeypatch.setattr(J, "_call", recorded)
+    head = ["encode_info", "encode_info", "quant_tables", "from_rgb", "fdct"]
+    tails = {("host", False): [], ("host", True): [], ("device", False): ["code_words", "huff_lengths", "huff_pack", "huff_stuff"],
+             ("device", True): ["huff_count", "huff_lengths", "huff_pack", "huff_stuff"]}
+    got = {}
+    for (entropy, optimize), tail in tails.items():
+        del seen[:]
+        got[entropy, optimize] = J.encode_batch(frames, entropy=entropy, optimize=optimize, **kw)
+        assert seen == head + tail, (entropy, optimize)
+    assert got["host", False] == got["device", False] and got["host", True] == got["device", True]
+    J.clear_buffers()

@@ -248,10 +248,7 @@ def main():
                     wall(lambda: list(ex.map(one, range(N))), a.rounds), "ms")
         # ---- upload and launches
         (bufs,) = [b for k, b in J._buffers.items() if k[2] == q]
-        m, q_off = N, N * ctypes.sizeof(J.JpegImg)
-        c_off = J._round(q_off + N * 384, 128)
-        count = N * ncoef
-        nbytes = c_off + 2 * count
+        m, nbytes, q_off, c_off, count, _ = bufs.layout             # (the plan of the call above)
         base, host = bufs.dev.data_ptr(), ctypes.c_void_p(bufs.stage.data_ptr())
         args = (ctypes.c_void_p(base + c_off), count, ctypes.c_void_p(base + q_off), N * 192, ctypes.c_void_p(base), host, m)
         res = compare([("upload", lambda: bufs.dev[:nbytes].copy_(bufs.stage[:nbytes], non_blocking=True)),

@@ -187,7 +187,7 @@ def main():
                          f"({100 * (1 - opt_bytes / plain_bytes):.1f} % smaller); both routes == Pillow's optimize=True, byte for byte")
             print(lines[-1], flush=True)
             ent, blocks = bufs.entropy, n * info.nblocks
-            (spans_off, codes_off, _), (_, start_at, _) = ent.layout(n, 1)          # the plain call above left one row of codes
+            (spans_off, codes_off, _), (_, start_at, _) = ent.layout                # the plain call above left one row of codes
             hb, db = ent.up.data_ptr(), ent.up_dev.data_ptr()
             spans = ent.up.numpy()[spans_off:spans_off + 16 * n].view(np.int64).reshape(n, 2)
             unstuffed = int(((spans[:, 1] + 7) // 8).sum())
