@@ -194,6 +194,13 @@ __global__ __launch_bounds__(256) void cls_cell_bwd_kernel(float* __restrict__ g
   dh_prev[g * dh_net + e] = d * zg;
 }
 
+// a * b + c in two roundings, as torch's mul_ / add_ pair leaves it.  hipcc contracts a * b + c into one fma by default, and HIP's
+// __fmul_rn / __fadd_rn are the plain operators, which it contracts just the same: the pragma is what pins the roundings.
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b + c;
+}
+
 __global__ __launch_bounds__(256) void cls_sgd_kernel(float* __restrict__ params, const float* __restrict__ grad, float* __restrict__ buf,
                                                       int S, float lr, float momentum, const int32_t* __restrict__ it_dev) {
   const int g = blockIdx.y;
@@ -205,9 +212,9 @@ __global__ __launch_bounds__(256) void cls_sgd_kernel(float* __restrict__ params
     for (int s = 1; s < S; ++s) gv += G[(int64_t)s * VUNET_CLS_P];
   const int64_t o = (int64_t)g * VUNET_CLS_P + e;
   // torch.optim.SGD (dampening 0, no nesterov): buf = g first, then buf = momentum buf + g;  p = p + (-lr) buf
-  const float b = *it_dev == 0 ? gv : __fadd_rn(__fmul_rn(momentum, buf[o]), gv);
+  const float b = *it_dev == 0 ? gv : mul_then_add(momentum, buf[o], gv);
   buf[o] = b;
-  params[o] = __fadd_rn(params[o], __fmul_rn(-lr, b));
+  params[o] = mul_then_add(-lr, b, params[o]);
 }
 
 __global__ __launch_bounds__(256) void cls_reg_loss_kernel(const float* __restrict__ pred, int ldp, int64_t pred_net,
@@ -350,6 +357,7 @@ extern "C" int vunet_seq_cls_reg_loss(const float* pred, int32_t ldp, int64_t pr
 extern "C" int vunet_seq_cls_adam(float* p, float* m, float* v, const float* g, int32_t nets, int64_t n, const vunet_seq_adam_hp* hp,
                                   void* stream) {
   if (!p || !m || !v || !g || !hp || nets < 1 || nets > 65535 || n < 1 || !hp->lr_dev || !hp->step_dev) return VUNET_ERR_ARG;
+  if (hp->beta1 < 0.f || hp->beta1 >= 1.f || hp->beta2 < 0.f || hp->beta2 >= 1.f || hp->eps < 0.f) return VUNET_ERR_ARG;
   VUNET_LAUNCH(cls_adam_kernel, dim3((unsigned)((n + 255) / 256), nets), dim3(256), 0, (hipStream_t)stream, p, m, v, g, n, *hp);
   return vunet_check_launch();
 }

@@ -82,7 +82,8 @@ __global__ __launch_bounds__(64) void seq_reg_fc4_adam_kernel(const float* __res
                                                               float* __restrict__ v4, float* __restrict__ bm4, float* __restrict__ bv4,
                                                               vunet_seq_adam_hp hp) {
   const int c = blockIdx.x, lane = threadIdx.x;
-  const int idx = idx_dev[k];
+  int idx = idx_dev[k];
+  idx = idx < 0 ? 0 : (idx >= VUNET_SEQ_REG_T ? VUNET_SEQ_REG_T - 1 : idx);   // the column seq_reg_gather_kernel read
   const AdamResolved h = adam_resolve(hp);
   const float g = wave_sum(lane < Bp ? dzc[(size_t)lane * VUNET_SEQ_REG_C + c] : 0.f);
   if (lane < VUNET_SEQ_REG_T) {

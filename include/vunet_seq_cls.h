@@ -98,12 +98,14 @@ int vunet_seq_cls_sgd(float* params, const float* grad, float* buf, int32_t nets
 /* The regressor's loss (one workgroup per net): target = xo[b bs + r][start_dev[g]] (xo [N][T][51], b = *it_dev % nb);
  * d_r = ||pred[r] - target||, loss = mean_r d_r -> loss_out[g][*it_dev + slot_off]; dpred = (pred - target) / (d_r bs) (0 where
  * d_r == 0).  xc != NULL: de = mean_r ||xc[b bs + r][start] - target|| -> de_out[g][*it_dev + slot_off].
- * pred and dpred: [bs][ldp] per net. */
+ * pred and dpred: [bs][ldp] per net; columns 51 .. ldp of pred are not read and those of dpred are not written (they keep
+ * what the caller put there). */
 int vunet_seq_cls_reg_loss(const float* pred, int32_t ldp, int64_t pred_net, const float* xo, const float* xc, int32_t T, int32_t bs,
                            int32_t nb, const int32_t* start_dev, const int32_t* it_dev, int32_t slot_off, float* loss_out,
                            float* de_out, int32_t ld_curve, float* dpred, int32_t nets, void* stream);
 
-/* torch.optim.Adam (defaults but lr) on n contiguous floats per net: p, m, v, g with net stride n. */
+/* torch.optim.Adam (defaults but lr) on n contiguous floats per net: p, m, v, g with net stride n.  beta1 / beta2 outside
+ * [0, 1) and eps < 0 are refused, as vunet_seq_reg_fc4_adam refuses them. */
 int vunet_seq_cls_adam(float* p, float* m, float* v, const float* g, int32_t nets, int64_t n, const vunet_seq_adam_hp* hp, void* stream);
 
 /* One thread: *it_dev += 1 (it_dev != NULL), *step_dev += 1 (step_dev != NULL). */

@@ -53,7 +53,8 @@ int vunet_seq_reg_loss(const float* pred, int32_t ldp, const float* tgt, int32_t
 int vunet_seq_reg_cat_bwd(const float* raw, int32_t S, int32_t Bp, int32_t H4, const float* cat, float* dz3, float* dzc, void* stream);
 
 /* Adam on fc4 (w4 [128][50], b4 [128]) with its gradient formed in place: g[c] = sum_{b < Bp} dzc[b][c] (batch order) is the
- * bias gradient and column idx_dev[k] of the weight gradient; every other column's gradient is 0 (Adam still moves it). */
+ * bias gradient and column idx_dev[k] (clamped into [0, 50), as vunet_seq_reg_gather reads it) of the weight gradient; every
+ * other column's gradient is 0 (Adam still moves it).  beta1 / beta2 outside [0, 1) and eps < 0 are refused. */
 int vunet_seq_reg_fc4_adam(const float* dzc, int32_t Bp, const int32_t* idx_dev, int32_t k, float* w4, float* b4, float* m4, float* v4,
                            float* bm4, float* bv4, const vunet_seq_adam_hp* hp, void* stream);
 

@@ -781,3 +781,26 @@ def test_every_sequence_kernel_entry_point_is_held_or_listed():
     named = {n for n in names if re.search(r"\b" + n + r"\b", rest)}
     assert not (named & set(not_held)), sorted(named & set(not_held))
     assert names - named - set(not_held) == set(), sorted(names - named - set(not_held))
+
+
+def test_every_classifier_study_and_regressor_entry_point_is_held_or_listed():
+    """Census: every ``extern "C" int vunet_*`` defined in csrc/seq_cls.hip and csrc/seq_reg.hip is named in
+    tests/test_hip_cls_reg_kernels.py (a per-kernel float64 / bit-exact test) or listed in that file's NOT_HELD dict with a reason;
+    NOT_HELD names only real entry points that the file does not otherwise name."""
+    import ast
+    csrc = os.path.join(ROOT, "behavior_driven_video_synthesis_amd", "csrc")
+    names = set()
+    for f in ("seq_cls.hip", "seq_reg.hip"):
+        names |= set(re.findall(r'extern "C" int (vunet_\w+)\s*\(', open(os.path.join(csrc, f)).read()))
+    assert len(names) >= 14, sorted(names)      # the two files define 14 today: 9 + 5
+    src = open(os.path.join(ROOT, "tests", "test_hip_cls_reg_kernels.py")).read()
+    tree = ast.parse(src)
+    node = next(n for n in tree.body if isinstance(n, ast.Assign) and any(getattr(t, "id", None) == "NOT_HELD" for t in n.targets))
+    not_held = ast.literal_eval(node.value)
+    lines = src.splitlines()
+    rest = "\n".join(lines[:node.lineno - 1] + lines[node.end_lineno:])
+    assert all(isinstance(r, str) and r.strip() for r in not_held.values())
+    assert set(not_held) <= names, sorted(set(not_held) - names)
+    named = {n for n in names if re.search(r"\b" + n + r"\b", rest)}
+    assert not (named & set(not_held)), sorted(named & set(not_held))
+    assert names - named - set(not_held) == set(), sorted(names - named - set(not_held))

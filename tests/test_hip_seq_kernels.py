@@ -25,17 +25,11 @@ import random
 import pytest
 import torch
 
-from hip_parity_utils import assert_ulps
+from hip_parity_utils import (DIV_U, ERR_ARG, ERR_UNSUPPORTED, EXP_U, LOG_U, NAN, SIG_U, SQRT_U, TANH_U, TINY, U, Outs, _adam64,
+                              _adam_hp, _d, _f32, _refused, assert_same, assert_ulps)
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
-TINY = 2.0 ** -126
-NAN = float("nan")
-GUARD = 256                  # sentinels after every output
-SENT = -7777.0
-ERR_ARG, ERR_UNSUPPORTED = -1, -3        # include/vunet_hip.h
-EXP_U, LOG_U, TANH_U, SQRT_U, DIV_U, SIG_U = 6 * U, 6 * U, 10 * U, 6 * U, 5 * U, 12 * U   # (module docstring)
 SLOPE = float(torch.tensor(0.01, dtype=torch.float32))   # 0.01f, the kernels' LeakyReLU slope
 
 NOT_HELD = {
@@ -64,60 +58,8 @@ def _cdiv(a, b):
     return (a + b - 1) // b
 
 
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def assert_same(a, b, name=""):
-    """Bit for bit (NaN equal to NaN of the same bits, -0 different from +0)."""
-    a, b = _bits(a), _bits(b)
-    assert a.shape == b.shape, f"{name}: shape {tuple(a.shape)} vs {tuple(b.shape)}"
-    if not torch.equal(a, b):
-        bad = torch.nonzero(a != b)
-        raise AssertionError(f"{name}: {bad.shape[0]} elements differ; first at {bad[0].tolist()}")
-
-
-_KEEP = []      # device copies of inputs stay referenced until the launches that read them have run (Outs.check)
-
-
-def _d(t):
-    if t is None:
-        return None
-    t = t if t.is_cuda else t.cuda()
-    _KEEP.append(t)
-    return t
-
-
-class Outs:
-    """Output buffers: NaN-filled (or pre-loaded), each followed by GUARD sentinels that ``check`` wants untouched."""
-
-    def __init__(self):
-        self.bufs = []
-
-    def new(self, *shape, fill=NAN, dtype=torch.float32):
-        n = int(math.prod(shape))
-        flat = torch.empty(n + GUARD, dtype=dtype, device="cuda")
-        if fill is not None:
-            flat[:n] = fill
-        flat[n:] = SENT
-        self.bufs.append((flat, n))
-        return flat[:n].view(*shape)
-
-    def load(self, t):
-        out = self.new(*t.shape, fill=None, dtype=t.dtype)
-        out.copy_(t)
-        return out
-
-    def check(self):
-        torch.cuda.synchronize()
-        for k, (flat, n) in enumerate(self.bufs):
-            assert bool((flat[n:] == SENT).all()), f"guard band of output {k} ({n} elements) was written"
-        _KEEP.clear()
-
-
-def _refused(ops, code, name, *args):
-    with pytest.raises(RuntimeError, match=rf"{name} failed with code {code}$"):
-        ops._call(name, *args)
+# (Outs, assert_same, _d, _refused, the constants, _adam_hp and _adam64 live in tests/hip_parity_utils.py: tests/
+# test_hip_cls_reg_kernels.py works under the same conventions)
 
 
 # ------------------------------------------------------------------------------------------------ tile-major images
@@ -1037,18 +979,6 @@ def test_actnorm_init_vs_float64(B, C):
     assert_ulps(scale, want, want * want * (dstd + U * (std + eps)) + DIV_U * want + TINY, "scale")
 
 
-def _adam_hp(T, lr, step, b1, b2, eps, wd, resolved=True):
-    lr_dev = torch.tensor([lr], dtype=torch.float64, device="cuda")
-    step_dev = torch.tensor([step], dtype=torch.int64, device="cuda")
-    res = torch.zeros(2, device="cuda") if resolved else None
-    hp = T.SeqAdamHp(lr_dev.data_ptr(), step_dev.data_ptr(), b1, b2, eps, wd, None if res is None else res.data_ptr())
-    return hp, (lr_dev, step_dev, res)
-
-
-def _f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
 @pytest.mark.parametrize("step", [0, 999])
 def test_adam_tick_vs_float64(step):
     """vunet_seq_adam_tick: ++step; resolved = {lr / (1 - b1^t), 1 / sqrt(1 - b2^t)} formed in double and rounded to fp32 once:
@@ -1068,28 +998,6 @@ def test_adam_tick_vs_float64(step):
     ops._call("vunet_seq_adam_tick", ops._p(st), None, b1, b2, None, ops._stream())
     o.check()
     assert int(st.item()) == t + 1
-
-
-def _adam64(p, g, m, v, step_size, inv_sqrt_bc2, b1, b2, eps, wd, dg):
-    """seq_adam.h's update in float64 from the fp32 state and the fp32 constants, with its bound given the gradient's (dg):
-    m: (1 - b1) dg + 3 U (b1 |m| + (1 - b1) |g|); v: (1 - b2) 2 |g| dg + 4 U (b2 v + (1 - b2) g^2); denom = sqrtf(v) k + eps: v's
-    error through the root + (sqrtf + 2 roundings) relative; p -= step (m / denom): the quotient's parts + (division + product +
-    the difference) relative."""
-    b1, b2, eps, wd = _f32(b1), _f32(b2), _f32(eps), _f32(wd)
-    p, g, m, v = p.double(), g.double(), m.double(), v.double()
-    g = g + wd * p
-    dg = dg + 2 * U * wd * p.abs()
-    m2 = b1 * m + (1 - b1) * g
-    dm = (1 - b1) * dg + 3 * U * (b1 * m.abs() + (1 - b1) * g.abs())
-    v2 = b2 * v + (1 - b2) * g * g
-    dv = (1 - b2) * (2 * g.abs() * dg + dg * dg) + 4 * U * (b2 * v + (1 - b2) * g * g)
-    root = v2.sqrt()
-    droot = torch.minimum(dv / (2 * root.clamp_min(TINY)), dv.sqrt())
-    denom = root * inv_sqrt_bc2 + eps
-    ddenom = droot * inv_sqrt_bc2 + (SQRT_U + 2 * U) * denom
-    upd = step_size * m2 / denom
-    dupd = step_size * dm / denom + upd.abs() * (ddenom / denom + DIV_U + 2 * U)
-    return (p - upd, dupd + U * (p.abs() + upd.abs()) + TINY), (m2, dm + TINY), (v2, dv + TINY)
 
 
 @pytest.mark.parametrize("C", [1, 65, 130])
